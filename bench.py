@@ -10,9 +10,16 @@ decode -> score top-k + rotated NMS) over one batch of ONE synthetic frame (tool
 BASELINE.json configs[1]) whose points are already resident in HBM.  Multi-GPU = replicas only: frames are sharded over
 ranks, no data-path collective; value = frames of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with `roofline` (VFE+scatter kernel group, HBM bound — the group BASELINE.json's metric
-names), `roofline_mfma` (BEV backbone + head, fp32 matrix-core bound) and `cpu_baseline` (the CPU oracle timed on this
-box's host cores on a bounded sample; rank 0, N=1 only).
+A plain run sets up, warms up, times the K steps of the headline path and prints ONE JSON line on rank 0 (`value`,
+`ms_per_step`, the configuration).  --full adds everything else to that line, as separate runs inside the same process: the
+latency mode, the per-stage probe, `roofline` (VFE+scatter kernel group, HBM bound — the group BASELINE.json's metric names),
+`roofline_mfma` (BEV backbone + head, fp32 matrix-core bound), `cpu_baseline` (the CPU oracle timed on this box's host cores
+on a bounded sample; rank 0, N=1 only) with the parity gates, the two-frames-per-replay pipeline, the other BASELINE.json
+configs and the train steps (--alt: the opt-in precisions as well).
+
+--dump-outputs DIR writes, after the timed steps, the detections the last timed step returned (pred_boxes, pred_scores,
+pred_labels, selected, pred_count of its one frame) as DIR/<name>.npy in float32 / float64.  Frames and weights are seeded,
+so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -39,6 +46,35 @@ def make_batch(frame, device):
     return {"points": torch.from_numpy(pts).to(device),
             "point_frame_offsets": torch.tensor([0, len(frame)], dtype=torch.int32, device=device),
             "batch_size": 1}
+
+
+DUMP_KEYS = ("pred_boxes", "pred_scores", "pred_labels", "selected")
+
+
+def host_detections(out):
+    """What a caller of the timed path receives from one step, on the host: per frame of the batch the live rows (pred_count of
+    them) of the padded `sync=False` detections — the rows post_processing(sync=True) returns — in float32 (boxes, scores) or
+    float64 (labels, anchor ids, count).  Synchronises; call it after the clock has stopped and before the next replay."""
+    if out is None:
+        raise SystemExit("bench.py --dump-outputs: the last timed step returned no frame yet (the frame pipeline needs warmup + steps "
+                         ">= its depth)")
+    recs = out[0] if isinstance(out, tuple) else out
+    torch.cuda.synchronize()
+    res = {}
+    for b, rec in enumerate(recs):
+        n = int(rec["pred_count"].item())
+        tag = "" if len(recs) == 1 else f"frame{b}_"
+        for k in DUMP_KEYS:
+            a = rec[k][:n].detach().cpu().numpy()
+            res[tag + k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        res[tag + "pred_count"] = np.array([n], np.float64)
+    return res
+
+
+def write_outputs(arrays, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def conv_flops(model, H, W):
@@ -542,20 +578,27 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity gates (profiling runs); the JSON line then carries parity = null")
-    ap.add_argument("--no-extras", action="store_true", help="skip the batch-16 / dense-scene group lines and the train-step line")
-    ap.add_argument("--probe-steps", type=int, default=30, help="extra untimed steps with per-stage HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (latency mode, per-stage probe, rooflines, CPU baseline + parity gates, "
+                         "two frames per replay, other configs, train steps); off by default: a plain run times the headline path only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the parity gates (profiling runs); the JSON line then carries parity = null")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the batch-16 / dense-scene group lines and the train-step line")
+    ap.add_argument("--probe-steps", type=int, default=30, help="(--full) extra untimed steps with per-stage HIP events")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying hipGraphs")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="one whole-frame hipGraph per step (frame latency = step) instead of the 3-stage frame pipeline")
     ap.add_argument("--conv-precision", choices=["fp32", "bf16x3", "bf16x6"], default="fp32",
                     help="fp32: exact fp32 matrix-core convolutions; bf16x3: 3-term split-bf16 trunk/SFM convolutions")
-    ap.add_argument("--skip-single", action="store_true", help="profiling: do not time the single-graph latency mode")
-    ap.add_argument("--alt", action="store_true", help="also time the opt-in modes (bf16x6 / bf16x3 split-precision convolutions, direct "
-                    "fp32 convolutions) and report them as `alt_precision` (never `value`); off by default: three more pipelines")
+    ap.add_argument("--skip-single", action="store_true", help="(--full) profiling: do not time the single-graph latency mode")
+    ap.add_argument("--alt", action="store_true", help="(--full) also time the opt-in modes (bf16x6 / bf16x3 split-precision convolutions, "
+                    "direct fp32 convolutions) and report them as `alt_precision` (never `value`); off by default: three more pipelines")
     ap.add_argument("--cls-bias", type=float, default=-4.59511985013459, help="conv_cls.bias of the synthetic weights")
     args = ap.parse_args()
+    if args.alt and not args.full:
+        ap.error("--alt is part of the full run: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: this process becomes the launcher — N fresh child processes, one rank per GPU (reference:
@@ -595,6 +638,7 @@ def main():
     nx, ny = int(ds.grid_size[0]), int(ds.grid_size[1])
 
     dt_local = [0.0]          # this rank's own time of the last timed() call
+    last_out = [None]         # what the last timed step of the last timed() call returned
 
     def barrier():
         distributed.barrier(device)
@@ -606,10 +650,15 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(batches[(args.warmup + i) % N_POOL])
+            last_out[0] = step(batches[(args.warmup + i) % N_POOL])
         barrier()
         dt_local[0] = time.perf_counter() - t0
         return distributed.max_over_ranks(dt_local[0], device)
+
+    def dump_headline():
+        """--dump-outputs: the headline's last timed step, read before anything replays the graphs that hold it."""
+        if args.dump_outputs is not None and rank == 0:
+            write_outputs(host_detections(last_out[0]), args.dump_outputs)
 
     alt = None
     timed_object = None
@@ -617,17 +666,23 @@ def main():
         if args.no_graph:
             mode = "eager launches"
             dt = timed(lambda b: model(dict(b), sync=False))
+            dump_headline()
             dt_single = None
         else:
-            # latency mode: one whole-frame hipGraph per step (a1..a8 of ONE frame, serial)
-            dt_single = None if (args.skip_single and not args.no_pipeline) else timed(detector.GraphedForward(model, batches[0]))
+            # latency mode: one whole-frame hipGraph per step (a1..a8 of ONE frame, serial); the headline with --no-pipeline,
+            # otherwise a --full figure
+            skip_single = (args.skip_single or not args.full) and not args.no_pipeline
+            dt_single = None if skip_single else timed(detector.GraphedForward(model, batches[0]))
             mode, dt = "one whole-frame hipGraph replay per step (frame latency = 1 step)", dt_single
-            if not args.no_pipeline:
+            if args.no_pipeline:
+                dump_headline()
+            else:
                 # throughput mode: every step is one graph replay that encodes frame k, convolves frames k-1 / k-2 (two halves of
                 # the backbone) and runs top-k + NMS of frame k-3 on separate streams; K timed steps retire exactly K frames (the
                 # pipeline is full before and after the timed region; the warm-up fills it), nothing is skipped
                 pipe = detector.PipelinedForward(model, batches[0])
                 dt = timed(pipe)
+                dump_headline()
                 for _ in pipe.flush():
                     pass
                 pipe.check_status()                       # (synchronising) no index kernel gave up a wait during the timed replays
@@ -722,16 +777,17 @@ def main():
 
             return alt
 
-        # ---- per-stage probe (untimed): HIP events on the launch stream ----
+        # ---- per-stage probe (untimed, --full only): HIP events on the launch stream ----
+        probe_steps = args.probe_steps if args.full else 0
         stage = np.zeros(3)
         n_pillars = 0
         out = None
-        staged = StagedGraphs(model, batches[0]) if args.probe_steps > 0 else None
+        staged = StagedGraphs(model, batches[0]) if probe_steps > 0 else None
         # The probe steps are enqueued back to back and read after ONE synchronize at the end: while the GPU runs step i the
         # host has long enqueued step i + 1, so the interval between two events holds GPU time only (with a synchronize
         # per step the first interval also counted the host's graph-launch latency, ~10-15 us of idle GPU).
         evs, pillars_dev = [], torch.zeros((), dtype=torch.int64, device=device)
-        for i in range(args.probe_steps):
+        for i in range(probe_steps):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             out = staged.run(batches[i % N_POOL], ev)
             pillars_dev += out[2]["voxel_offsets"][-1]
@@ -739,8 +795,8 @@ def main():
         torch.cuda.synchronize()
         for ev in evs:
             stage += [ev[k].elapsed_time(ev[k + 1]) for k in range(3)]
-        n_pillars = float(pillars_dev.item()) / max(args.probe_steps, 1)
-        stage /= max(args.probe_steps, 1)
+        n_pillars = float(pillars_dev.item()) / max(probe_steps, 1)
+        stage /= max(probe_steps, 1)
         # The VFE+scatter group alone: R consecutive replays of its captured graph between two HIP events (a different
         # frame per repetition), so that the interval is the group's kernels and the gaps between them — a single replay between two
         # events also counts the ~15 us the command processor needs to start a graph launch, which a frame pays once for
@@ -750,14 +806,14 @@ def main():
             # eight captured copies of the group, one per pool frame, on ONE persistent canvas pair: consecutive replays see
             # consecutive DIFFERENT frames (the stale-cell clear of the previous frame's pillars is inside the interval)
             group_us = GroupGraphs(model, batches).time_us(rounds=5)
-        kept = int(out[0][0]["pred_count"].item()) if args.probe_steps > 0 else -1
+        kept = int(out[0][0]["pred_count"].item()) if probe_steps > 0 else -1
 
     rccl_ranks = distributed.ranks_seen(device)                       # all-reduce of ones over RCCL
     per_rank_fps = [round(args.steps / t, 2) for t in distributed.gather_floats(dt_rank, device)]
     # N > 1: the exchange step the path really has — BASELINE.json configs[3]: hvpr 3-class, batch 8 per GPU, data parallel over
     # RCCL (one gradient all-reduce of ~62 MB per step, reference tools/train.py:143-145) — timed on every rank
     train_ddp = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         staged = None
         torch.cuda.empty_cache()
         train_ddp = train_step_line(device, "3class", 8, ddp=True)
@@ -766,6 +822,29 @@ def main():
         return
 
     fps = world * args.steps / dt
+    config = {"workload": "hvpr_car.yaml batch=1 forward-only, a1..a8 (on-GPU voxelize, pillar VFE, memory read-out + "
+                          "scatter, BEV backbone, head + decode, score top-k + rotated-BEV NMS); frames sharded "
+                          "over ranks, replicas only",
+              "frame": f"synthetic 64-beam LiDAR, ~{raw_pts} raw points -> range mask -> {n_pts} sampled points, "
+                       + (f"~{int(n_pillars)} pillars, " if args.full else "") + f"grid {nx}x{ny}x1", "global_batch": world,
+              "weights": f"deterministic synthetic (seed 0), BN stats randomised, cls bias {args.cls_bias:.3f}"}
+    if args.full:
+        config["nms_candidates_kept"] = kept                            # (per-stage probe)
+    config["launch"] = mode
+    res = {
+        "metric": "KITTI frames/sec/GPU (fwd, ~20k pts); VFE+scatter achieved HBM GB/s vs peak",
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "rccl_ranks_seen": rccl_ranks, "per_rank_frames_per_s": per_rank_fps,
+        "config": config,
+    }
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        distributed.finalize()
+        return
+
+    # ---- --full: everything beyond the headline ----
     # algorithmic bytes of the VFE+scatter group per frame (SURVEY.md §8d / BASELINE.md §6): raw points read once +
     # dense canvases written once (zeros included) + VFE weights and memory bank read once
     group_bytes_ = group_bytes(n_pts, nx, ny, 1)
@@ -800,19 +879,7 @@ def main():
     in_frame_us = round(sum(members.values()), 2) if len(members) >= 3 else None
     isolated_us = group_s * 1e6
     profile_consistent = None if in_frame_us is None else bool(abs(in_frame_us - isolated_us) <= 0.25 * isolated_us)
-    res = {
-        "metric": "KITTI frames/sec/GPU (fwd, ~20k pts); VFE+scatter achieved HBM GB/s vs peak",
-        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "rccl_ranks_seen": rccl_ranks, "per_rank_frames_per_s": per_rank_fps,
-        "config": {"workload": "hvpr_car.yaml batch=1 forward-only, a1..a8 (on-GPU voxelize, pillar VFE, memory read-out + "
-                               "scatter, BEV backbone, head + decode, score top-k + rotated-BEV NMS); frames sharded "
-                               "over ranks, replicas only",
-                   "frame": f"synthetic 64-beam LiDAR, ~{raw_pts} raw points -> range mask -> {n_pts} sampled points, "
-                            f"~{int(n_pillars)} pillars, grid {nx}x{ny}x1", "global_batch": world,
-                   "weights": f"deterministic synthetic (seed 0), BN stats randomised, cls bias {args.cls_bias:.3f}",
-                   "nms_candidates_kept": kept, "launch": mode},
+    res.update({
         "single_graph_latency_mode": None if dt_single is None else {"value": round(world * args.steps / dt_single, 2),
                                                                      "unit": "frames/s", "ms_per_frame": round(1e3 * dt_single / args.steps, 4)},
         "stage_ms": {"voxelize+vfe+memory+scatter": round(float(stage[0]), 4), "backbone+head+decode": round(float(stage[1]), 4),
@@ -858,7 +925,7 @@ def main():
                                   "the algorithm.  peak = 157.3 TFLOP/s at 2.4 GHz; under this load the shader clock measured 2.02 GHz "
                                   "(DESIGN.md §4.2), i.e. ~132 TFLOP/s attainable.  alt_precision[mode=conv_algo_direct] is the same frame "
                                   "with every layer on the direct kernel"},
-    }
+    })
     res["train_step_ddp"] = train_ddp
     # cpu_baseline + parity gates while the timed object is still alive: the oracle's frames go through it as well
     gates = None

@@ -1,4 +1,4 @@
-"""CPU: the committed bench line of the round (profiles/r*_bench_line.json, the stdout of `python bench.py` on an MI355X) carries every
+"""CPU: the committed bench line of the round (profiles/r*_bench_line.json, the stdout of `python bench.py --full` on an MI355X) carries every
 field of the driver's contract — and the numbers inside it are consistent with each other."""
 import glob
 import json

@@ -115,6 +115,17 @@ def test_bn_relu_train_mode_matches_torch(shape, relu):
     _close(db, dbr, what="dbeta")
 
 
+@contextlib.contextmanager
+def _without_miopen():
+    """torch's native convolution / BatchNorm kernels instead of MIOpen's."""
+    was = torch.backends.cudnn.enabled
+    torch.backends.cudnn.enabled = False
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.enabled = was
+
+
 def test_backbone_training_forward_backward_hip_equals_torch_autograd():
     """The whole BaseBEVBackbone_Scale training forward (two streams through shared weights, SFM steps with the shared gate,
     multi-call BatchNorm running statistics) and its backward: own kernels vs torch autograd of the same module."""
@@ -135,7 +146,10 @@ def test_backbone_training_forward_backward_hip_equals_torch_autograd():
     ref64 = copy.deepcopy(a).double()                      # the yardstick: the same module in float64 through torch autograd
     import torch_forms
     for name, m, mode, dt in (("hip", a, "hip", torch.float32), ("torch", b, "torch", torch.float32), ("f64", ref64, "torch", torch.float64)):
-        with (torch_forms.patched(m) if mode == "torch" else contextlib.nullcontext()):
+        # the torch passes run on torch's native convolutions (MIOpen off): MIOpen picks its solvers by timing them, and the winner
+        # moved torch fp32's distance to float64 on this chain — the bar below — by up to 9x from run to run
+        native = _without_miopen() if mode == "torch" else contextlib.nullcontext()
+        with (torch_forms.patched(m) if mode == "torch" else contextlib.nullcontext()), native:
             ins = [t.detach().clone().to(dt).requires_grad_(True) for t in (sp, spp, sc)]
             d = m({"spatial_features": ins[0], "spatial_features_point": ins[1], "spatial_scale_features": ins[2]})
             f, fp = d["spatial_features_2d"], d["spatial_features_point_2d"]
@@ -151,9 +165,10 @@ def test_backbone_training_forward_backward_hip_equals_torch_autograd():
     def nerr(x, ref):
         return float((x.double() - ref).norm() / ref.norm().clamp_min(1e-300))
     # Gradients come out of a 25-layer chain of train-mode BatchNorm backward passes on a sparse canvas — an ill-conditioned
-    # chain: torch's own fp32 kernels land between 3e-4 and 1.3e-3 of float64 on it depending on the solvers MIOpen picks on the
-    # box.  Norm-wise bounds: 5e-3 for parameter gradients, 1e-2 for the canvas gradients at the far end of the chain, never
-    # worse than 3x torch fp32.  The element-wise 1e-3 parity of every single operator is in the tests above.
+    # chain: torch's fp32 kernels land between 4e-4 and 3.5e-3 (median) of float64 on it depending on the solvers MIOpen picks, and
+    # at 9.6e-4 (median) .. 6.7e-3 (max) on torch's native convolutions, the yardstick used here.  Norm-wise bounds: 5e-3 for
+    # parameter gradients, 1e-2 for the canvas gradients at the far end of the chain, never worse than 3x torch fp32.  The
+    # element-wise 1e-3 parity of every single operator is in the tests above.
     rows = [(f"input grad {k}", nerr(gh, gr), nerr(gt, gr)) for k, (gh, gt, gr) in enumerate(zip(h[2], t[2], r[2]))]
     assert set(h[3]) == set(r[3])
     for k in r[3]:
@@ -171,7 +186,7 @@ def test_backbone_training_forward_backward_hip_equals_torch_autograd():
     # a ReLU network in fp32: any two implementations disagree on a few of the millions of ReLU decisions (a pre-activation within
     # round-off of zero), and every flipped decision moves the gradients behind it by a finite amount.  Each operator on its own is
     # at fp32 round-off of float64 (1e-7 .. 1e-6 norm-wise, tools/train_precision_probe.py — the same as torch fp32); on this
-    # 25-layer chain torch's own fp32 kernels sit at 2e-3 (median) .. 5e-3 (max) of float64.  The bar: the same regime as torch
+    # 25-layer chain torch's native fp32 kernels sit at 9.6e-4 (median) .. 6.7e-3 (max) of float64.  The bar: the same regime as torch
     # fp32 — within 3x of its median and of its maximum — and no tensor beyond 3e-2.
     assert np.median(eh) < 3 * np.median(et) + 1e-3, (np.median(eh), np.median(et))
     assert eh.max() < 3 * et.max() + 2e-3 and eh.max() < 3e-2, (eh.max(), et.max())

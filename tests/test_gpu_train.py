@@ -121,8 +121,6 @@ def test_config3_full_train_step_batch16():
     train branch, three canvases, two-stream backbone, head, target assigner, losses, backward, clip, Adam-onecycle) at the FULL
     size — 16 frames of 16384 points per step.  Finite loss, EVERY trainable parameter receives a finite gradient, the step
     changes the weights, peak memory is recorded (and bounded well below the 288 GB of the part)."""
-    import json
-    import os
     cfg = hvpr_car_cfg()
     model = detector.build_network(cfg.MODEL, 1, detector.SyntheticDataset(cfg, training=True))
     synthetic_weights.load_synthetic(model, seed=3, cls_bias=-4.595)
@@ -154,9 +152,6 @@ def test_config3_full_train_step_batch16():
     assert np.isfinite(float(loss2))
     peak = torch.cuda.max_memory_allocated() / 2**30
     print(f"config 3 (batch 16): loss {float(loss):.4f} -> {float(loss2):.4f}, peak memory {peak:.1f} GiB")
-    os.makedirs("gpurun_out", exist_ok=True)
-    json.dump({"config": "hvpr_car full train step, batch 16", "loss": [float(loss), float(loss2)], "peak_mem_GiB": round(peak, 1)},
-              open(os.path.join("gpurun_out", "config3_train_step_test.json"), "w"))
     assert peak < 200.0
 
 

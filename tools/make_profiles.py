@@ -1,9 +1,9 @@
 """Turn the raw rocprofv3 CSVs under gpurun_out/<run> (written by tools/run_profiles.sh on the GPU box) into the committed
 summaries under profiles/.   usage: python tools/make_profiles.py <run dir under gpurun_out> <round prefix, e.g. r03>
 
-  profiles/<r>_kernel_stats_single_graph.csv   rocprofv3 --kernel-trace --stats of `bench.py --no-pipeline` (latency mode, branch streams)
+  profiles/<r>_kernel_stats_single_graph.csv   rocprofv3 --kernel-trace --stats of `bench.py --full --no-pipeline` (latency mode, branch streams)
   profiles/<r>_kernel_stats_serial.csv         the same with HVPR_BEV_STREAMS=1: every kernel on one stream, durations do not overlap
-  profiles/<r>_kernel_stats_pipeline.csv       same of the default `bench.py` (frame pipeline; also holds the latency-mode and probe replays)
+  profiles/<r>_kernel_stats_pipeline.csv       same of `bench.py --full` (frame pipeline; also holds the latency-mode and probe replays)
   profiles/<r>_kernel_stats_group_b16.csv      the VFE+scatter group alone at hvpr_car batch 16 (tools/bench_group.py --only16)
   profiles/<r>_kernel_stats_group_dense.csv    ... on the dense scene, BASELINE.json configs[4] (--only-dense);  ..._group_b1.csv: hvpr_car batch 1 (--car1)
   profiles/<r>_pmc_sq_group_b16.csv            SQ counters per kernel of that run (two --pmc passes), averaged per dispatch
@@ -92,7 +92,7 @@ for k in sorted(f_tot, key=lambda k: -(2 * f_tot[k] + w_tot.get(k, 0))):
             conv_parts[c] += b
             break
 with open(os.path.join(OUT, f"{R}_pmc_hbm_traffic.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE  and  --pmc WRITE_SIZE (two separate passes) of: HVPR_BEV_STREAMS=1 bench.py --no-pipeline --steps 10 --warmup 3 --no-cpu-baseline --no-extras --probe-steps 0\n")
+    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE  and  --pmc WRITE_SIZE (two separate passes) of: HVPR_BEV_STREAMS=1 bench.py --full --no-pipeline --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-parity --probe-steps 0\n")
     f.write("# per-frame HBM bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 * calls_per_frame ; the factor 2 is the gfx950 FETCH_SIZE correction (MI355X_MICROARCH.md, HBM section); WRITE_SIZE is used as reported\n")
     w = csv.writer(f)
     w.writerow(["kernel", "calls_per_frame", "FETCH_SIZE_KB_per_call", "WRITE_SIZE_KB_per_call", "hbm_bytes_per_frame"])

@@ -3,7 +3,7 @@
 O=gpurun_out/${1:-wsq}
 export TMPDIR=/tmp HVPR_BEV_STREAMS=1
 mkdir -p $O
-B="--no-pipeline --no-cpu-baseline --no-extras --steps 10 --warmup 3 --probe-steps 0"
+B="--full --no-pipeline --no-cpu-baseline --no-extras --steps 10 --warmup 3 --probe-steps 0"
 timeout 280 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VALU_MFMA_MOPS_F32 --output-format csv -d $O/p1 -o s -- python3 bench.py $B > $O/p1.log 2>&1
 timeout 280 rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $O/p2 -o s -- python3 bench.py $B > $O/p2.log 2>&1
 timeout 280 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/p3 -o s -- python3 bench.py $B > $O/p3.log 2>&1
