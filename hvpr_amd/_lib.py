@@ -6,7 +6,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 6          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
+ABI_VERSION = 7          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
 LIB_PATH = os.environ.get("HVPR_AMD_LIB", os.path.join(_HERE, "libhvpr_amd.so"))   # override: kernel experiments only
 
 _c = ctypes
@@ -53,11 +53,9 @@ SIGNATURES = {
     "hvpr_three_interpolate_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hvpr_three_interpolate_grad_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hvpr_group_rows_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "hvpr_group_rows_grad_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "hvpr_max_samples_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P, _P]),
     "hvpr_max_samples_grad_f32": (_I, [_P, _P, _c.c_longlong, _I, _I, _P, _P]),
     "hvpr_fp_rows_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "hvpr_fp_rows_grad_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "hvpr_spatial_gate_train_workspace_bytes": (_Z, [_I, _I, _I]),
     "hvpr_spatial_gate_train_fwd_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "hvpr_spatial_gate_train_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
@@ -65,10 +63,9 @@ SIGNATURES = {
     "hvpr_conv2d_wgrad_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "hvpr_bn_workspace_bytes": (_Z, [_c.c_longlong, _I]),
     "hvpr_bn_stats_nhwc_f32": (_I, [_P, _c.c_longlong, _I, _F, _P, _P, _P, _P, _Z, _P]),
-    "hvpr_bn_relu_fwd_nhwc_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _P]),
-    "hvpr_bn_relu_bwd_nhwc_f32": (_I, [_P, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "hvpr_bn_relu_bwd_sums_nhwc_f32": (_I, [_P, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
-    "hvpr_bn_relu_bwd_apply_nhwc_f32": (_I, [_P, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _c.c_double, _P]),
+    "hvpr_bn_relu_fwd_nhwc_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "hvpr_bn_relu_bwd_sums_nhwc_f32": (_I, [_P, _I, _I, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "hvpr_bn_relu_bwd_apply_nhwc_f32": (_I, [_P, _I, _I, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _c.c_double, _P]),
     "hvpr_memory_train_workspace_bytes": (_Z, [_I]),
     "hvpr_memory_train_fwd_f32": (_I, [_P, _c.c_longlong, _P, _I, _F, _P, _P, _P, _Z, _P]),
     "hvpr_memory_train_bwd_f32": (_I, [_P, _P, _c.c_longlong, _P, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
@@ -102,8 +99,6 @@ SIGNATURES = {
     "hvpr_conv2d_wino_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "hvpr_conv2d_wino_stats_rows": (_I, [_I, _I, _I]),
     "hvpr_conv2d_s2_dgrad_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "hvpr_bn_relu_fwd_slice_nhwc_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _I, _I, _P]),
-    "hvpr_bn_relu_bwd_slice_nhwc_f32": (_I, [_P, _I, _I, _P, _c.c_longlong, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "hvpr_bn_train_affine_f32": (_I, [_P, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hvpr_bn_finalize_partials_f32": (_I, [_P, _I, _I, _c.c_longlong, _F, _P, _P, _P, _P]),
     "hvpr_conv2d_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P]),

@@ -11,8 +11,9 @@ Activations are NHWC tensors (N, H, W, C) — what torch calls channels_last —
   deconv (k == s)     forward  the 1x1 GEMM with s*s*Cout columns + pixel shuffle in the epilogue (ConvTranspose2d, :177-188)
                       backward 1x1 dgrad / wgrad on the space-to-depth view of the gradient
   bn_relu             train-mode BatchNorm (batch statistics, differentiated through) + ReLU: hvpr_bn_stats_nhwc_f32,
-                      hvpr_bn_relu_fwd_nhwc_f32, hvpr_bn_relu_bwd_nhwc_f32; running statistics updated like nn.BatchNorm2d
-                      (momentum, unbiased variance, one update per CALL — SURVEY.md B.5).
+                      hvpr_bn_relu_fwd_nhwc_f32, hvpr_bn_relu_bwd_sums / _apply_nhwc_f32 (_bn_forward / _bn_backward, which
+                      sfm_step and bn_relu_cat share); running statistics updated like nn.BatchNorm2d (momentum, unbiased
+                      variance, one update per CALL — SURVEY.md B.5).
 """
 import os
 
@@ -26,7 +27,7 @@ _ws_cache = {}
 # ---------------------------------------------------------------------------------------------- SyncBatchNorm
 # tools/train.py:119-120 turns every BatchNorm into torch.nn.SyncBatchNorm when --sync_bn is given (off by default).  The
 # BatchNorms of this path do not run torch's kernels, so convert_sync_batchnorm would not synchronise anything; instead the
-# statistics of bn_relu / sfm_step below — every BatchNorm2d of the two-stream backbone and head, the point stream's shared MLPs
+# statistics of bn_relu / sfm_step / bn_relu_cat below — every BatchNorm2d of the two-stream backbone and head, the point stream's shared MLPs
 # and the VFE scale stream — are all-reduced over a process group when one is set here: per-channel (sum x, sum x^2, count) in the
 # forward, (sum dy, sum dy * xhat) in the backward, in float64, one all-reduce each (RCCL on the GPU; gloo runs the same code).
 # The two BatchNorm1d inside the fused PFN kernels (csrc/vfe_train.hip) and SpatialAttention's one-channel BatchNorm
@@ -181,58 +182,79 @@ def bn_statistics(z, eps, partials=None):
     return sync_moments(s1, s2, P, eps, sg[0])
 
 
-def _affine(mean, var, invstd, gamma, beta, count, running):
-    """scale = gamma * invstd, shift = beta - mean * scale for the normalising kernel.  running = (running_mean, running_var,
-    num_batches_tracked, momentum) of the nn.BatchNorm2d, or None: updated like the module does in train mode — in the same launch
-    (hvpr_bn_train_affine_f32) when the moments are this rank's own; the SyncBatchNorm path keeps its torch arithmetic and updates
-    them in _update_running.  Returns (scale, shift, running statistics are done)."""
-    if _sync_group() is not None or torch.is_tensor(count):
+def _affine(mean, var, invstd, gamma, beta, count, bn):
+    """scale = gamma * invstd, shift = beta - mean * scale for the normalising kernel, and the running statistics of the
+    nn.BatchNorm2d `bn` updated like the module does in train mode: in the same launch (hvpr_bn_train_affine_f32) when the moments
+    are this rank's own and the momentum is a number, else by _update_running (SyncBatchNorm — count is then the global count, a
+    tensor — keeps its torch arithmetic; momentum None averages cumulatively)."""
+    if torch.is_tensor(count):
         scale = (gamma.detach() * invstd).contiguous()
-        return scale, (beta.detach() - mean * scale).contiguous(), False
+        shift = (beta.detach() - mean * scale).contiguous()
+        _update_running(bn, mean, var, count)
+        return scale, shift
     scale, shift = torch.empty_like(mean), torch.empty_like(mean)
-    rm = rv = nbt = None
-    m = mu = 0.0
-    if running is not None and running[3] is not None:
-        rm, rv, nbt, m = running
-        mu = m * count / max(count - 1, 1)
+    running = _running_of(bn)
+    rm, rv, nbt, m = running if running is not None else (None, None, None, 0.0)
+    mu = m * count / max(count - 1, 1)
     check(lib().hvpr_bn_train_affine_f32(mean.data_ptr(), var.data_ptr(), invstd.data_ptr(), mean.numel(), kernels._ptr(gamma.detach(), torch.float32, "gamma"),
                                          kernels._ptr(beta.detach(), torch.float32, "beta"), float(m), float(mu), kernels._ptr(rm, torch.float32, "running_mean"),
                                          kernels._ptr(rv, torch.float32, "running_var"), kernels._ptr(nbt, torch.int64, "num_batches_tracked"),
                                          scale.data_ptr(), shift.data_ptr(), kernels._stream()), "hvpr_bn_train_affine_f32")
-    if rm is not None:      # the kernel wrote the buffers through raw pointers: let torch's version counters know (no launch)
+    if running is None:
+        _update_running(bn, mean, var, count)
+    else:                   # the kernel wrote the buffers through raw pointers: let torch's version counters know (no launch)
         for t in (rm, rv, nbt):
             torch.autograd.graph.increment_version(t)
-    return scale, shift, rm is not None
+    return scale, shift
 
 
 def _running_of(bn):
-    """The running buffers of `bn` for _affine (None when it keeps none or averages cumulatively: _update_running then does it)."""
+    """The running buffers of `bn` for hvpr_bn_train_affine_f32 (None when it keeps none or averages cumulatively)."""
     if not bn.track_running_stats or bn.momentum is None or bn.running_mean is None:
         return None
     return (bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum))
 
 
-def _bn_backward(dy, z, P, C, scale, shift, mean, invstd, relu, gate, dgate, count):
-    """dz, d gamma, d beta of the train-mode BatchNorm (+ ReLU, + SFM gate) — one kernel pair per rank, or, with SyncBatchNorm,
-    the two halves with the all-reduce of the two sums between them (count: the global count of the forward)."""
+def _bn_forward(z, gamma, beta, eps, partials, bn, relu, gate=None, resid=None, out=None, out_coff=0):
+    """relu(BN_train(z)) of contiguous z (N,H,W,C) — with gate (N,H,W,1) and resid (N,H,W,C): gate * relu(BN_train(z)) + resid: batch
+    statistics (from the producing convolution's partials when it left them), scale / shift and `bn`'s running statistics (_affine),
+    then one hvpr_bn_relu_fwd_nhwc_f32 launch into out[..., out_coff:out_coff + C] (out None: a new tensor).
+    -> (y, (scale, shift, mean, invstd), count): the output, what _bn_backward needs besides z, and the count of the statistics."""
+    C = z.shape[-1]
+    P = z.numel() // C
+    mean, var, invstd, count = bn_statistics(z, eps, partials)
+    scale, shift = _affine(mean, var, invstd, gamma, beta, count, bn)
+    y = torch.empty_like(z) if out is None else out
+    check(lib().hvpr_bn_relu_fwd_nhwc_f32(z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(), 1 if relu else 0,
+                                          kernels._ptr(gate, torch.float32, "gate"), kernels._ptr(resid, torch.float32, "resid"),
+                                          kernels._ptr(y, torch.float32, "out"), y.shape[-1], out_coff, kernels._stream()),
+          "hvpr_bn_relu_fwd_nhwc_f32")
+    return y, (scale, shift, mean, invstd), count
+
+
+def _bn_backward(dy, dy_cstride, dy_coff, z, scale, shift, mean, invstd, relu, gate, count):
+    """dz, d gamma, d beta and d gate (None without a gate) of _bn_forward from dy[..., dy_coff:dy_coff + C] (dy_cstride channels per
+    pixel): the local sums, then dz from them and 1 / P — or, with SyncBatchNorm (count: the global count of the forward), from their
+    all-reduce over the global batch.  The parameter gradients are this rank's sums (DistributedDataParallel averages them)."""
+    C = z.shape[-1]
+    P = z.numel() // C
     dz = torch.empty_like(z)
     dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
+    dgate = torch.empty_like(gate) if gate is not None else None
     ws = _workspace(lib().hvpr_bn_workspace_bytes(P, C), z.device)
+    common = (kernels._ptr(dy, torch.float32, "dy"), dy_cstride, dy_coff, z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(),
+              mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0, kernels._ptr(gate))
+    check(lib().hvpr_bn_relu_bwd_sums_nhwc_f32(*common, dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
+          "hvpr_bn_relu_bwd_sums_nhwc_f32")
     sg = _sync_group()
-    if sg is None or not torch.is_tensor(count):
-        check(lib().hvpr_bn_relu_bwd_nhwc_f32(kernels._ptr(dy, torch.float32, "dy"), z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(),
-                                              mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0, kernels._ptr(gate), kernels._ptr(dgate),
-                                              dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              kernels._stream()), "hvpr_bn_relu_bwd_nhwc_f32")
-        return dz, dgamma, dbeta
-    check(lib().hvpr_bn_relu_bwd_sums_nhwc_f32(kernels._ptr(dy, torch.float32, "dy"), z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(),
-                                               mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0, kernels._ptr(gate), dgamma.data_ptr(),
-                                               dbeta.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_bn_relu_bwd_sums_nhwc_f32")
-    dg_t, db_t = sync_backward_sums(dgamma, dbeta, count, sg[0])          # over the global batch, divided by its count
-    check(lib().hvpr_bn_relu_bwd_apply_nhwc_f32(dy.data_ptr(), z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                                                invstd.data_ptr(), 1 if relu else 0, kernels._ptr(gate), kernels._ptr(dgate), dz.data_ptr(),
-                                                dg_t.data_ptr(), db_t.data_ptr(), 1.0, kernels._stream()), "hvpr_bn_relu_bwd_apply_nhwc_f32")
-    return dz, dgamma, dbeta          # parameter gradients: this rank's sums (DistributedDataParallel averages them)
+    if sg is not None and torch.is_tensor(count):
+        dg_t, db_t = sync_backward_sums(dgamma, dbeta, count, sg[0])          # over the global batch, divided by its count
+        inv_n = 1.0
+    else:
+        dg_t, db_t, inv_n = dgamma, dbeta, 1.0 / P
+    check(lib().hvpr_bn_relu_bwd_apply_nhwc_f32(*common, kernels._ptr(dgate), dz.data_ptr(), dg_t.data_ptr(), db_t.data_ptr(), inv_n,
+                                                kernels._stream()), "hvpr_bn_relu_bwd_apply_nhwc_f32")
+    return dz, dgamma, dbeta, dgate
 
 
 _wino_pack_cache = {}
@@ -279,13 +301,19 @@ def _pack_wino(weight, adjoint):
                    lambda: kernels.pack_conv_wino(weight.detach(), relu=False, px_groups=_wino_groups(), adjoint=adjoint))
 
 
+def _winograd(weight, stride, adjoint):
+    """The Winograd kernel takes the convolution: 3x3 stride 1, output channels % 4, input channels % 8 (adjoint: of the data
+    gradient), unless HVPR_CONV_ALGO=direct."""
+    cout, cin = (weight.shape[1], weight.shape[0]) if adjoint else (weight.shape[0], weight.shape[1])
+    return weight.shape[2] == 3 and stride == 1 and kernels.conv_algo() == "winograd" and cout % 4 == 0 and cin % 8 == 0
+
+
 def conv_fwd_raw(x, weight, stride=1, adjoint=False, stats=False):
     """x (N,H,W,Cin) -> conv(x, weight) (N,OH,OW,Cout), no bias / activation.  weight (Cout,Cin,k,k), k in {1,3}, pad (k-1)/2.
     stats: return (z, partials) — partials = the batch statistics' per-tile sums when the Winograd kernel produced them, else None.
     adjoint: weight is the (Cin', Cout', 3, 3) filter of the layer whose data gradient is wanted and x its output gradient.
     Stride-1 3x3: the Winograd kernel (packed on the device per call) unless HVPR_CONV_ALGO=direct."""
-    if weight.shape[2] == 3 and stride == 1 and kernels.conv_algo() == "winograd" and weight.shape[1 if adjoint else 0] % 4 == 0 \
-            and weight.shape[0 if adjoint else 1] % 8 == 0:
+    if _winograd(weight, stride, adjoint):
         g = _wino_groups()
         partials = None
         if stats and g == 1:
@@ -401,40 +429,24 @@ class _Deconv(torch.autograd.Function):
 
 class _BNReLU(torch.autograd.Function):
     """y = relu(BN_train(z)); with (gate (N,H,W,1), resid (N,H,W,C)): y = gate * relu(BN_train(z)) + resid — the SFM step
-    x_att = attention(sfm(x_att), y) + x_att (base_bev_backbone.py:250-255) in the same two kernels."""
+    x_att = attention(sfm(x_att), y) + x_att (base_bev_backbone.py:250-255) in the same kernels."""
 
     @staticmethod
-    def forward(ctx, z, gamma, beta, eps, relu, gate, resid, partials=None, running=None):
+    def forward(ctx, z, gamma, beta, eps, relu, gate, resid, partials, bn):
         z = z.contiguous()
-        C = z.shape[-1]
-        P = z.numel() // C
-        dev = z.device
-        mean, var, invstd, count = bn_statistics(z, eps, partials)
-        scale, shift, ctx.running_done = _affine(mean, var, invstd, gamma, beta, count, running)
-        y = torch.empty_like(z)
         if gate is not None:
             gate, resid = gate.detach().contiguous(), resid.detach().contiguous()
-            assert gate.numel() == P and resid.shape == z.shape
-        check(lib().hvpr_bn_relu_fwd_nhwc_f32(z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(), 1 if relu else 0,
-                                              kernels._ptr(gate, torch.float32, "gate"), kernels._ptr(resid, torch.float32, "resid"),
-                                              y.data_ptr(), kernels._stream()), "hvpr_bn_relu_fwd_nhwc_f32")
-        ctx.save_for_backward(z, scale, shift, mean, invstd, gate)
-        ctx.relu, ctx.count = relu, count
-        cnt = count if torch.is_tensor(count) else torch.tensor(float(count), dtype=torch.float64)      # (a HOST tensor: no copy to the device, no sync)
-        ctx.mark_non_differentiable(mean, var, cnt)
-        ctx.set_materialize_grads(False)     # (their gradients would arrive as zero tensors: one allocation + fill each, per call)
-        return y, mean, var, cnt
+            assert gate.numel() == z.numel() // z.shape[-1] and resid.shape == z.shape
+        y, saved, ctx.count = _bn_forward(z, gamma, beta, eps, partials, bn, relu, gate, resid)
+        ctx.save_for_backward(z, *saved, gate)
+        ctx.relu = relu
+        return y
 
     @staticmethod
-    def backward(ctx, dy, _dm, _dv, _dc):
-        if dy is None:
-            return (None,) * 9
+    def backward(ctx, dy):
         z, scale, shift, mean, invstd, gate = ctx.saved_tensors
         dy = dy.contiguous()
-        C = z.shape[-1]
-        P = z.numel() // C
-        dgate = torch.empty_like(gate) if gate is not None else None
-        dz, dgamma, dbeta = _bn_backward(dy, z, P, C, scale, shift, mean, invstd, ctx.relu, gate, dgate, ctx.count)
+        dz, dgamma, dbeta, dgate = _bn_backward(dy, z.shape[-1], 0, z, scale, shift, mean, invstd, ctx.relu, gate, ctx.count)
         return dz, dgamma, dbeta, None, None, dgate, (dy if gate is not None else None), None, None
 
 
@@ -454,40 +466,24 @@ class _SfmStep(torch.autograd.Function):
     leaving a 3-tensor element-wise add of full activations to autograd."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, eps, gate, running=None):
+    def forward(ctx, x, weight, gamma, beta, eps, gate, bn):
         x = x.contiguous()
         z, partials = conv_fwd_raw(x, weight, 1, stats=True)
-        C = z.shape[-1]
-        P = z.numel() // C
-        dev = z.device
-        mean, var, invstd, count = bn_statistics(z, eps, partials)
-        scale, shift, ctx.running_done = _affine(mean, var, invstd, gamma, beta, count, running)
         gate = gate.detach().contiguous()
-        assert gate.numel() == P
-        y = torch.empty_like(z)
-        check(lib().hvpr_bn_relu_fwd_nhwc_f32(z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(), 1, gate.data_ptr(), x.data_ptr(),
-                                              y.data_ptr(), kernels._stream()), "hvpr_bn_relu_fwd_nhwc_f32")
-        ctx.save_for_backward(x, weight, z, scale, shift, mean, invstd, gate)
-        ctx.count = count
-        cnt = count if torch.is_tensor(count) else torch.tensor(float(count), dtype=torch.float64)      # (a HOST tensor: no copy to the device, no sync)
-        ctx.mark_non_differentiable(mean, var, cnt)
-        ctx.set_materialize_grads(False)     # (their gradients would arrive as zero tensors: one allocation + fill each, per call)
-        return y, mean, var, cnt
+        assert gate.numel() == z.numel() // z.shape[-1]
+        y, saved, ctx.count = _bn_forward(z, gamma, beta, eps, partials, bn, True, gate, x)
+        ctx.save_for_backward(x, weight, z, *saved, gate)
+        return y
 
     @staticmethod
-    def backward(ctx, dy, _dm, _dv, _dc):
-        if dy is None:
-            return (None,) * 7
+    def backward(ctx, dy):
         x, weight, z, scale, shift, mean, invstd, gate = ctx.saved_tensors
         dy = dy.contiguous()
-        C = z.shape[-1]
-        P = z.numel() // C
-        dgate = torch.empty_like(gate)
-        dz, dgamma, dbeta = _bn_backward(dy, z, P, C, scale, shift, mean, invstd, True, gate, dgate, ctx.count)
+        dz, dgamma, dbeta, dgate = _bn_backward(dy, z.shape[-1], 0, z, scale, shift, mean, invstd, True, gate, ctx.count)
         cout, cin = weight.shape[0], weight.shape[1]
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            if kernels.conv_algo() == "winograd" and cin % 4 == 0 and cout % 8 == 0:
+            if _winograd(weight, 1, adjoint=True):
                 pc = _pack_wino(weight, True)
                 dx = kernels.conv2d_wino_nhwc(dz, pc, gate=_ones(tuple(dz.shape[:3]), dz.device), resid=dy)    # + the residual path
             else:
@@ -499,72 +495,45 @@ class _SfmStep(torch.autograd.Function):
 
 def sfm_step(x, weight, bn, gate):
     """gate * relu(bn(conv3x3(x))) + x with train-mode `bn` (running statistics updated like nn.BatchNorm2d), one autograd node."""
-    running = _running_of(bn) if _sync_group() is None else None        # then updated inside, by the launch that forms scale / shift
-    y, mean, var, count = _SfmStep.apply(x, weight, bn.weight, bn.bias, bn.eps, gate, running)
-    if running is None:
-        _update_running(bn, mean, var, count if _sync_group() is not None else x.numel() // x.shape[-1])
-    return y
+    return _SfmStep.apply(x, weight, bn.weight, bn.bias, bn.eps, gate, bn)
 
 
 class _BNReLUCat(torch.autograd.Function):
     """cat([relu(BN_train(z_j)) for j], dim=-1) as ONE node: every branch normalises straight into its channel slice of the result and
-    takes its gradient straight out of the result's gradient (hvpr_bn_relu_fwd/bwd_slice_nhwc_f32) — base_bev_backbone.py:262-279 without
-    the concatenation's copy (1.8 GB per stream at batch 16) and the three slice copies of its backward.
-    apply(eps_0, running_0, ..., z_0, gamma_0, beta_0, z_1, ...): the first 2 k arguments are not tensors."""
+    takes its gradient straight out of the result's gradient — base_bev_backbone.py:262-279 without the concatenation's copy (1.8 GB
+    per stream at batch 16) and the three slice copies of its backward.  apply(bns, z_0, gamma_0, beta_0, z_1, ...)."""
 
     @staticmethod
-    def forward(ctx, k, *args):
-        meta, ten = args[:2 * k], args[2 * k:]
-        zs = [ten[3 * j].contiguous() for j in range(k)]
-        Cs = [z.shape[-1] for z in zs]
-        P = zs[0].numel() // Cs[0]
-        total = sum(Cs)
-        out = torch.empty(tuple(zs[0].shape[:-1]) + (total,), dtype=torch.float32, device=zs[0].device)
-        saved, off = [], 0
-        for j in range(k):
-            z, gamma, beta = zs[j], ten[3 * j + 1], ten[3 * j + 2]
-            assert z.numel() // Cs[j] == P
-            mean, var, invstd, count = bn_statistics(z, meta[2 * j])
-            scale, shift, done = _affine(mean, var, invstd, gamma, beta, count, meta[2 * j + 1])
-            assert done or meta[2 * j + 1] is None
-            check(lib().hvpr_bn_relu_fwd_slice_nhwc_f32(z.data_ptr(), P, Cs[j], scale.data_ptr(), shift.data_ptr(), 1, out.data_ptr(), total, off,
-                                                        kernels._stream()), "hvpr_bn_relu_fwd_slice_nhwc_f32")
-            saved += [z, scale, shift, mean, invstd]
-            off += Cs[j]
+    def forward(ctx, bns, *ten):
+        zs = [z.contiguous() for z in ten[0::3]]
+        P = zs[0].numel() // zs[0].shape[-1]
+        out = torch.empty(tuple(zs[0].shape[:-1]) + (sum(z.shape[-1] for z in zs),), dtype=torch.float32, device=zs[0].device)
+        saved, ctx.counts, off = [], [], 0
+        for z, gamma, beta, bn in zip(zs, ten[1::3], ten[2::3], bns):
+            assert z.numel() // z.shape[-1] == P
+            _, s, count = _bn_forward(z, gamma, beta, bn.eps, None, bn, True, out=out, out_coff=off)
+            saved += [z, *s]
+            ctx.counts.append(count)
+            off += z.shape[-1]
         ctx.save_for_backward(*saved)
-        ctx.k, ctx.Cs, ctx.P = k, Cs, P
         return out
 
     @staticmethod
     def backward(ctx, dy):
         dy = dy.contiguous()
-        k, Cs, P = ctx.k, ctx.Cs, ctx.P
-        total = sum(Cs)
         grads, off = [], 0
-        for j in range(k):
+        for j, count in enumerate(ctx.counts):
             z, scale, shift, mean, invstd = ctx.saved_tensors[5 * j:5 * j + 5]
-            dz = torch.empty_like(z)
-            dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
-            ws = _workspace(lib().hvpr_bn_workspace_bytes(P, Cs[j]), z.device)
-            check(lib().hvpr_bn_relu_bwd_slice_nhwc_f32(dy.data_ptr(), total, off, z.data_ptr(), P, Cs[j], scale.data_ptr(), shift.data_ptr(),
-                                                        mean.data_ptr(), invstd.data_ptr(), 1, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_bn_relu_bwd_slice_nhwc_f32")
+            dz, dgamma, dbeta, _ = _bn_backward(dy, dy.shape[-1], off, z, scale, shift, mean, invstd, True, None, count)
             grads += [dz, dgamma, dbeta]
-            off += Cs[j]
-        return (None,) + (None,) * (2 * k) + tuple(grads)
+            off += z.shape[-1]
+        return (None,) + tuple(grads)
 
 
 def bn_relu_cat(zs, bns):
     """torch.cat([bn_relu(z, bn) for z, bn in zip(zs, bns)], dim=-1) with train-mode BatchNorm2d modules, one autograd node, no copy of
-    the parts (SyncBatchNorm or a BatchNorm that keeps no running statistics of the usual kind: the plain form)."""
-    runs = [_running_of(bn) for bn in bns]
-    if _sync_group() is not None or any(r is None for r in runs):
-        return torch.cat([bn_relu(z, bn) for z, bn in zip(zs, bns)], dim=-1)
-    meta, ten = [], []
-    for z, bn, r in zip(zs, bns, runs):
-        meta += [bn.eps, r]
-        ten += [z, bn.weight, bn.bias]
-    return _BNReLUCat.apply(len(zs), *meta, *ten)
+    the parts."""
+    return _BNReLUCat.apply(tuple(bns), *[t for z, bn in zip(zs, bns) for t in (z, bn.weight, bn.bias)])
 
 
 def _update_running(bn, mean, var, n):
@@ -595,11 +564,7 @@ def deconv(x, weight):
 def bn_relu(z, bn, relu=True, gate=None, resid=None, partials=None):
     """Train-mode nn.BatchNorm2d `bn` (its weight / bias / eps / momentum / running buffers) + optional ReLU on NHWC `z`; with
     gate (N,H,W,1) and resid (N,H,W,C): gate * relu(bn(z)) + resid, differentiable in all of them."""
-    running = _running_of(bn) if _sync_group() is None else None        # then updated inside, by the launch that forms scale / shift
-    y, mean, var, count = _BNReLU.apply(z, bn.weight, bn.bias, bn.eps, relu, gate, resid, partials, running)
-    if running is None:
-        _update_running(bn, mean, var, count if _sync_group() is not None else z.numel() // z.shape[-1])
-    return y
+    return _BNReLU.apply(z, bn.weight, bn.bias, bn.eps, relu, gate, resid, partials, bn)
 
 
 class _GateTrain(torch.autograd.Function):

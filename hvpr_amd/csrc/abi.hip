@@ -7,8 +7,10 @@
 // grew) — a caller that sized either buffer with a version-3 formula is too small: always size them with the two functions; 5: adds
 // hvpr_bn_train_affine_f32 and hvpr_bn_relu_fwd / bwd_slice_nhwc_f32; hvpr_conv2d_wino_wgrad_nhwc_f32 answers HVPR_ERR_UNSUPPORTED for images of 2 GB and more (32-bit offsets
 // inside an image; its workspace size is unchanged); 6: hvpr_encode_fwd_f32 takes index_mode (the one-launch index kernel is opt-in and guarded),
-// hvpr_voxelize_workspace_status, HVPR_ERR_TIMEOUT
-extern "C" int hvpr_abi_version(void) { return 6; }
+// hvpr_voxelize_workspace_status, HVPR_ERR_TIMEOUT; 7: hvpr_bn_relu_fwd_nhwc_f32 takes y_cstride / y_coff and hvpr_bn_relu_bwd_sums /
+// _apply_nhwc_f32 take dy_cstride / dy_coff (a channel slice of a wider tensor); hvpr_bn_relu_fwd / bwd_slice_nhwc_f32, hvpr_bn_relu_bwd_nhwc_f32
+// (= _sums then _apply), hvpr_group_rows_grad_f32 and hvpr_fp_rows_grad_f32 are gone
+extern "C" int hvpr_abi_version(void) { return 7; }
 
 extern "C" const char *hvpr_status_string(int status) {
     switch (status) {

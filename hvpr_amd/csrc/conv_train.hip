@@ -439,6 +439,15 @@ __global__ void __launch_bounds__(256) k_zero_p(float *__restrict__ p, long long
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
+// A channel slice [coff, coff + C) of an NHWC tensor with cstride channels per pixel, in whole float4 groups (cstride == C, coff == 0:
+// the dense tensor).  The backbone's deconvolution branches write their 128 channels straight into the 384-channel concatenation the
+// head reads and take their gradient out of its gradient: no torch.cat, no slice copies.
+bool bn_slice_ok(int C, int cstride, int coff) {
+    return C >= 4 && C % 4 == 0 && cstride % 4 == 0 && coff % 4 == 0 && coff >= 0 && coff + C <= cstride;
+}
+
+unsigned bn_apply_grid(long long n4) { return (unsigned)((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256); }
+
 }  // namespace
 
 extern "C" size_t hvpr_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, int Cin, int Cout, int taps, int stride) {
@@ -509,98 +518,48 @@ extern "C" int hvpr_bn_train_affine_f32(const float *mean, const float *var, con
 }
 
 extern "C" int hvpr_bn_relu_fwd_nhwc_f32(const float *z, long long P, int C, const float *scale, const float *shift, int relu,
-                                         const float *gate, const float *resid, float *y, hvpr_stream_t stream) {
+                                         const float *gate, const float *resid, float *y, int y_cstride, int y_coff, hvpr_stream_t stream) {
     if (!z || !scale || !shift || !y || P < 1 || ((gate == nullptr) != (resid == nullptr))) return HVPR_ERR_INVALID_ARG;
-    if (C < 4 || C % 4 != 0) return HVPR_ERR_UNSUPPORTED;
+    if (!bn_slice_ok(C, y_cstride, y_coff)) return HVPR_ERR_UNSUPPORTED;
     const long long n4 = P * (C / 4);
-    long long blocks = (n4 + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float4 *)z, n4, C / 4, scale, shift, relu,
-                       gate, (const float4 *)resid, (float4 *)y, C / 4, 0);
-    HVPR_CHECK_LAUNCH();
-    return HVPR_OK;
-}
-
-// The same into / out of a channel slice of a wider NHWC tensor (the deconvolution branches write their 128 channels straight into the
-// 384-channel concatenation the head reads, and take their gradient out of its gradient: no torch.cat, no slice copies).
-extern "C" int hvpr_bn_relu_fwd_slice_nhwc_f32(const float *z, long long P, int C, const float *scale, const float *shift, int relu, float *y,
-                                               int y_cstride, int y_coff, hvpr_stream_t stream) {
-    if (!z || !scale || !shift || !y || P < 1) return HVPR_ERR_INVALID_ARG;
-    if (C < 4 || C % 4 != 0 || y_cstride % 4 != 0 || y_coff % 4 != 0 || y_coff < 0 || y_coff + C > y_cstride) return HVPR_ERR_UNSUPPORTED;
-    const long long n4 = P * (C / 4);
-    long long blocks = (n4 + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float4 *)z, n4, C / 4, scale, shift, relu,
-                       (const float *)nullptr, (const float4 *)nullptr, (float4 *)y, y_cstride / 4, y_coff / 4);
+    hipLaunchKernelGGL(k_bn_apply, dim3(bn_apply_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const float4 *)z, n4, C / 4, scale, shift, relu,
+                       gate, (const float4 *)resid, (float4 *)y, y_cstride / 4, y_coff / 4);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }
 
 // The backward in its two halves, so that a caller can put an all-reduce between them (SyncBatchNorm: the sums and the count are
 // those of the GLOBAL batch, tools/train.py:119-120): sums = local d beta / d gamma; apply = dz from whatever sums it is given.
-extern "C" int hvpr_bn_relu_bwd_sums_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                                              const float *mean, const float *invstd, int relu, const float *gate, float *dgamma,
-                                              float *dbeta, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
+extern "C" int hvpr_bn_relu_bwd_sums_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C,
+                                              const float *scale, const float *shift, const float *mean, const float *invstd, int relu,
+                                              const float *gate, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                              hvpr_stream_t stream) {
     if (!dy || !z || !scale || !shift || !mean || !invstd || !dgamma || !dbeta || !workspace || P < 1) return HVPR_ERR_INVALID_ARG;
-    if (C < 4 || C % 4 != 0 || C > 1024) return HVPR_ERR_UNSUPPORTED;
+    if (!bn_slice_ok(C, dy_cstride, dy_coff) || C > 1024) return HVPR_ERR_UNSUPPORTED;
     if (workspace_bytes < hvpr_bn_workspace_bytes(P, C)) return HVPR_ERR_WORKSPACE;
     const int blocks = bn_blocks(P);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_bn_reduce<true>, dim3(blocks), dim3(256), 0, s, z, dy, P, C, scale, shift, mean, invstd, relu, gate, bn_slab(P), (float *)workspace);
+    hipLaunchKernelGGL(k_bn_reduce<true>, dim3(blocks), dim3(256), 0, s, z, dy + dy_coff, P, C, scale, shift, mean, invstd, relu, gate, bn_slab(P),
+                       (float *)workspace, dy_cstride);
     // s1 -> dbeta, s2 -> dgamma  (d beta = sum dy_m, d gamma = sum dy_m * xhat)
     launch_bn_finalize((const float *)workspace, blocks, C, (double)P, 0.f, 1, dbeta, dgamma, (float *)nullptr, s);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }
 
-extern "C" int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                                               const float *mean, const float *invstd, int relu, const float *gate, float *dgate, float *dz,
-                                               const float *dgamma_total, const float *dbeta_total, double inv_count, hvpr_stream_t stream) {
+extern "C" int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C,
+                                               const float *scale, const float *shift, const float *mean, const float *invstd, int relu,
+                                               const float *gate, float *dgate, float *dz, const float *dgamma_total,
+                                               const float *dbeta_total, double inv_count, hvpr_stream_t stream) {
     if (!dy || !z || !scale || !shift || !mean || !invstd || !dz || !dgamma_total || !dbeta_total || P < 1 || !(inv_count > 0.0))
         return HVPR_ERR_INVALID_ARG;
     if ((gate == nullptr) != (dgate == nullptr)) return HVPR_ERR_INVALID_ARG;
-    if (C < 4 || C % 4 != 0 || C > 1024) return HVPR_ERR_UNSUPPORTED;
+    if (!bn_slice_ok(C, dy_cstride, dy_coff) || C > 1024) return HVPR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if (dgate) hipLaunchKernelGGL(k_zero_p, dim3(hvpr_cdiv(P, 256) > 8192 ? 8192 : hvpr_cdiv(P, 256)), dim3(256), 0, s, dgate, P);
     const long long n4 = P * (C / 4);
-    long long g = (n4 + 255) / 256;
-    if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)g), dim3(256), 0, s, (const float4 *)dy, (const float4 *)z, n4, C / 4, scale, shift, mean,
-                       invstd, dbeta_total, dgamma_total, (float)inv_count, relu, gate, dgate, (float4 *)dz, C / 4);
+    hipLaunchKernelGGL(k_bn_bwd_apply, dim3(bn_apply_grid(n4)), dim3(256), 0, s, (const float4 *)(dy + dy_coff), (const float4 *)z, n4, C / 4,
+                       scale, shift, mean, invstd, dbeta_total, dgamma_total, (float)inv_count, relu, gate, dgate, (float4 *)dz, dy_cstride / 4);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
-}
-
-extern "C" int hvpr_bn_relu_bwd_slice_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C,
-                                               const float *scale, const float *shift, const float *mean, const float *invstd, int relu,
-                                               float *dz, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
-                                               hvpr_stream_t stream) {
-    if (!dy || !z || !scale || !shift || !mean || !invstd || !dz || !dgamma || !dbeta || !workspace || P < 1) return HVPR_ERR_INVALID_ARG;
-    if (C < 4 || C % 4 != 0 || C > 1024 || dy_cstride % 4 != 0 || dy_coff % 4 != 0 || dy_coff < 0 || dy_coff + C > dy_cstride) return HVPR_ERR_UNSUPPORTED;
-    if (workspace_bytes < hvpr_bn_workspace_bytes(P, C)) return HVPR_ERR_WORKSPACE;
-    const int blocks = bn_blocks(P);
-    hipStream_t s = (hipStream_t)stream;
-    const float *dys = dy + dy_coff;
-    hipLaunchKernelGGL(k_bn_reduce<true>, dim3(blocks), dim3(256), 0, s, z, dys, P, C, scale, shift, mean, invstd, relu, (const float *)nullptr,
-                       bn_slab(P), (float *)workspace, dy_cstride);
-    launch_bn_finalize((const float *)workspace, blocks, C, (double)P, 0.f, 1, dbeta, dgamma, (float *)nullptr, s);
-    const long long n4 = P * (C / 4);
-    long long g = (n4 + 255) / 256;
-    if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)g), dim3(256), 0, s, (const float4 *)dys, (const float4 *)z, n4, C / 4, scale, shift, mean,
-                       invstd, dbeta, dgamma, (float)(1.0 / (double)P), relu, (const float *)nullptr, (float *)nullptr, (float4 *)dz,
-                       dy_cstride / 4);
-    HVPR_CHECK_LAUNCH();
-    return HVPR_OK;
-}
-
-extern "C" int hvpr_bn_relu_bwd_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                                         const float *mean, const float *invstd, int relu, const float *gate, float *dgate, float *dz,
-                                         float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
-    if (!dz || (gate == nullptr) != (dgate == nullptr)) return HVPR_ERR_INVALID_ARG;
-    const int st = hvpr_bn_relu_bwd_sums_nhwc_f32(dy, z, P, C, scale, shift, mean, invstd, relu, gate, dgamma, dbeta, workspace,
-                                                  workspace_bytes, stream);
-    if (st != HVPR_OK) return st;
-    return hvpr_bn_relu_bwd_apply_nhwc_f32(dy, z, P, C, scale, shift, mean, invstd, relu, gate, dgate, dz, dgamma, dbeta, 1.0 / (double)P,
-                                           stream);
 }

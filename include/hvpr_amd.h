@@ -35,7 +35,7 @@ enum hvpr_status {
     HVPR_ERR_TIMEOUT = -5        /* hvpr_voxelize_workspace_status: a one-launch index kernel gave up a wait (workspace needs a reset) */
 };
 
-int hvpr_abi_version(void);     /* 5 (history: csrc/abi.hip); size every workspace / packed buffer with the *_bytes / *_floats functions */
+int hvpr_abi_version(void);     /* 7 (history: csrc/abi.hip); size every workspace / packed buffer with the *_bytes / *_floats functions */
 const char *hvpr_status_string(int status);
 
 /* SyncBatchNorm across ranks (reference: tools/train.py:119-120, --sync_bn -> torch.nn.SyncBatchNorm).  The training entry points
@@ -336,24 +336,18 @@ int hvpr_three_interpolate_grad_f32(const float *grad_out, const int32_t *idx, c
  *     [samples, cpad]: channels contiguous, zero columns up to cpad (a multiple of 8).
  *     hvpr_group_rows_f32:       QueryAndGroup(use_xyz): xyz [B,N,3], features [B,N,C] (null when C == 0), new_xyz [B,npoint,3],
  *                                idx [B,npoint,nsample] i32 -> out [B*npoint*nsample, cpad], row = [xyz[idx] - new_xyz | features[idx] | 0].
- *     hvpr_group_rows_grad_f32:  grad_out [rows, cpad] -> grad_features [B,N,C], overwritten (zeroed + fp32 atomics).
  *     hvpr_max_samples_f32:      y [G, nsample, C] -> out [G, C] = max over the samples of a group, argmax [G, C] u8 (lowest sample
  *                                on ties); nsample <= 255.        hvpr_max_samples_grad_f32: grad_out [G,C] -> grad_y [G,nsample,C].
  *     hvpr_fp_rows_f32:          PointnetFPModule's input: known [B,m,C1], idx / weight [B,n,3], skip [B,n,C2] (null when C2 == 0)
  *                                -> out [B*n, cpad], row = [(k0 w0 + k1 w1) + k2 w2 | skip | 0].
- *     hvpr_fp_rows_grad_f32:     grad_out [B*n, cpad] -> grad_known [B,m,C1] (zeroed + fp32 atomics), grad_skip [B,n,C2] (may be null).
  * ------------------------------------------------------------------------------------------- */
 int hvpr_group_rows_f32(const float *xyz, const float *features, const float *new_xyz, const int32_t *idx, int B, int N, int C,
                         int npoint, int nsample, int cpad, float *out, hvpr_stream_t stream);
-int hvpr_group_rows_grad_f32(const float *grad_out, const int32_t *idx, int B, int N, int C, int npoint, int nsample, int cpad,
-                             float *grad_features, hvpr_stream_t stream);
 int hvpr_max_samples_f32(const float *y, long long G, int nsample, int C, float *out, uint8_t *argmax, hvpr_stream_t stream);
 int hvpr_max_samples_grad_f32(const float *grad_out, const uint8_t *argmax, long long G, int nsample, int C, float *grad_y,
                               hvpr_stream_t stream);
 int hvpr_fp_rows_f32(const float *known, const int32_t *idx, const float *weight, const float *skip, int B, int m, int n, int C1,
                      int C2, int cpad, float *out, hvpr_stream_t stream);
-int hvpr_fp_rows_grad_f32(const float *grad_out, const int32_t *idx, const float *weight, int B, int m, int n, int C1, int C2,
-                          int cpad, float *grad_known, float *grad_skip, hvpr_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * a11 (training)  SpatialAttention with BATCH statistics (pcdet/models/backbones_2d/spatial_attention.py:47-63): ChannelPool ->
  *     conv3x3 2 -> 1 (+ bias) -> BatchNorm2d(1) -> sigmoid, forward and backward on NHWC y [N,H,W,C] (C % 4 == 0).  Parameters are
@@ -418,64 +412,66 @@ int hvpr_memory_train_bwd_f32(const float *x, const float *dy, long long R, cons
  *     hvpr_conv2d_wgrad_nhwc_f32: weight gradient on the fp32 matrix cores.  x [N,H,W,Cin] and dz [N,OH,OW,Cout] NHWC
  *         (OH = (H + 2 - 3) / stride + 1 for taps == 9 (3x3, pad 1), = H for taps == 1) -> dw [Cout, Cin, k, k] (torch layout),
  *         overwritten.  Split-K over pixel tiles into `workspace` partials, summed in a fixed order: deterministic.
- *     hvpr_bn_stats_nhwc_f32: per-channel batch mean, biased variance and 1/sqrt(var + eps) of z [P, C] (train-mode BatchNorm,
- *         double-precision final sums).
- *     hvpr_bn_train_affine_f32: what train-mode nn.BatchNorm2d does with the batch moments besides normalising, one launch:
- *         scale = gamma * invstd, shift = beta - mean * scale, and (running_mean / running_var both non-NULL)
- *         running = (1 - momentum) * running + momentum * mean | momentum_unbiased * var (momentum_unbiased = momentum * n / (n - 1)),
- *         *num_batches_tracked += 1 (int64, may be NULL).
- *     hvpr_bn_relu_fwd_nhwc_f32: y = max(0, z * scale + shift) (relu == 0: no max); scale = gamma * invstd, shift = beta - mean * scale.
- *     hvpr_bn_relu_bwd_nhwc_f32: dz, dgamma, dbeta of y = relu(gamma * (z - mean) * invstd + beta) with BATCH statistics
- *         (the mean / variance terms are differentiated through).
- *     gate [P] + resid [P,C] (both or neither; may be NULL): the SFM step fused in, y = gate[p] * relu(...) + resid
- *         (x_att = attention(sfm(x_att), y) + x_att, base_bev_backbone.py:250-255); the backward then also returns dgate [P]
- *         (= sum_c relu(...) * dy, overwritten) and propagates gate * dy; d resid = dy.
- *     C % 4 == 0, C <= 1024 for the reductions.
+ *     hvpr_conv2d_wino_wgrad_nhwc_f32: the same weight gradient for 3x3 / stride 1 / pad 1 in the Winograd F(2x2,3x3) domain
+ *         (dU = sum_blocks (A dY At) . (Bt d B), dw = Gt dU G): 16 instead of 36 fp32 multiplies per 2x2 block and (co, ci) pair;
+ *         x [N,H,W,Cin], dz [N,H,W,Cout] -> dw [Cout,Cin,3,3], deterministic split-K like the direct form.
+ *     hvpr_conv2d_s2_dgrad_nhwc_f32: data gradient of a 3x3 stride-2 (pad 1) convolution, gathered per output-pixel parity class
+ *         (1 / 2 / 2 / 4 taps) instead of a stride-1 convolution over a zero-upsampled gradient: dz [N, H, W, Cin] (the layer's
+ *         output gradient; Cin = its output channels) -> dx [N, OH, OW, out_cstride] channels [out_coff, out_coff + cout) (its
+ *         input's gradient; H == (OH + 2 - 3) / 2 + 1, W likewise).  w_packed = hvpr_conv2d_nhwc_f32's weight image of the layer's
+ *         filter with the channel axes swapped ((cout, Cin, 3, 3), taps NOT flipped), bias [cout_pad] (zeros for a plain gradient),
+ *         cout_pad a multiple of 64.
  * ------------------------------------------------------------------------------------------- */
-/* hvpr_conv2d_wino_wgrad_nhwc_f32: the same weight gradient for 3x3 / stride 1 / pad 1 in the Winograd F(2x2,3x3) domain
- *     (dU = sum_blocks (A dY At) . (Bt d B), dw = Gt dU G): 16 instead of 36 fp32 multiplies per 2x2 block and (co, ci) pair;
- *     x [N,H,W,Cin], dz [N,H,W,Cout] -> dw [Cout,Cin,3,3], deterministic split-K like the direct form. */
 size_t hvpr_conv2d_wino_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout);
 int hvpr_conv2d_wino_wgrad_nhwc_f32(const float *x, int N, int H, int W, int Cin, const float *dz, int Cout, float *dw,
                                     void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
 size_t hvpr_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, int Cin, int Cout, int taps, int stride);
 int hvpr_conv2d_wgrad_nhwc_f32(const float *x, int N, int H, int W, int Cin, const float *dz, int Cout, int taps, int stride, float *dw,
                                void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_conv2d_s2_dgrad_nhwc_f32(const float *dz, int N, int H, int W, int Cin, const float *w_packed, const float *bias, int cout,
+                                  int cout_pad, int OH, int OW, float *dx, int out_cstride, int out_coff, hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * a11 (training)  Train-mode BatchNorm + ReLU over NHWC activations z [P, C] with BATCH statistics — every BatchNorm2d of the
+ *     backbone and head, the point stream's shared MLPs and the VFE scale stream.  C % 4 == 0; C <= 1024 for the reductions.
+ *     Sums: per-workgroup fp32 partials, final sums in double in a fixed order (deterministic).
+ *     hvpr_bn_stats_nhwc_f32: per-channel batch mean, biased variance and 1/sqrt(var + eps) of z.
+ *     hvpr_bn_finalize_partials_f32: the same from per-tile sums a producing kernel left behind (hvpr_conv2d_wino_nhwc_f32's
+ *         bn_partials [rows][2][C]: sum, sum of squares; count = the pixels they cover).
+ *     hvpr_bn_train_affine_f32: what train-mode nn.BatchNorm2d does with the batch moments besides normalising, one launch:
+ *         scale = gamma * invstd, shift = beta - mean * scale, and (running_mean / running_var both non-NULL)
+ *         running = (1 - momentum) * running + momentum * mean | momentum_unbiased * var (momentum_unbiased = momentum * n / (n - 1)),
+ *         *num_batches_tracked += 1 (int64, may be NULL).
+ *     hvpr_bn_relu_fwd_nhwc_f32: y = max(0, z * scale + shift) (relu == 0: no max).
+ *     hvpr_bn_relu_bwd_sums_nhwc_f32: the LOCAL d gamma = sum dy_m * xhat and d beta = sum dy_m (dy_m = dy through the ReLU / gate).
+ *     hvpr_bn_relu_bwd_apply_nhwc_f32: dz (and dgate) of y = relu(gamma * (z - mean) * invstd + beta), the mean / variance terms
+ *         differentiated through, from given sums d gamma, d beta and 1 / count.  One rank: _sums, then _apply with its sums and
+ *         1 / P.  SyncBatchNorm (tools/train.py:119-120): the caller all-reduces the sums over the ranks between the two and
+ *         passes those of the GLOBAL batch with 1 / its count.
+ *     gate [P] + resid [P,C] (both or neither; may be NULL): the SFM step fused in, y = gate[p] * relu(...) + resid
+ *         (x_att = attention(sfm(x_att), y) + x_att, base_bev_backbone.py:250-255); the backward then also returns dgate [P]
+ *         (= sum_c relu(...) * dy, overwritten) and propagates gate * dy; d resid = dy.
+ *     Channel slices: y (forward) and dy (backward) are channels [coff, coff + C) of an NHWC tensor with cstride channels per pixel
+ *         (cstride % 4 == 0, coff % 4 == 0, coff + C <= cstride; cstride == C, coff == 0: dense).  Every other tensor is dense
+ *         [P, C] — resid included.  The backbone's deconvolution branches write straight into the 384-channel concatenation the
+ *         head reads and take their gradient out of its gradient.
+ * ------------------------------------------------------------------------------------------- */
 size_t hvpr_bn_workspace_bytes(long long P, int C);
 int hvpr_bn_stats_nhwc_f32(const float *z, long long P, int C, float eps, float *mean, float *var, float *invstd, void *workspace,
                            size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_bn_finalize_partials_f32(const float *partials, int rows, int C, long long count, float eps, float *mean, float *var,
+                                  float *invstd, hvpr_stream_t stream);
 int hvpr_bn_train_affine_f32(const float *mean, const float *var, const float *invstd, int C, const float *gamma, const float *beta,
                              float momentum, float momentum_unbiased, float *running_mean, float *running_var,
                              long long *num_batches_tracked, float *scale, float *shift, hvpr_stream_t stream);
 int hvpr_bn_relu_fwd_nhwc_f32(const float *z, long long P, int C, const float *scale, const float *shift, int relu, const float *gate,
-                              const float *resid, float *y, hvpr_stream_t stream);
-/* ... into / out of a channel slice [coff, coff + C) of a wider NHWC tensor with cstride channels per pixel (no gate): the backbone's
- * deconvolution branches write straight into the 384-channel concatenation and take their gradient out of its gradient. */
-/* Data gradient of a 3x3 stride-2 (pad 1) convolution, gathered per output-pixel parity class (1 / 2 / 2 / 4 taps) instead of a
- * stride-1 convolution over a zero-upsampled gradient: dz [N, H, W, Cin] (the layer's output gradient; Cin = its output channels) ->
- * dx [N, OH, OW, out_cstride] channels [out_coff, out_coff + cout) (its input's gradient; H == (OH + 2 - 3) / 2 + 1, W likewise).
- * w_packed = hvpr_conv2d_nhwc_f32's weight image of the layer's filter with the channel axes swapped ((cout, Cin, 3, 3), taps NOT
- * flipped), bias [cout_pad] (zeros for a plain gradient), cout_pad a multiple of 64. */
-int hvpr_conv2d_s2_dgrad_nhwc_f32(const float *dz, int N, int H, int W, int Cin, const float *w_packed, const float *bias, int cout,
-                                  int cout_pad, int OH, int OW, float *dx, int out_cstride, int out_coff, hvpr_stream_t stream);
-int hvpr_bn_relu_fwd_slice_nhwc_f32(const float *z, long long P, int C, const float *scale, const float *shift, int relu, float *y,
-                                    int y_cstride, int y_coff, hvpr_stream_t stream);
-int hvpr_bn_relu_bwd_slice_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C, const float *scale,
-                                    const float *shift, const float *mean, const float *invstd, int relu, float *dz, float *dgamma,
-                                    float *dbeta, void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
-int hvpr_bn_relu_bwd_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                              const float *mean, const float *invstd, int relu, const float *gate, float *dgate, float *dz, float *dgamma,
-                              float *dbeta, void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
-/* The same backward in its two halves, for SyncBatchNorm (tools/train.py:119-120 converts every BatchNorm when --sync_bn is given):
- * _sums leaves the LOCAL d gamma = sum dy_m * xhat and d beta = sum dy_m (dy_m = dy through the ReLU / gate); the caller all-reduces
- * them over the ranks; _apply computes dz (and dgate) from the sums and 1 / count of the GLOBAL batch.  hvpr_bn_relu_bwd_nhwc_f32 is
- * _sums followed by _apply with the local sums and 1 / P. */
-int hvpr_bn_relu_bwd_sums_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                                   const float *mean, const float *invstd, int relu, const float *gate, float *dgamma, float *dbeta,
-                                   void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
-int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, const float *z, long long P, int C, const float *scale, const float *shift,
-                                    const float *mean, const float *invstd, int relu, const float *gate, float *dgate, float *dz,
-                                    const float *dgamma_total, const float *dbeta_total, double inv_count, hvpr_stream_t stream);
+                              const float *resid, float *y, int y_cstride, int y_coff, hvpr_stream_t stream);
+int hvpr_bn_relu_bwd_sums_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C, const float *scale,
+                                   const float *shift, const float *mean, const float *invstd, int relu, const float *gate, float *dgamma,
+                                   float *dbeta, void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, int dy_cstride, int dy_coff, const float *z, long long P, int C, const float *scale,
+                                    const float *shift, const float *mean, const float *invstd, int relu, const float *gate, float *dgate,
+                                    float *dz, const float *dgamma_total, const float *dbeta_total, double inv_count, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a12 (training)  Anchor target assignment for ONE anchor set (one class of ANCHOR_GENERATOR_CONFIG) and all frames of the batch —
@@ -565,8 +561,6 @@ int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, int Cin, con
  * a pass over the written tensor; hvpr_bn_finalize_partials_f32 turns them into mean / biased variance / 1/sqrt(var + eps)
  * (count = N * H * W; sums finished in double, fixed order: deterministic). */
 int hvpr_conv2d_wino_stats_rows(int N, int H, int W);
-int hvpr_bn_finalize_partials_f32(const float *partials, int rows, int C, long long count, float eps, float *mean, float *var,
-                                  float *invstd, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a5 optional precision modes: 3x3 convolutions on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulation)

@@ -1,7 +1,8 @@
 """Child process of tests/test_gpu_distributed.py: SyncBatchNorm over the library's own BatchNorm kernels on ONE rank of an RCCL group
-(all this pool can run): with the process group set (distributed.convert_sync_batchnorm) conv_train.bn_relu and the fused SFM step
-take the all-reduce path — per-rank sums -> float64 all-reduce -> statistics, and the split backward (hvpr_bn_relu_bwd_sums_nhwc_f32 ->
-all-reduce -> hvpr_bn_relu_bwd_apply_nhwc_f32) — and must agree with the per-rank path, which at world size 1 computes the same thing.
+(all this pool can run): with the process group set (distributed.convert_sync_batchnorm) conv_train.bn_relu, the fused SFM step and
+bn_relu_cat (channel slices of one output; one branch with momentum=None) take the all-reduce path — per-rank sums -> float64
+all-reduce -> statistics, and the split backward (hvpr_bn_relu_bwd_sums_nhwc_f32 -> all-reduce -> hvpr_bn_relu_bwd_apply_nhwc_f32) — and
+must agree with the per-rank path, which at world size 1 computes the same thing.
 SpatialAttention's BatchNorm (inside one library call) goes through the library's hook: an RCCL all-reduce on the library's own device
 doubles (forward and backward: two hook calls)."""
 import json
@@ -24,6 +25,9 @@ x0 = (torch.randn(N, H, W, C, generator=g) * 1.5 + 0.3).to(dev)
 wconv = (torch.randn(C, C, 3, 3, generator=g) * 0.05).to(dev)
 gate = torch.rand(N, H, W, 1, generator=g).to(dev)
 wout = torch.randn(N, H, W, C, generator=g).to(dev)
+Cs = (32, 16)                                                 # bn_relu_cat's branches: slices [0, 32) and [32, 48) of 48 channels
+zcat0 = [(torch.randn(N, H, W, c, generator=g) * 1.2 - 0.1).to(dev) for c in Cs]
+wcat = torch.randn(N, H, W, sum(Cs), generator=g).to(dev)
 
 
 def run(sync):
@@ -41,9 +45,14 @@ def run(sync):
     gw = (torch.linspace(-0.4, 0.4, 18).view(1, 2, 3, 3)).to(dev).requires_grad_(True)
     gb, gg, gbe = (torch.tensor([v], device=dev, requires_grad=True) for v in (0.3, 1.3, -0.2))
     sgate, smean, svar = ct.spatial_gate_train(y, gw, gb, gg, gbe, 1e-3)
-    ((y * wout).sum() + (sgate * wout[..., :1]).sum()).backward()
+    bns = [torch.nn.BatchNorm2d(Cs[0], eps=1e-3, momentum=0.01).to(dev), torch.nn.BatchNorm2d(Cs[1], eps=1e-3, momentum=None).to(dev)]
+    zc = [t.clone().requires_grad_(True) for t in zcat0]
+    ycat = ct.bn_relu_cat(zc, bns)
+    ((y * wout).sum() + (sgate * wout[..., :1]).sum() + (ycat * wcat).sum()).backward()
     torch.cuda.synchronize()
-    res = {"y": y.detach(), "dx": x.grad, "dw": w.grad, "dg": bn.weight.grad, "db": bn.bias.grad, "dg2": bn2.weight.grad,
+    res = {"ycat": ycat.detach(), "dzc0": zc[0].grad, "dzc1": zc[1].grad, "dgc0": bns[0].weight.grad, "dbc1": bns[1].bias.grad,
+           "rmc0": bns[0].running_mean.clone(), "rvc0": bns[0].running_var.clone(), "rvc1": bns[1].running_var.clone(),
+           "y": y.detach(), "dx": x.grad, "dw": w.grad, "dg": bn.weight.grad, "db": bn.bias.grad, "dg2": bn2.weight.grad,
            "rm": bn.running_mean.clone(), "rv": bn.running_var.clone(), "rv2": bn2.running_var.clone(),
            "sgate": sgate.detach(), "smean": smean.clone(), "svar": svar.clone(), "sdw": gw.grad, "sdgamma": gg.grad}
     ct.set_sync_batchnorm(None)

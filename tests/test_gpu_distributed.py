@@ -63,9 +63,9 @@ def test_bench_train_step_ddp_line_over_one_rank_rccl(tmp_path):
 
 def test_sync_batchnorm_path_on_one_rank_rccl(tmp_path):
     """SyncBatchNorm (reference tools/train.py:119-120) over the own BatchNorm kernels: conv -> bn_relu (statistics from the Winograd
-    kernel's per-tile sums) -> fused SFM step, forward + backward, with the statistics all-reduced over a one-rank RCCL group against
-    the per-rank path.  At world size 1 the two compute the same numbers by different routes (float64 torch sums + split backward
-    vs the finalize kernel + fused backward): agreement to fp32 round-off.  The N > 1 arithmetic of the all-reduces is covered on
+    kernel's per-tile sums) -> fused SFM step, and bn_relu_cat (channel slices), forward + backward, with the statistics all-reduced
+    over a one-rank RCCL group against the per-rank path.  At world size 1 the two compute the same numbers by different routes
+    (float64 torch sums + all-reduced backward sums vs the finalize kernel + local sums): agreement to fp32 round-off.  The N > 1 arithmetic of the all-reduces is covered on
     CPU/gloo (test_sync_batchnorm_two_ranks_batch1_equal_one_process_batch2)."""
     from hvpr_amd import distributed
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_syncbn_worker.py")
