@@ -9,7 +9,10 @@
 // inside an image; its workspace size is unchanged); 6: hvpr_encode_fwd_f32 takes index_mode (the one-launch index kernel is opt-in and guarded),
 // hvpr_voxelize_workspace_status, HVPR_ERR_TIMEOUT; 7: hvpr_bn_relu_fwd_nhwc_f32 takes y_cstride / y_coff and hvpr_bn_relu_bwd_sums /
 // _apply_nhwc_f32 take dy_cstride / dy_coff (a channel slice of a wider tensor); hvpr_bn_relu_fwd / bwd_slice_nhwc_f32, hvpr_bn_relu_bwd_nhwc_f32
-// (= _sums then _apply), hvpr_group_rows_grad_f32 and hvpr_fp_rows_grad_f32 are gone
+// (= _sums then _apply), hvpr_group_rows_grad_f32 and hvpr_fp_rows_grad_f32 are gone.  Later within 7 (no signature changed):
+// hvpr_nms_workspace_bytes grows with n_max (past 4096 it also reserves the two-launch mask's segments, ~17 MB more), so a
+// workspace serves every smaller n_max; the hvpr_score_topk_f32 workspace keeps its zeroed state in front of the keys, and calls
+// that share one pass the same batch; -0.0 scores rank as +0.0
 extern "C" int hvpr_abi_version(void) { return 7; }
 
 extern "C" const char *hvpr_status_string(int status) {

@@ -674,10 +674,10 @@ extern "C" size_t hvpr_nms_workspace_bytes(int n_max) {
     if (n_max < 1) return 0;
     const size_t nb = (n_max + 63) / 64;
     size_t bytes = (size_t)n_max * nb * sizeof(unsigned long long) + 256 + (size_t)n_max * sizeof(Box) + 256;
-    if (nb <= 64) {     // the two-launch mask: per-tile pair segments + counts
-        const size_t tiles = nb * (nb + 1) / 2;
-        bytes += tiles * kTileCap * sizeof(unsigned short) + 256 + tiles * sizeof(int) + 256 + sizeof(ClipIndex) + 256;
-    }
+    // the two-launch mask (nb <= 64): per-tile pair segments + counts.  Past 4096 they are reserved at their largest too, so
+    // that the size grows with n_max and a workspace serves every n_max up to the one it was sized for.
+    const size_t nbl = nb < 64 ? nb : 64, tiles = nbl * (nbl + 1) / 2;
+    bytes += tiles * kTileCap * sizeof(unsigned short) + 256 + tiles * sizeof(int) + 256 + sizeof(ClipIndex) + 256;
     return bytes;
 }
 

@@ -114,8 +114,9 @@ __global__ void __launch_bounds__(256) k_head_decode(const float *__restrict__ h
 }
 
 // ------------------------------------------------------------------------------------------------ score filter + top-k
+// -0.0 takes the key of +0.0: the two compare equal, so they tie and the lower id goes first
 __device__ __forceinline__ unsigned ord_bits(float v) {
-    const unsigned b = __float_as_uint(v);
+    const unsigned b = __float_as_uint(v) == 0x80000000u ? 0u : __float_as_uint(v);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float unord_bits(unsigned u) {
@@ -443,12 +444,16 @@ extern "C" int hvpr_score_topk_f32(const float *scores, int batch, int n_scores,
     if (pre_max > SORTCAP) return HVPR_ERR_UNSUPPORTED;
     if (workspace_bytes < hvpr_score_topk_workspace_bytes(batch, n_scores)) return HVPR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *keys = (unsigned long long *)workspace;
-    char *tail = (char *)workspace + (((size_t)batch * n_scores * sizeof(unsigned long long) + 255) / 256) * 256;
-    int *cnt = (int *)tail;                                              // [batch]
-    unsigned *tbin = (unsigned *)(tail + ((batch * sizeof(int) + 255) / 256) * 256);   // [batch]
-    unsigned *hist = (unsigned *)((char *)tbin + ((batch * sizeof(unsigned) + 255) / 256) * 256);   // [batch][HBINS], adjacent to cnt/tbin
+    const size_t lds = (size_t)SORTCAP * 8 + 2048 * 4;
+    static unsigned long long lds_set = 0ull;   // per device
+    if (hvpr_ensure_dyn_lds((const void *)k_topk_select, (int)lds, &lds_set) != 0) return HVPR_ERR_LAUNCH;
+    // The state that is zero between calls comes first and its place depends on `batch` only; the keys (rewritten by every
+    // call) follow it.  So calls with the same batch and any n_scores the workspace is large enough for can share it.
+    int *cnt = (int *)workspace;                                                                    // [batch]
+    unsigned *tbin = (unsigned *)((char *)cnt + ((batch * sizeof(int) + 255) / 256) * 256);        // [batch]
+    unsigned *hist = (unsigned *)((char *)tbin + ((batch * sizeof(unsigned) + 255) / 256) * 256);  // [batch][HBINS]
     unsigned *rank = (unsigned *)((char *)hist + (((size_t)batch * HBINS * sizeof(unsigned) + 255) / 256) * 256);   // [batch][SORTCAP]
+    unsigned long long *keys = (unsigned long long *)((char *)rank + (((size_t)batch * SORTCAP * sizeof(unsigned) + 255) / 256) * 256);
     int bx = hvpr_cdiv(n_scores, 256 * 4);
     if (bx > 1024) bx = 1024;
     // cnt and hist are zero on entry (workspace contract) and are returned to zero by k_hist_find / k_topk_select
@@ -459,9 +464,6 @@ extern "C" int hvpr_score_topk_f32(const float *scores, int batch, int n_scores,
     } else {
         hipLaunchKernelGGL(k_score_compact, dim3(bx, batch), dim3(256), 0, s, scores, n_scores, score_thresh, use_thresh, keys, cnt);
     }
-    const size_t lds = (size_t)SORTCAP * 8 + 2048 * 4;
-    static unsigned long long lds_set = 0ull;   // per device
-    if (hvpr_ensure_dyn_lds((const void *)k_topk_select, (int)lds, &lds_set) != 0) return HVPR_ERR_LAUNCH;
     hipLaunchKernelGGL(k_rank_count, dim3(SORTCAP / 256, SORTCAP / RK_CHUNK, batch), dim3(256), 0, s, keys, n_scores, cnt, rank);
     hipLaunchKernelGGL(k_rank_place, dim3(SORTCAP / 256, batch), dim3(256), 0, s, keys, n_scores, cnt, rank, pre_max, order,
                        sorted_scores);

@@ -618,6 +618,8 @@ class PostWorkspace:
 def score_topk(scores, score_thresh, pre_max, ws, want_scores=True):
     """scores (B, A) -> order (B, pre_max) i32, sorted scores (B, pre_max), counts (B,) i32."""
     B, A = scores.shape
+    if B != ws.batch:     # the workspace's zero state is laid out per frame
+        raise ValueError(f"score_topk: {B} frames on a workspace made for {ws.batch}")
     dev = scores.device
     order = torch.empty((B, pre_max), dtype=torch.int32, device=dev)
     ss = torch.empty((B, pre_max), dtype=torch.float32, device=dev) if want_scores else None

@@ -264,8 +264,10 @@ int hvpr_head_decode_f32(const float *head, int N, int H, int W, int head_channe
  *     class_agnostic_nms, pcdet/models/model_utils/model_nms_utils.py:8-16,22-24.
  *     scores [batch, n_scores]; order [batch, pre_max] i32 = ids sorted by (score desc, id asc);
  *     sorted_scores [batch, pre_max] (may be NULL); counts [batch] i32 = min(#passing, pre_max).
- *     use_thresh = 0 keeps every non-NaN score.  pre_max <= 8192.
- *     workspace: zero-filled by the caller ONCE; every call returns it zero-filled (no per-call memset).
+ *     use_thresh = 0 keeps every non-NaN score.  pre_max <= 8192.  -0.0 and +0.0 are equal scores (ties go by id);
+ *     sorted_scores holds +0.0 for both.
+ *     workspace: zero-filled by the caller ONCE; every call returns its counters, histogram and rank array to zero (no
+ *     per-call memset).  Calls that share a workspace pass the same batch; n_scores may change from call to call.
  * ------------------------------------------------------------------------------------------- */
 size_t hvpr_score_topk_workspace_bytes(int batch, int n_scores);
 int hvpr_score_topk_f32(const float *scores, int batch, int n_scores, float score_thresh, int use_thresh, int pre_max,
@@ -279,7 +281,8 @@ int hvpr_score_topk_f32(const float *scores, int batch, int n_scores, float scor
  *     hvpr_nms_bev_f32: candidate i is boxes[order ? order[i] : i], candidates already in descending score;
  *       n_device (may be NULL) holds the live count <= n_max (<= 16384); IoU > thresh suppresses (strict);
  *       keep[0..keep_count) = kept candidate positions, or order[position] when map_through_order != 0;
- *       at most max_keep are produced (NMS_POST_MAXSIZE).
+ *       at most max_keep are produced (NMS_POST_MAXSIZE).  A workspace of hvpr_nms_workspace_bytes(n) bytes serves every
+ *       n_max <= n.
  *     hvpr_boxes_pairwise_f32: mode 0 BEV overlap area, 1 BEV IoU, 2 3D IoU; out [n, m]; rows 7 floats apart.
  * ------------------------------------------------------------------------------------------- */
 size_t hvpr_nms_workspace_bytes(int n_max);

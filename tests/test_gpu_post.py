@@ -7,22 +7,10 @@ import torch
 
 from hvpr_amd import kernels
 from oracle import hvpr_oracle as O
+from post_paths import car_boxes as _boxes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _boxes(rng, n, spread=40.0, clustered=True):
-    """Car-sized boxes; clustered so that many pairs overlap."""
-    if clustered:
-        centres = rng.uniform([0, -20], [spread, 20], (max(n // 6, 1), 2))
-        xy = centres[rng.integers(0, len(centres), n)] + rng.normal(0, 0.8, (n, 2))
-    else:
-        xy = rng.uniform([0, -20], [spread, 20], (n, 2))
-    z = rng.normal(-1.0, 0.2, (n, 1))
-    size = np.array([3.9, 1.6, 1.56]) * rng.uniform(0.8, 1.2, (n, 3))
-    yaw = rng.uniform(-np.pi, np.pi, (n, 1))
-    return np.concatenate([xy, z, size, yaw], 1).astype(np.float32)
 
 
 def test_spatial_gate_vs_oracle():
