@@ -2,7 +2,14 @@
 spatial_attention.py): same registry key, ctor kwargs and state-dict names.  The eval forward runs every convolution
 on the fp32 matrix cores through hvpr_conv2d_nhwc_f32 with BatchNorm / ReLU / gate / residual fused in the epilogue,
 activations kept NHWC end to end, the gate computed ONCE per level (it depends only on the scale stream,
-base_bev_backbone.py:289-293) and each deconv writing straight into its slice of the 384-channel concat."""
+base_bev_backbone.py:289-293) and each deconv writing straight into its slice of the 384-channel concat.
+
+The eval forward is a plan and two steps.  _build_plan folds and packs, for the selected conv_precision only, what every level
+launches (_Level, in launch order); _trunk and _branch enqueue one level's layers through kernels.conv2d_nhwc, which picks the
+kernel from the packed type; _Fork owns the HIP streams the branches run on.  forward() runs every level; forward_head() /
+forward_tail() run the same steps as two halves on caller-owned boundary buffers (split_buffers), which the frame pipeline
+overlaps between neighbouring frames."""
+import collections
 import contextlib
 import os
 
@@ -43,20 +50,103 @@ def _conv_bn_relu(cin, cout, stride=1, zero_pad=False):
     return [nn.Conv2d(cin, cout, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(cout, eps=1e-3, momentum=0.01), nn.ReLU()]
 
 
-# Workgroup tile of hvpr_conv2d_nhwc_f32 per layer group and level: 0 = 128 px x 128 ch, 1 = 64 px x 64 ch, 2 = 128 px x 64 ch.
-# Measured on MI355X at batch 1 inside the whole frame (bench.py; the two streams of the backbone interact, so the per-layer
-# micro-benchmarks tools/bench_conv.py / bench_conv1x1.py do not decide alone); the sweeps are in profiles/NOTES_r04.md.
-_TILES = {"trunk": (1, 1, 1), "sfm": (1, 1, 1), "scale": (1, 1, 1), "deconv": (1, 1, 1)}   # deconv level 2: 128 x 64 won 0.2 % in round 1's 3-stage pipeline, 64 x 64 wins 0.7 % in the 4-stage one
+# Workgroup tile of hvpr_conv2d_nhwc_f32 (0 = 128 px x 128 ch, 1 = 64 px x 64 ch, 2 = 128 px x 64 ch): 64 x 64 on every layer group (trunk,
+# SFM, scale, deconv) and level.  Measured on MI355X at batch 1 inside the whole frame (bench.py; the streams of the backbone interact, so
+# the per-layer micro-benchmarks tools/bench_conv.py / bench_conv1x1.py do not decide alone); the sweeps are in profiles/NOTES_r04.md.
+# The k = s = 4 deconvolution of level 2 (K = 512, 2048 columns, 4.6 k pixels) is bound by what its tiles pull out of L2 and 128 x 64
+# halves its weight traffic per FLOP (121 -> 111 us alone): that won 0.2 % in round 1's 3-stage pipeline, 64 x 64 wins 0.7 % in the
+# 4-stage one.
+_TILE_CFG = 1
+# Pixel groups per workgroup of the Winograd kernel: 1 = 8 x 16 px x 64 channels on every level (16 x 16 px workgroups and 32-channel
+# tiles were measured slower inside the frame pipeline, profiles/NOTES_r04.md).
+_WINO_PX_GROUPS = 1
+
+# What the eval forward launches for one level, in launch order: trunk (packed layers), then on the branch scale, the gate (parameters
+# of kernels.spatial_gate), sfm_steps (one packed layer per SFM iteration) and deconv into out[..., coff:coff + up_filters[index]].
+_Level = collections.namedtuple("_Level", "index trunk scale gate sfm_steps deconv coff")
+_Plan = collections.namedtuple("_Plan", "levels planes")          # planes: bf16 planes per value of the trunk's activations, 0 = fp32
 
 
-def _tile_cfg(kind, level):
-    return _TILES[kind][min(level, 2)]
+def _fold_pack(pack, conv, bn, **kw):
+    """Fold the eval-mode BatchNorm `bn` into `conv`'s weights and pack them with kernels.pack_*."""
+    scale, shift = bn_scale_shift(bn)
+    return pack(conv.weight, scale, shift, **kw)
 
 
-def _wino_groups(level):
-    """Pixel groups per workgroup of the Winograd kernel: 1 = 8 x 16 px x 64 channels on every level (16 x 16 px workgroups and
-    32-channel tiles were measured slower inside the frame pipeline, profiles/NOTES_r04.md)."""
-    return 1
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()       # no copy when the scatter produced channels_last
+
+
+class _Fork:
+    """HIP streams and allocator lifetime of one eval-forward call.  The trunk (blocks of level i+1) does not depend on the attentive
+    branch of level i (scale conv, gate, the weight-shared SFM steps and the deconv), and the branches depend on each other only
+    through the scale stream y_i = scale_i(y_{i-1}).  The trunk runs on the caller's stream, every branch on sides[i] (waiting for its
+    x_i and, by event, for y_{i-1}): at batch 1 the upper levels have fewer tiles than the chip has workgroup slots.  sides = []: the
+    branches stay in line on the caller's stream."""
+
+    __slots__ = ("main", "sides", "used", "held", "y_event", "y_side", "eager")
+
+    def __init__(self, sides):
+        self.main, self.sides, self.used = torch.cuda.current_stream(), sides, []
+        # tensors another stream reads: referenced until the join, so that the allocator of the producing stream cannot hand their
+        # memory out again while the other stream still reads them
+        self.held = []
+        self.y_event = self.y_side = None
+        self.eager = not torch.cuda.is_current_stream_capturing()      # eager mode: record_stream keeps the caching allocator from recycling early
+
+    def branch(self, i, x, out):
+        """The stream context level i's branch is enqueued in."""
+        if not self.sides:
+            return contextlib.nullcontext()
+        side = self.sides[i]
+        self.used.append(side)
+        side.wait_stream(self.main)                 # x_i (and, at level 0, the scale stream's input) are ready for the branch
+        if self.y_event is not None and self.y_side is not side:
+            side.wait_event(self.y_event)           # y_{i-1} from the previous branch's stream
+        self.held.append(x)
+        if self.eager:
+            x.record_stream(side)
+            out.record_stream(side)
+        return torch.cuda.stream(side)
+
+    def y_ready(self, i, y):
+        """y_i is enqueued (call inside branch(i)): the next level's branch waits for this point, not for the whole branch."""
+        if self.sides:
+            self.y_side = self.sides[i]
+            self.y_event = torch.cuda.Event()
+            self.y_event.record(self.y_side)
+            self.held.append(y)
+            if self.eager:
+                y.record_stream(self.y_side)
+                if i + 1 < len(self.sides):
+                    y.record_stream(self.sides[i + 1])
+
+    def join(self):
+        for side in dict.fromkeys(self.used):       # only the streams this call forked (the other half of a split forward may own the others)
+            self.main.wait_stream(side)
+        self.held.clear()
+
+
+def _trunk(lv, x, out=None):
+    """The level's trunk convolutions, the last one into `out` when given."""
+    for pc in lv.trunk[:-1]:
+        x = kernels.conv2d_nhwc(x, pc)
+    return kernels.conv2d_nhwc(x, lv.trunk[-1], out=out)
+
+
+def _branch(lv, x, y, out, fork, y_out=None):
+    """The level's attentive branch on x = its trunk output and y = the scale stream: scale conv (into `y_out` when given), gate, SFM
+    steps, deconv into the level's slice of `out`.  Returns the level's scale output, the next level's y."""
+    with fork.branch(lv.index, x, out):
+        y = kernels.conv2d_nhwc(y, lv.scale, out=y_out)
+        fork.y_ready(lv.index, y)
+        gate = kernels.spatial_gate(y, *lv.gate)
+        for pc in lv.sfm_steps:
+            x = kernels.conv2d_nhwc(x, pc, gate=gate, resid=x)
+            fork.held.append(x)
+        fork.held.append(gate)
+        kernels.conv2d_nhwc(x, lv.deconv, out=out, out_coff=lv.coff)
+    return y
 
 
 class BaseBEVBackbone_Scale(nn.Module):
@@ -93,12 +183,9 @@ class BaseBEVBackbone_Scale(nn.Module):
         self.num_bev_features = sum(up_filters)
         self.attention = SpatialAttention()
         self._fold = FoldCache()
-        self._shape_key = None
-        self._side = None
         self._sides = None
         # HIP streams of the eval forward: "1" none, "2" trunk + one branch stream, "4" trunk + one stream per level's branch
         self.n_streams = int(os.environ.get("HVPR_BEV_STREAMS", "4"))
-        self.overlap_branches = self.n_streams != 1
         # "fp32": exact fp32 matrix-core kernel (default, the parity reference).  "bf16x3" / "bf16x6": trunk and SFM 3x3
         # convolutions on the bf16 matrix cores with operands split into 2 / 3 bf16 planes (kernels.conv2d_nhwc_bf3):
         # ~5e-6 relative error per layer / the fp32 kernel's own ~1.5e-6 (fp32 emulation)
@@ -112,17 +199,14 @@ class BaseBEVBackbone_Scale(nn.Module):
         self.conv_precision = precision
         self._fold.invalidate()
 
-    def _side_stream(self, device):
-        if self._side is None or self._side.device != device:
-            self._side = torch.cuda.Stream(device=device)
-        return self._side
-
-    def _branch_streams(self, device, n):
-        """One stream per level's attentive branch (n_streams == 4); a single shared one otherwise."""
-        if self.n_streams < 4:
-            return [self._side_stream(device)] * n
+    def _streams(self, device):
+        """The stream of every level's attentive branch (_Fork): one each (n_streams == 4), one shared by all (2), [] = in line (1)."""
+        n = len(self.blocks)
+        if self.n_streams == 1:
+            return []
         if self._sides is None or len(self._sides) != n or self._sides[0].device != device:
-            self._sides = [torch.cuda.Stream(device=device) for _ in range(n)]
+            own = [torch.cuda.Stream(device=device) for _ in range(n if self.n_streams >= 4 else 1)]
+            self._sides = [own[i % len(own)] for i in range(n)]
         return self._sides
 
     def train(self, mode=True):
@@ -133,53 +217,37 @@ class BaseBEVBackbone_Scale(nn.Module):
         self._fold.invalidate()
         return super()._load_from_state_dict(*a, **k)
 
-    def _build_packed(self, H, W):
-        packed = {"levels": [], "gate": self.attention.gate_params()}
-        h, w = H, W
-        for i in range(len(self.blocks)):
-            s = self.layer_strides[i]
-            h, w = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-            blk = self.blocks[i]
-            cout = blk[1].weight.shape[0]
-            cfg = _tile_cfg("trunk", i)
-            lv = {"convs": []}
-            sc, sh = bn_scale_shift(blk[2])
+    def _build_plan(self):
+        planes = self.PRECISIONS[self.conv_precision]
+
+        def conv_f32(conv, bn, stride=1):
             # stride-1 3x3 layers: Winograd F(2x2,3x3) kernel unless HVPR_CONV_ALGO=direct (kernels.pack_conv_auto)
-            wg = _wino_groups(i)
-            lv["convs"].append(kernels.pack_conv_auto(blk[1].weight, sc, sh, stride=s, tile_cfg=cfg, px_groups=wg))
-            for k in range(self.layer_nums[i]):
-                sc, sh = bn_scale_shift(blk[5 + 3 * k])
-                lv["convs"].append(kernels.pack_conv_auto(blk[4 + 3 * k].weight, sc, sh, tile_cfg=cfg, px_groups=wg))
-            sc, sh = bn_scale_shift(self.sfmblocks_down[i][1])
-            lv["sfm"] = kernels.pack_conv_auto(self.sfmblocks_down[i][0].weight, sc, sh, tile_cfg=_tile_cfg("sfm", i), px_groups=wg)
-            planes = self.PRECISIONS[self.conv_precision]
-            if planes:
-                c3 = 4                                # 64 px x 64 ch tiles, weights staged per kernel row (2-3 workgroups per CU)
-                lv["convs3"] = []
-                sc, sh = bn_scale_shift(blk[2])
-                lv["convs3"].append(kernels.pack_conv_bf3(blk[1].weight, sc, sh, stride=s, tile_cfg=c3, planes=planes))
-                for k in range(self.layer_nums[i]):
-                    sc, sh = bn_scale_shift(blk[5 + 3 * k])
-                    lv["convs3"].append(kernels.pack_conv_bf3(blk[4 + 3 * k].weight, sc, sh, tile_cfg=c3, planes=planes))
-                sc, sh = bn_scale_shift(self.sfmblocks_down[i][1])
-                lv["sfm3"] = kernels.pack_conv_bf3(self.sfmblocks_down[i][0].weight, sc, sh, tile_cfg=c3, planes=planes)
-                de = self.deblocks[i]
-                sc, sh = bn_scale_shift(de[1])
-                # two planes: the deconvolution runs split as well; three planes: its six-product 1x1 is slower than the fp32 kernel
-                lv["deconv3"] = kernels.pack_deconv_bf3(de[0].weight, sc, sh, planes=planes) \
-                    if (planes == 2 and de[0].weight.shape[0] % 64 == 0) else None
-            sl = self.scale_layers[i]
-            sc, sh = bn_scale_shift(sl[2])
-            lv["scale"] = kernels.pack_conv_auto(sl[1].weight, sc, sh, stride=s, tile_cfg=_tile_cfg("scale", i), px_groups=wg)
+            return _fold_pack(kernels.pack_conv_auto, conv, bn, stride=stride, tile_cfg=_TILE_CFG, px_groups=_WINO_PX_GROUPS)
+
+        def conv_bf3(conv, bn, stride=1):
+            # tile_cfg 4: 64 px x 64 ch tiles, weights staged per kernel row (2-3 workgroups per CU)
+            return _fold_pack(kernels.pack_conv_bf3, conv, bn, stride=stride, tile_cfg=4, planes=planes)
+
+        conv = conv_bf3 if planes else conv_f32          # trunk and SFM layers; the scale stream is always fp32
+        gate = self.attention.gate_params()
+        levels, coff = [], 0
+        for i, blk in enumerate(self.blocks):
+            s = self.layer_strides[i]
+            trunk = [conv(blk[1], blk[2], stride=s)] + [conv(blk[4 + 3 * k], blk[5 + 3 * k]) for k in range(self.layer_nums[i])]
+            sfm = conv(*self.sfmblocks_down[i][:2])
+            scale = conv_f32(*self.scale_layers[i][1:3], stride=s)
             de = self.deblocks[i]
-            sc, sh = bn_scale_shift(de[1])
-            us = int(self.upsample_strides[i])
-            # the k = s = 4 deconvolution (K = 512, 2048 columns, 4.6 k pixels) is bound by what its tiles pull out of L2: the
-            # 128 px x 64 ch tile halves the weight traffic per FLOP (121 -> 111 us alone; +0.2 % frames/s in an A/B of whole frames)
-            dcfg = _tile_cfg("deconv", i)
-            lv["deconv"] = kernels.pack_deconv(de[0].weight, sc, sh, tile_cfg=dcfg)
-            packed["levels"].append(lv)
-        return packed
+            # two planes: the deconvolution runs split as well; three planes: its six-product 1x1 is slower than the fp32 kernel
+            if planes == 2 and de[0].weight.shape[0] % 64 == 0:
+                deconv = _fold_pack(kernels.pack_deconv_bf3, de[0], de[1], planes=planes)
+            else:
+                deconv = _fold_pack(kernels.pack_deconv, de[0], de[1], tile_cfg=_TILE_CFG)
+            sfm_steps = [sfm] * self.sfm_layer_nums[i]
+            if planes and sfm_steps and isinstance(deconv, kernels.PackedConv):
+                sfm_steps[-1] = sfm.fp32_output()          # the last step hands fp32 to the deconvolution only when that one runs on the fp32 kernel
+            levels.append(_Level(i, trunk, scale, gate, sfm_steps, deconv, coff))
+            coff += self.up_filters[i]
+        return _Plan(levels, planes)
 
     def _forward_train(self, data_dict):
         """Training forward, base_bev_backbone.py:228-279: the memory-fed and the point-fed canvases go through the SAME
@@ -252,127 +320,57 @@ class BaseBEVBackbone_Scale(nn.Module):
         data_dict["spatial_features_point_2d"] = ct.bn_relu_cat(ups_p, bns).permute(0, 3, 1, 2)
         return data_dict
 
+    def _head(self, plan, x, y, out, level, x_out={}, y_out=None):
+        """The whole trunk and the branches of the levels below `level`; x_out[i] / y_out receive the trunk output of level i / the
+        scale output of level - 1."""
+        fork = _Fork(self._streams(y.device))
+        for lv in plan.levels:
+            x = _trunk(lv, x, out=x_out.get(lv.index))
+            if lv.index < level:
+                y = _branch(lv, x, y, out, fork, y_out=y_out if lv.index == level - 1 else None)
+        fork.join()
+
     def forward(self, data_dict):
-        """Eval forward.  data_dict["_bev_split"] = {"phase": "a" | "b", "level": L, "x": {i: ...}, "y": ..., "out": ...} runs it in
-        two halves on caller-owned boundary buffers (the frame pipeline overlaps the halves of neighbouring frames): phase "a" =
-        the whole trunk and the branches of the levels below L (writes x[i] = the trunk output of every level i >= L, y = the scale
-        output of level L - 1, and its slices of out = the concat); phase "b" = the branches of the levels >= L (reads x, y;
-        finishes out)."""
         if self.training:
             return self._forward_train(data_dict)
-        split = data_dict.get("_bev_split")
-        phase = split["phase"] if split is not None else None
-        n_lv = len(self.blocks)
-        L = split["level"] if split is not None else n_lv
-        if phase == "b":
-            x, y, out = None, split["y"], split["out"]
-            B = y.shape[0]
-            H, W = self._shape_key
-        else:
-            sp, sc = data_dict["spatial_features"], data_dict["spatial_scale_features"]
-            x = sp.permute(0, 2, 3, 1).contiguous()       # no copy when the scatter produced channels_last
-            y = sc.permute(0, 2, 3, 1).contiguous()
-            B, H, W, _ = x.shape
-            if self._shape_key != (H, W):
-                self._fold.invalidate()
-                self._shape_key = (H, W)
-        P = self._fold.get(y.device, lambda: self._build_packed(H, W))
-        gw, gb, gs, gt = P["gate"]
-        gw = gw.to(y.device)
-        us_all = [int(u) for u in self.upsample_strides]
-        if phase is None:
-            # output size of the concat: level-0 resolution after its own stride, times its upsample stride
-            h0 = (H + 2 - 3) // self.layer_strides[0] + 1
-            w0 = (W + 2 - 3) // self.layer_strides[0] + 1
-            out = torch.empty((B, h0 * us_all[0], w0 * us_all[0], self.num_bev_features), dtype=torch.float32, device=x.device)
-        elif phase == "a":
-            out = split["out"]
-        # HIP streams: the trunk (blocks of level i+1) does not depend on the attentive branch of level i (scale conv, gate, the
-        # three weight-shared SFM steps and the deconv), and the branches depend on each other only through the scale stream
-        # y_i = scale_i(y_{i-1}).  The trunk runs on the caller's stream, every branch on a stream of its own (waiting for its
-        # x_i and, by event, for y_{i-1}): at batch 1 the upper levels have fewer tiles than the chip has workgroup slots.
-        main = torch.cuda.current_stream()
-        # phase "b" already runs on a forked stream of the caller's capture: forking again from it (a second level of stream
-        # forks inside one hipGraph capture) crashed hipStreamEndCapture on this ROCm build, so its branches stay in line
-        two_streams = self.overlap_branches and phase != "b"
-        sides = self._branch_streams(y.device, n_lv) if two_streams else []
-        coff = 0
-        capturing = torch.cuda.is_current_stream_capturing()
-        held = []     # tensors another stream reads: referenced until the join, so that the allocator of the producing stream
-        #               cannot hand their memory out again while the other stream still reads them
-        y_ready = None
-        used = []
-        planes = self.PRECISIONS[self.conv_precision]
-        bf3 = planes > 0
-        assert not (bf3 and phase is not None), "the split forward runs the fp32 kernels"
-        if bf3:
-            x = kernels.split_bf16(x, planes)  # the trunk runs in split-bf16 form from here on
-        for i, lv in enumerate(P["levels"]):
-            in_b = i >= L
-            if phase == "b":
-                if not in_b:
-                    coff += self.up_filters[i]
-                    continue
-                x = split["x"][i]
-            elif bf3:
-                for pc in lv["convs3"]:
-                    x = kernels.conv2d_nhwc_bf3(x, pc)
-            else:
-                for j, pc in enumerate(lv["convs"]):
-                    x = kernels.conv2d_nhwc(x, pc, out=split["x"][i] if (phase == "a" and in_b and j == len(lv["convs"]) - 1) else None)
-            if phase == "a" and in_b:
-                coff += self.up_filters[i]
-                continue                                   # this level's branch is phase "b"
-            if two_streams:
-                side = sides[i]
-                used.append(side)
-                side.wait_stream(main)          # x_i (and, at level 0, the scale stream's input) are ready for the branch
-                if y_ready is not None and sides[i - 1] is not side:
-                    side.wait_event(y_ready)    # y_{i-1} from the previous branch's stream
-                held.append(x)
-                ctx = torch.cuda.stream(side)
-            else:
-                ctx = contextlib.nullcontext()
-            with ctx:
-                y = kernels.conv2d_nhwc(y, lv["scale"], out=split["y"] if (phase == "a" and i == L - 1) else None)
-                if two_streams:
-                    y_ready = torch.cuda.Event()
-                    y_ready.record(side)
-                    held.append(y)
-                gate = kernels.spatial_gate(y, gw, gb, gs, gt)
-                x_att = x
-                nsfm = self.sfm_layer_nums[i]
-                for it in range(nsfm):
-                    if bf3:     # the last step hands fp32 to the deconvolution only when that one runs on the fp32 kernel
-                        x_att = kernels.conv2d_nhwc_bf3(x_att, lv["sfm3"], out_split=(it + 1 < nsfm or lv["deconv3"] is not None),
-                                                        gate=gate, resid=x_att)
-                    else:
-                        x_att = kernels.conv2d_nhwc(x_att, lv["sfm"], gate=gate, resid=x_att)
-                    held.append(x_att)
-                held.append(gate)
-                if bf3 and lv["deconv3"] is not None:
-                    kernels.deconv_nhwc_bf3(x_att, lv["deconv3"], out, out_coff=coff)
-                elif bf3 and nsfm == 0:
-                    kernels.conv2d_nhwc(kernels.unsplit_bf16(x_att), lv["deconv"], out=out, out_coff=coff)
-                else:
-                    kernels.conv2d_nhwc(x_att, lv["deconv"], out=out, out_coff=coff)
-                if two_streams and not capturing:     # eager mode: keep the caching allocator from recycling early
-                    for t in (x, y, out):
-                        t.record_stream(side)
-                    if i + 1 < len(sides):
-                        y.record_stream(sides[i + 1])
-            coff += self.up_filters[i]
-        if two_streams:
-            for side in dict.fromkeys(used):          # only the streams this call forked (another phase may own the others)
-                main.wait_stream(side)
-        held.clear()
-        if phase == "a":
-            return data_dict
+        x, y = _nhwc(data_dict["spatial_features"]), _nhwc(data_dict["spatial_scale_features"])
+        plan = self._fold.get(y.device, self._build_plan)
+        # output size of the concat: level-0 resolution after its own stride, times its upsample stride
+        B, H, W, _ = x.shape
+        s0, us0 = self.layer_strides[0], int(self.upsample_strides[0])
+        out = torch.empty((B, ((H + 2 - 3) // s0 + 1) * us0, ((W + 2 - 3) // s0 + 1) * us0, self.num_bev_features),
+                          dtype=torch.float32, device=x.device)
+        if plan.planes:
+            x = kernels.split_bf16(x, plan.planes)        # the trunk runs in split-bf16 form from here on
+        self._head(plan, x, y, out, len(plan.levels))
         data_dict["spatial_features_2d"] = out.permute(0, 3, 1, 2)   # (B, 384, H, W), channels_last
         return data_dict
 
+    def forward_head(self, spatial, scale, split):
+        """First half of the eval forward on the boundary buffers `split` (split_buffers) — the frame pipeline overlaps the halves of
+        neighbouring frames: the whole trunk and the branches of the levels below L = split["level"].  Writes split["x"][i] = the trunk
+        output of every level i >= L, split["y"] = the scale output of level L - 1, and its slices of split["out"] = the concat."""
+        y = _nhwc(scale)
+        plan = self._fold.get(y.device, self._build_plan)
+        assert not plan.planes, "the split forward runs the fp32 kernels"
+        self._head(plan, _nhwc(spatial), y, split["out"], split["level"], split["x"], split["y"])
+
+    def forward_tail(self, split):
+        """Second half: the branches of the levels >= split["level"] (reads split["x"], split["y"]; finishes split["out"]).  Returns
+        spatial_features_2d, a view of split["out"]."""
+        y, out = split["y"], split["out"]
+        plan = self._fold.get(y.device, self._build_plan)
+        assert not plan.planes, "the split forward runs the fp32 kernels"
+        # the caller runs this half on a forked stream of its capture: forking again from it (a second level of stream forks inside
+        # one hipGraph capture) crashed hipStreamEndCapture on this ROCm build, so its branches stay in line
+        fork = _Fork([])
+        for lv in plan.levels[split["level"]:]:
+            y = _branch(lv, split["x"][lv.index], y, out, fork)
+        fork.join()
+        return out.permute(0, 3, 1, 2)                               # (B, 384, H, W), channels_last
+
     def split_buffers(self, batch_size, H, W, device, level=None):
-        """Boundary buffers of the two-phase forward for canvases of (H, W): x[i] (trunk output of every level i >= level), y
+        """Boundary buffers of forward_head / forward_tail for canvases of (H, W): x[i] (trunk output of every level i >= level), y
         (scale output of level - 1), out (the concat).  level defaults to the last one; >= 1."""
         n_lv = len(self.blocks)
         if level is None:

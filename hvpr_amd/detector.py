@@ -414,13 +414,11 @@ class MixAnchor_Memory(_VoxelizingDetector):
     def stage_dense_a(self, batch_dict, split):
         """First half of stage_dense on caller-owned boundary buffers (BaseBEVBackbone_Scale.split_buffers): the trunk and every
         branch but the last."""
-        return self.backbone_2d({**batch_dict, "_bev_split": {**split, "phase": "a"}})
+        self.backbone_2d.forward_head(batch_dict["spatial_features"], batch_dict["spatial_scale_features"], split)
 
     def stage_dense_b(self, batch_dict, split):
         """Second half: the last level's branch, head and decode."""
-        bd = self.backbone_2d({**batch_dict, "_bev_split": {**split, "phase": "b"}})
-        bd.pop("_bev_split", None)
-        return self.dense_head(bd)
+        return self.dense_head({**batch_dict, "spatial_features_2d": self.backbone_2d.forward_tail(split)})
 
     def prefetch_point_indices(self, batch_dict):
         """Training: compute the point stream's index tensors (FPS, ball query, three-NN: they depend on the coordinates only)
@@ -493,6 +491,15 @@ class _CapturedState:
                                    "load_state_dict, set_conv_precision or a workspace re-allocation): capture a new graph")
 
 
+def _check_voxelizer_status(model):
+    """check_status() of GraphedForward / PipelinedForward.  SYNCHRONISES: raises when the voxelizer workspace's error word is up (a
+    one-launch index kernel gave up a wait: include/hvpr_amd.h, hvpr_voxelize_workspace_status).  Call it wherever the results of a
+    run are read back."""
+    for vg in getattr(model, "_voxgen", {}).values():
+        if vg._ws is not None:
+            vg._ws.status()
+
+
 class GraphedForward:
     """Whole-frame hipGraph of the eval forward (voxelize -> ... -> NMS) for a fixed input shape.
 
@@ -528,7 +535,8 @@ class GraphedForward:
         self.graph.replay()
         return self.static_out
 
-    check_status = None      # (assigned below: the same method as PipelinedForward's)
+    def check_status(self):
+        _check_voxelizer_status(self.model)
 
 
 class PipelinedForward:
@@ -656,11 +664,7 @@ class PipelinedForward:
         return d
 
     def check_status(self):
-        """SYNCHRONISES: raises when the voxelizer workspace's error word is up (a one-launch index kernel gave up a wait:
-        include/hvpr_amd.h, hvpr_voxelize_workspace_status).  Call it wherever the results of a run are read back."""
-        for vg in getattr(self.model, "_voxgen", {}).values():
-            if vg._ws is not None:
-                vg._ws.status()
+        _check_voxelizer_status(self.model)
 
     def flush(self):
         """depth - 1 more steps (re-encoding the last inputs, whose results are dropped): yields the results of the frames still in
@@ -671,9 +675,6 @@ class PipelinedForward:
             self.step += 1
             if self.step >= self.depth:
                 yield self.out[p]
-
-
-GraphedForward.check_status = PipelinedForward.check_status
 
 
 class PointPillar(_VoxelizingDetector):

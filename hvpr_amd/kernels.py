@@ -217,11 +217,18 @@ def scatter_bev_fwd(pillar, memory, scale, coords, batch, nx, ny, workspace, m_d
 
 # ------------------------------------------------------------------------------------------------ split-bf16 convolutions
 class PackedConvBf3:
-    """3x3 conv weights split into `planes` bf16 planes, layout [9, Cin/8, planes, cout_pad, 8] (BatchNorm scale folded)."""
+    """Weights split into `planes` bf16 planes, layout [taps, Cin/8, planes, cout_pad, 8] (BatchNorm scale folded).  up is None: a 3x3
+    convolution (pack_conv_bf3) whose output is split-bf16 again (out_split) or fp32; up = s: a ConvTranspose2d with kernel ==
+    stride == s as a 1x1 GEMM (pack_deconv_bf3), fp32 output."""
 
-    def __init__(self, w, bias, cin, cout, cout_pad, stride, relu, tile_cfg, planes):
+    def __init__(self, w, bias, cin, cout, cout_pad, stride, relu, tile_cfg, planes, up=None, out_split=True):
         self.w, self.bias, self.cin, self.cout, self.cout_pad = w, bias, cin, cout, cout_pad
-        self.stride, self.relu, self.tile_cfg, self.planes = stride, relu, tile_cfg, planes
+        self.stride, self.relu, self.tile_cfg, self.planes, self.up, self.out_split = stride, relu, tile_cfg, planes, up, out_split
+
+    def fp32_output(self):
+        """The same layer (shared weight image) writing fp32 NHWC: the hand-over from a split-bf16 chain to an fp32 kernel."""
+        return PackedConvBf3(self.w, self.bias, self.cin, self.cout, self.cout_pad, self.stride, self.relu, self.tile_cfg, self.planes,
+                             out_split=False)
 
 
 def _planes_of(x, planes):
@@ -262,9 +269,7 @@ def pack_deconv_bf3(weight, scale, shift, relu=True, planes=2):
         wp[0, :, k, :cols, :] = part.reshape(cin // 8, 8, cols).permute(0, 2, 1)
     b = torch.zeros((cout_pad,), dtype=torch.float32, device=w.device)
     b[:cols] = shift.detach().float().repeat(s * s)
-    pc = PackedConvBf3(wp.contiguous(), b, cin, cout, cout_pad, 1, relu, 1, planes)
-    pc.up = s
-    return pc
+    return PackedConvBf3(wp.contiguous(), b, cin, cout, cout_pad, 1, relu, 1, planes, up=s)
 
 
 def deconv_nhwc_bf3(xs, pc, out, out_coff=0):
@@ -532,7 +537,17 @@ def pack_conv_auto(weight, scale=None, shift=None, stride=1, relu=True, tile_cfg
 
 
 def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None):
-    """x (N,H,W,Cin) contiguous f32 -> (N,OH*up,OW*up,C) ; optional fused y = gate*y + resid (SFM step)."""
+    """x (N,H,W,Cin) contiguous f32 -> (N,OH*up,OW*up,C) ; optional fused y = gate*y + resid (SFM step).  The packed type selects the
+    kernel.  A PackedConvBf3 takes split-bf16 activations (split_bf16) and returns them, or fp32 when pc.out_split is off or it is
+    a deconvolution; split-bf16 activations handed to an fp32 layer are recombined first."""
+    if isinstance(pc, PackedConvBf3):
+        if pc.up is not None:
+            assert gate is None and resid is None
+            return deconv_nhwc_bf3(x, pc, out, out_coff=out_coff)
+        assert out is None, "the split-bf16 convolution allocates its own output"
+        return conv2d_nhwc_bf3(x, pc, out_split=pc.out_split, gate=gate, resid=resid)
+    if x.dtype == torch.bfloat16:
+        x = unsplit_bf16(x)
     if isinstance(pc, PackedConvWino):
         return conv2d_wino_nhwc(x, pc, out=out, out_coff=out_coff, gate=gate, resid=resid)
     N, H, W, cin = x.shape
