@@ -190,6 +190,27 @@ def segment_sum_rows(src, src_off, C, edge_row, edge_w, chunk_ptr, dest_ptr, n_d
     return dst
 
 
+def attend_rows(q, rows, idx=None, k=None):
+    """hvpr_attend_rows_fwd_f32: w[m] = softmax_j <q[m], rows[r(m,j)]>, out[m] = sum_j w[m,j] rows[r(m,j)] without the gathered
+    (M, k, 64) tensor.  q (M, 64), rows (N, 64) f32; idx (M, k) i32 picks rows of the table, idx=None is the dense form over
+    rows = an (M*k, 64) tensor (k given).  Returns (out (M, 64), w (M, k)); no autograd here (map_to_bev._AttendRows)."""
+    if idx is not None:
+        if idx.dim() != 2 or (k is not None and int(k) != idx.shape[1]):
+            raise ValueError("hvpr_amd: attend_rows needs idx of shape (M, k)")
+        k = idx.shape[1]
+    elif k is None:
+        raise ValueError("hvpr_amd: attend_rows without idx needs k")
+    M, C = q.shape
+    if rows.dim() != 2 or rows.shape[1] != C or (idx is not None and idx.shape[0] != M):
+        raise ValueError("hvpr_amd: attend_rows needs q (M, C), rows (N, C) and idx (M, k)")
+    qp, rp, ip = _ptr(q, torch.float32, "q"), _ptr(rows, torch.float32, "rows"), _ptr(idx, torch.int32, "idx")
+    out = torch.empty((M, C), dtype=torch.float32, device=q.device)
+    w = torch.empty((M, int(k)), dtype=torch.float32, device=q.device)
+    check(lib().hvpr_attend_rows_fwd_f32(qp, M, rp, rows.shape[0], ip, int(k), C, out.data_ptr(), w.data_ptr(), _stream()),
+          "hvpr_attend_rows_fwd_f32")
+    return out, w
+
+
 def scatter_workspace(batch, nx, ny, device):
     """Idle cell map (-1 everywhere); every call returns it to idle."""
     n = lib().hvpr_scatter_workspace_bytes(batch, nx, ny) // 4

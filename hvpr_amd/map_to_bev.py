@@ -59,9 +59,8 @@ class MemoryUnit_Agg(nn.Module):
         is not returned: nothing on the path consumes it, pointpillar_scatter.py:133-138).  Torch form: tests/torch_forms.py."""
         nv, _, d = positives.shape
         self._check_train(positives, d)
-        mem = _MemoryTrain.apply(positives.reshape(-1, d), self.weight, float(self.shrink_thres)).reshape(nv, k, d)
-        agg = torch.softmax((mem * pillars.unsqueeze(1)).sum(dim=2), dim=1)
-        return {"output": (agg.detach().unsqueeze(2) * mem).sum(dim=1)}
+        mem = _MemoryTrain.apply(positives.reshape(-1, d), self.weight, float(self.shrink_thres))     # (nv * k, d)
+        return {"output": _AttendRows.apply(pillars, mem, None, None)}                                # :53-57, dense form
 
     def forward_train_indexed(self, pillars, k, points, idx, plan=None):
         """The training branch when the k positives of every pillar are ROWS OF ONE POINT TENSOR, positives = points[idx] (what
@@ -74,9 +73,7 @@ class MemoryUnit_Agg(nn.Module):
         nv, d = idx.shape[0], points.shape[1]
         self._check_train(points, d)
         mem_points = _MemoryTrain.apply(points, self.weight, float(self.shrink_thres))      # (N, d)
-        mem = _GatherRows.apply(mem_points, idx, plan)                                       # (nv, k, d)
-        agg = torch.softmax((mem * pillars.unsqueeze(1)).sum(dim=2), dim=1)
-        return {"output": (agg.detach().unsqueeze(2) * mem).sum(dim=1)}
+        return {"output": _AttendRows.apply(pillars, mem_points, idx, plan)}                 # :53-57 over mem_points[idx], never formed
 
     def extra_repr(self):
         return f"mem_dim={self.mem_dim}, fea_dim={self.fea_dim}"
@@ -148,16 +145,66 @@ class _GatherRows(torch.autograd.Function):
 
 class _EdgePlan:
     """The picks idx -> rows of an (n, C) tensor grouped by destination (kernels.edges_by_destination: one stable argsort + a
-    handful of scans), built on first use and shared by every gather of the SAME index tensor — the training branch gathers the point
-    features and the per-point memory read-out with one idx."""
+    handful of scans), built on first use and shared by every gather of the SAME index tensor — the training branch attends over the
+    point features and over the per-point memory read-out with one idx."""
 
     def __init__(self, idx, n):
-        self.idx, self.n, self._plan = idx, n, None
+        self.idx, self.n, self._plan, self._owner, self._i32 = idx, n, None, None, None
 
     def get(self):
         if self._plan is None:
             self._plan = kernels.edges_by_destination(self.idx.reshape(-1).to(torch.int64), self.n)
         return self._plan
+
+    def idx32(self):
+        """idx as the contiguous i32 tensor the kernels read."""
+        if self._i32 is None:
+            self._i32 = self.idx.to(torch.int32).contiguous()
+        return self._i32
+
+    def owner(self):
+        """For idx (M, k): the row m = pick / k of every pick in the plan's order (i32) — the edge_row of _AttendRows' backward, built
+        once and shared like the plan itself."""
+        if self._owner is None:
+            self._owner = torch.div(self.get()[0], self.idx.shape[-1], rounding_mode="floor")
+        return self._owner
+
+
+class _AttendRows(torch.autograd.Function):
+    """out[m] = sum_j w[m,j] rows[r(m,j)] with w[m] = softmax_j <q[m], rows[r(m,j)]> DETACHED — get_score's aggregate
+    (pointpillar_scatter.py:76-81) and the memory's (memory_module.py:53-57) on hvpr_attend_rows_fwd_f32: the gathered (M, k, C)
+    tensor exists neither forward nor backward.  apply(q, rows, idx, plan): idx (M, k) integer picks of rows (N, C) with their
+    _EdgePlan (optional: built here when absent); idx None = the dense form over rows (M*k, C), row m*k + j being pick j of m.
+    Backward: the weights are constants, so d rows[n] = sum over the picks e = (m, j) of n, in ascending e, of w[m,j] d out[m] —
+    hvpr_segment_sum_rows_f32 over the plan (fixed order, no atomics); dense: d rows[m*k+j] = w[m,j] d out[m].  No gradient to q."""
+
+    @staticmethod
+    def forward(ctx, q, rows, idx, plan=None):
+        q, rows = q.detach().contiguous(), rows.detach().contiguous()
+        if idx is None:
+            if rows.shape[0] % max(q.shape[0], 1):
+                raise ValueError("hvpr_amd: the dense attend needs rows (M * k, C) for q (M, C)")
+            out, w = kernels.attend_rows(q, rows, None, rows.shape[0] // q.shape[0] if q.shape[0] else 1)
+        else:
+            if plan is None:
+                plan = _EdgePlan(idx, rows.shape[0])
+            out, w = kernels.attend_rows(q, rows, plan.idx32())
+        ctx.save_for_backward(w)
+        ctx.plan, ctx.n = plan, rows.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        (w,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        grad = grad.contiguous()
+        if ctx.plan is None:
+            return None, (w.unsqueeze(2) * grad.unsqueeze(1)).reshape(ctx.n, grad.shape[1]), None, None
+        order, chunk_ptr, dest_ptr = ctx.plan.get()
+        edge_w = torch.index_select(w.reshape(-1), 0, order)
+        g = kernels.segment_sum_rows(grad, 0, grad.shape[1], ctx.plan.owner(), edge_w, chunk_ptr, dest_ptr, ctx.n)
+        return None, g, None, None
 
 
 class _ScatterCanvas(torch.autograd.Function):
@@ -278,9 +325,8 @@ class PointPillarScatter_Agg_Memory_1_scale(_ScatterBase):
         # formed transposed so that the top-k runs along the contiguous dimension.
         with torch.no_grad():
             idx = self._topk_points(pillars.detach(), points.detach())            # (M, k), descending
-        positives = _GatherRows.apply(points, idx)                                          # (M, k, C)
-        w = torch.softmax((pillars.unsqueeze(1) * positives).sum(dim=2), dim=1)            # (M, k) logits of the k positives
-        return (w.detach().unsqueeze(2) * positives).sum(dim=1), positives
+        positives = _GatherRows.apply(points, idx)                                          # (M, k, C): returned, so it is formed here
+        return _AttendRows.apply(pillars, positives.reshape(-1, positives.shape[2]), None, None), positives
 
     def _topk_points(self, pillars, points):
         """Indices (M, k) of the k points with the largest pillar . point logits, descending — hvpr_point_pillar_topk_f32: the
@@ -324,10 +370,8 @@ class PointPillarScatter_Agg_Memory_1_scale(_ScatterBase):
                          for (v0, v1), (p0, p1) in zip(vr, pr) if v1 > v0]
             idx = torch.cat(picks, 0) if picks else torch.zeros((0, self.k), dtype=torch.long, device=pf.device)
             plan = _EdgePlan(idx, point_f.shape[0])
-            positives = _GatherRows.apply(point_f, idx, plan)                                  # (M, k, C)
-            wgt = torch.softmax((pf.unsqueeze(1) * positives).sum(dim=2), dim=1)               # get_score, :76-83
-            pos_point = (wgt.detach().unsqueeze(2) * positives).sum(dim=1)
-            # the memory's second input IS positives = point_f[idx] (T1): addressed once per point, then gathered (MemoryUnit_Agg)
+            pos_point = _AttendRows.apply(pf, point_f, idx, plan)                              # get_score, :76-83, on point_f[idx]
+            # the memory's second input IS positives = point_f[idx] (T1): addressed once per point, attended by index (MemoryUnit_Agg)
             pos_mem = self.memory.forward_train_indexed(pf, self.k, point_f, idx, plan)["output"]
         else:       # rows not grouped by frame: the reference's boolean masks, frame by frame
             for b in range(B):

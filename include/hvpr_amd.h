@@ -391,6 +391,18 @@ int hvpr_segment_sum_rows_f32(const float *src, long long src_stride, int src_of
                               const float *edge_w, const int32_t *rowptr, long long n_dst, float *dst, long long dst_stride,
                               hvpr_stream_t stream);
 
+/* a10 (training)  "Attend over k rows": the second half of get_score (pointpillar_scatter.py:76-81) and the aggregation of the
+ * memory's training branch (memory_module.py:53-57) in one launch, without the gathered (M, k, C) tensor:
+ *     w[m][j] = softmax_j( <q[m], rows[r(m,j)]> ), j < k (row maximum subtracted);   out[m] = sum_j w[m][j] * rows[r(m,j)], ascending j
+ * q [M,C], rows [N,C], out [M,C], w [M,k] (what the backward needs: the weights are constants for autograd, so d rows is
+ * hvpr_segment_sum_rows_f32 with src = d out, edge_row = pick / k, edge_w = w, and there is no d q).  r(m,j) = idx[m*k+j] (i32), or
+ * with idx == NULL the dense form r(m,j) = m*k+j over the caller's (M,k,C) tensor (then N must be M*k).  An index outside [0, N)
+ * reads as a row of zeros.  One fixed order per output element: two runs, and the dense and the indexed form on equal row values,
+ * give the same bits.  C == 64 and 1 <= k <= 32, else HVPR_ERR_UNSUPPORTED; M == 0 is a no-op; every argument check is made on the
+ * host before any device call.  Row offsets are 64-bit. */
+int hvpr_attend_rows_fwd_f32(const float *q, int M, const float *rows, long long N, const int32_t *idx, int k, int C, float *out,
+                             float *w, hvpr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a10 (training)  MemAE memory addressing with hard shrinkage, MemoryUnit_Agg.forward training branch,
  *     map_to_bev/memory_module.py:31-48 (+ hard_shrink_relu :85-87), without materialising the (R, n_items) attention:
