@@ -45,16 +45,17 @@ struct GtLds {
     int cls[kMaxGt];
 };
 
-// the frame's ground truths in LDS: nearest-axis boxes, areas, and `use` = inside the valid range (trailing all-zero rows are
-// padding, axis_aligned_target_assigner.py:53-57) and of this anchor set's class (:66-70; python's class_names[c - 1]: class 0
-// wraps to the last class)
+// the frame's ground truths in LDS: nearest-axis boxes, areas, and `use` = inside the valid range (trailing rows whose SIGNED sum
+// over the 7 box fields, class column excluded, is exactly 0 are padding; row 0 always stays: `while cnt > 0 and cur_gt[cnt].sum()
+// == 0`, axis_aligned_target_assigner.py:53-57) and of this anchor set's class (:62-66; python's class_names[c - 1]: class 0 wraps
+// to the last class)
 __device__ __forceinline__ void load_gt(GtLds &s, const float *__restrict__ gt, int b, int G, int class_index, int n_classes, int *s_last) {
     if (threadIdx.x == 0) *s_last = 0;
     __syncthreads();
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         const float *p = gt + ((size_t)b * G + g) * 8;
         float sum = 0.f;
-        for (int j = 0; j < 8; ++j) sum += fabsf(p[j]);
+        for (int j = 0; j < 7; ++j) sum += p[j];                  // left to right, as written (contraction is off for this file)
         if (sum != 0.f) atomicMax(s_last, g);
     }
     __syncthreads();
@@ -204,7 +205,10 @@ __global__ void __launch_bounds__(256) k_rpn_losses(const float *__restrict__ cl
             const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
             l_cls += aw * pt * pt * bce * cls_w;
             const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-            g_cls[i * NC + k] = aw * (2.f * pt * dpt * bce + pt * pt * (p - t)) * cls_w * inv_b * c.cls_weight;
+            // d bce / dx = p - t; at x == 0 exactly the reference's gradient is autograd's of the line above it (loss_utils.py:40-41):
+            // clamp(x, min=0) passes 1 and |x| passes sign(0) = 0, which makes 1 - t
+            const float dbce = x == 0.f ? 1.f - t : p - t;
+            g_cls[i * NC + k] = aw * (2.f * pt * dpt * bce + pt * pt * dbce) * cls_w * inv_b * c.cls_weight;
         }
         // smooth L1 on the sin-difference-encoded residuals, anchor_head_template.py:153-160,216-220, loss_utils.py:117-136
         const float reg_w = (pos ? 1.f : 0.f) / pos_norm;

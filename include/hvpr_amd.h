@@ -495,7 +495,8 @@ int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, int dy_cstride, int dy_coff
  *     boxes3d_nearest_bev_iou (pcdet/utils/box_utils.py:252-323) and ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:
  *     13-43).  Two launches, no host round trip (the reference: two `.cpu().numpy()` arg-maxes per frame, :148,:153).
  *     anchors        [n_anchors, 7] f32 of this set, order (z, y, x, size, rotation); per_loc of them per BEV location
- *     gt_boxes       [batch, n_gt, 8] f32 [x, y, z, dx, dy, dz, heading, class]; trailing all-zero rows are padding (:53-57);
+ *     gt_boxes       [batch, n_gt, 8] f32 [x, y, z, dx, dy, dz, heading, class]; trailing rows whose signed sum over the 7 box
+ *                    fields (class excluded) is exactly 0 are padding, row 0 is always kept (:53-57, the reference's own rule);
  *                    a row takes part when class_names[class - 1] is this set's class (class_index, 0-based; python's negative
  *                    index for class 0, as the reference has it), n_gt <= 256
  *     outputs in the HEAD's anchor order: entry ((a / per_loc) * loc_stride + loc_offset + a % per_loc) of frame b, rows of

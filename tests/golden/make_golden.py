@@ -453,6 +453,186 @@ def g8_assigner_losses(R):
                         **{"param." + k: v for k, v in sd_np(m).items()})
 
 
+G18_CLASSES = {
+    # name -> (class names, per class: anchor size, bottom height, matched / unmatched threshold): hvpr.yaml's one-class head (the
+    # _head_cfg of G8) and hvpr_3class.yaml's three anchor sets, as plain values
+    "car": (["Car"], [[3.9, 1.6, 1.56]], [-1.78], [0.6], [0.45]),
+    "3c": (["Car", "Pedestrian", "Cyclist"], [[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], [-1.78, -0.6, -0.6],
+           [0.6, 0.5, 0.5], [0.45, 0.35, 0.35]),
+}
+G18_ROTATIONS = [0, 1.57]
+G18_PAD = 50                      # rows per frame of the mixed batch (the padded size hvpr.yaml's loader produces)
+
+
+def _g18_head_cfg(which):
+    names, sizes, heights, matched, unmatched = G18_CLASSES[which]
+    cfg = _head_cfg(1)
+    cfg.ANCHOR_GENERATOR_CONFIG = [dict(class_name=n, anchor_sizes=[s], anchor_rotations=list(G18_ROTATIONS), anchor_bottom_heights=[h],
+                                        align_center=False, feature_map_stride=1, matched_threshold=m, unmatched_threshold=u)
+                                   for n, s, h, m, u in zip(names, sizes, heights, matched, unmatched)]
+    return cfg
+
+
+def g18_frames(which, anchors, iou):
+    """The edge frames of G18 as {name: (G, 8) float32}.  `anchors`: the head's anchor tensors (case 10 sits on anchor centres),
+    `iou`: the reference's boxes3d_nearest_bev_iou.
+
+    Rows whose trim outcome hinges on cancellation (`cancel*`) hold small dyadic numbers only — multiples of 0.25 below 16 — so
+    that every partial sum of the 7 box fields is exact in fp32 in EVERY summation order: the reference sums on whatever device
+    it runs on, in an order that is not ours to know, and the outcome `sum == 0` must not depend on it."""
+    three = which == "3c"
+    last = 3 if three else 1                                            # the class that class 0 wraps to (class_names[-1])
+    car = [1.5, 1.0, -1.0, 4.0, 1.5, 1.5, 0.0, 1]
+    ped = [2.0, 1.0, -0.5, 0.75, 0.5, 1.75, 0.25, 2]
+    cyc = [4.5, -1.5, -0.5, 1.75, 0.5, 1.75, -0.5, 3]
+    first = ped if three else car
+    cancel = [3.0, -1.0, -1.0, 4.0, 1.5, 1.5, -8.0, 1]                   # a real car: 3 - 1 - 1 + 4 + 1.5 + 1.5 - 8 == 0
+    moved = cancel[:6] + [-7.5, 1]                                       # the same car, heading moved by 0.5: the sum is 0.5
+    zero = [0.0] * 8
+    f = {}
+    # 1. trailing real box whose signed 7-field sum is exactly 0: last row / followed by all-zero rows; the control keeps it
+    f["cancel_last"] = [first, cancel]
+    f["cancel_then_zeros"] = [first, cancel, zero, zero, zero]
+    f["cancel_control_moved"] = [first, moved]
+    f["cancel_inside"] = [first, cancel, cyc if three else car]          # not trailing: stays
+    # 2. trailing row with a zero box and a non-zero class
+    for c in ((1, 2, 3) if three else (1,)):
+        f[f"zero_box_class{c}_trailing"] = [first, car, zero[:7] + [c]]
+    # 3. all-zero row inside the valid range: class 0 wraps to the last class name
+    f["zero_row_inside"] = [car, zero, cyc if three else cancel[:6] + [1.5, 1]]
+    # 4. G = 1: cnt stops at 0, row 0 is never trimmed; one class entry -> the reference's other mask branch (:62-66)
+    f["g1_all_zero"] = [zero]
+    f[f"g1_zero_box_class{last}"] = [zero[:7] + [last]]
+    f["g1_real"] = [car]
+    # 5. only padding
+    f["only_padding"] = [zero] * 4
+    # 6. two identical ground truths: the first maximum wins.  Class 0 reads class_names[-1]: it shares the last class's anchor set
+    #    with a real ground truth of that class, and whichever comes first gives the label (0 = no positive at all)
+    box = cyc if three else car
+    f["twins_same_class"] = [box, box]
+    f["twins_real_first"] = [box, box[:7] + [0]]
+    f["twins_class0_first"] = [box[:7] + [0], box]
+    # 7. a ground truth that overlaps no anchor (no forced match, :155-156) next to one that does
+    far = [30.0, 0.5, -1.0, 3.9, 1.6, 1.56, 0.3, 1]
+    f["far_and_near"] = [far, car]
+    f["near_only"] = [car]
+    # 8. a ground truth that fits another class's anchors better than its own: the masks are per class
+    if three:
+        f["cyclist_sized_pedestrian"] = [[3.0, 0.5, -0.6, 1.76, 0.6, 1.73, 0.0, 2], [5.0, -1.0, -0.6, 0.8, 0.6, 1.73, 1.57, 3]]
+    # 9. headings on the axis-snap border (|limit_period(r, 0.5, pi)| < pi/4) as fp32 and their fp32 neighbours on both sides
+    for tag, base in (("pi4", np.pi / 4), ("mpi4", -np.pi / 4), ("3pi4", 3 * np.pi / 4)):
+        b32 = np.float32(base)
+        hs = [np.nextafter(b32, np.float32(-10)), b32, np.nextafter(b32, np.float32(10))]
+        rows = []
+        for h, y in zip(hs, (-1.6, 0.0, 1.6)):
+            if three:
+                rows.append([2.0, y, -0.6, 1.76, 0.6, 1.73, float(h), 3])
+                rows.append([5.0, y, -0.6, 0.8, 0.6, 1.73, float(h), 2])
+            else:
+                rows.append([3.2, y, -1.0, 3.9, 1.6, 1.56, float(h), 1])
+        f["snap_" + tag] = rows
+    # 10. on an anchor centre.  (a) with the anchor's own box: IoU exactly 1 with the rotation-0 anchor — the other rotation of that
+    #     location has the dimensions swapped, so with no square anchor in either head it does NOT tie.  (b) a SQUARE footprint
+    #     inside both rotations' boxes: the two rotations of the location tie for the ground truth's maximum, both are forced.
+    #     The areas of the two anchors are products of rounded extents about different centre coordinates and may differ in the last
+    #     bit, so the cell is searched for: the first interior one where the reference's own IoU of both rotations is the maximum.
+    k = 1 if three else 0
+    a = anchors[k][0, 13, 17]                                           # (sizes, rotations, 7) at grid cell y 13, x 17
+    f["on_anchor_exact"] = [a[0, 0].tolist() + [k + 1]]
+    side = 0.4 if three else 1.0
+    for cy, cx in ((y, x) for y in range(8, 24) for x in range(12, 28)):
+        a = anchors[k][0, cy, cx, 0]                                    # (rotations, 7)
+        sq = a[0].tolist() + [k + 1]
+        sq[3] = sq[4] = side
+        v = iou(anchors[k].reshape(-1, 7).clone(), torch.tensor([sq[:7]]))[:, 0].reshape(anchors[k].shape[1:5])[:, :, 0]
+        if float(v[cy, cx, 0]) == float(v[cy, cx, 1]) == float(v.max()):
+            break
+    else:
+        raise AssertionError("no cell where the two rotations tie")
+    f["on_anchor_square"] = [sq]
+    f["on_anchor_square_cell"] = (cy, cx)
+    # 11. 50 random ground truths of all classes
+    r = np.random.default_rng(1818)
+    sizes = np.array(G18_CLASSES[which][1], np.float32)
+    cls = r.integers(0, len(sizes), G18_PAD)
+    g = np.zeros((G18_PAD, 8), np.float32)
+    g[:, 0] = r.uniform(0.3, 6.1, G18_PAD)
+    g[:, 1] = r.uniform(-2.3, 2.3, G18_PAD)
+    g[:, 2] = r.uniform(-1.2, -0.6, G18_PAD)
+    g[:, 3:6] = sizes[cls] * r.uniform(0.85, 1.15, (G18_PAD, 3))
+    g[:, 6] = r.uniform(-np.pi, np.pi, G18_PAD)
+    g[:, 7] = cls + 1
+    f["random50"] = g
+    cell = f.pop("on_anchor_square_cell")
+    return {k: np.asarray(v, np.float32).reshape(-1, 8) for k, v in f.items()}, cell
+
+
+def g18_assigner_edges(R):
+    """G18: the reference's own AnchorHeadSingle.assign_targets (AxisAlignedTargetAssigner, CPU) on the 40 x 32 grid of G8 at the
+    assigner's edges (g18_frames), for the one-class head of G8 and the three-class head of hvpr_3class.yaml.  Stored, data only:
+    grid, range, the class configuration as plain values, every frame, and per frame the reference's box_cls_labels, reg_weights
+    and box_reg_targets (the rows with label > 0 and their indices: every other row is exactly zero, asserted here).  Every frame
+    padded with zero rows to 50 and stacked is one mixed batch; the reference gives for it, frame by frame, what it gives for the
+    frames alone (asserted here), so the batch needs no data of its own."""
+    nx, ny = 40, 32
+    rng = np.array([0, -2.56, -2.5, 6.4, 2.56, 0.5], dtype=np.float32)     # 0.16 m cells, as G8
+    out = dict(nx=nx, ny=ny, point_cloud_range=rng, anchor_rotations=np.array(G18_ROTATIONS, np.float64), pad_rows=G18_PAD,
+               configs=np.array(list(G18_CLASSES)))
+    for which, (names, sizes, heights, matched, unmatched) in G18_CLASSES.items():
+        torch.manual_seed(1800)
+        m = R.head_single.AnchorHeadSingle(model_cfg=_g18_head_cfg(which), input_channels=8, num_class=len(names), class_names=names,
+                                           grid_size=np.array([nx, ny, 1]), point_cloud_range=rng)
+        frames, (cy, cx) = g18_frames(which, m.anchors, R.box_utils.boxes3d_nearest_bev_iou)
+        out.update({f"{which}.class_names": np.array(names), f"{which}.anchor_sizes": np.array(sizes, np.float64),
+                    f"{which}.anchor_bottom_heights": np.array(heights, np.float64), f"{which}.matched": np.array(matched, np.float64),
+                    f"{which}.unmatched": np.array(unmatched, np.float64), f"{which}.cases": np.array(list(frames))})
+        res = {}
+        for name, gt in frames.items():
+            t = m.assign_targets(gt_boxes=torch.from_numpy(gt.copy())[None])
+            lab, tgt, w = (t[k][0].numpy() for k in ("box_cls_labels", "box_reg_targets", "reg_weights"))
+            pos = np.nonzero(lab > 0)[0]
+            assert not tgt[lab <= 0].any() and np.isfinite(tgt).all() and lab.min() >= -1 and lab.max() <= len(names)
+            res[name] = (lab, tgt, w)
+            out.update({f"{which}.{name}.gt": gt, f"{which}.{name}.labels": lab.astype(np.int8), f"{which}.{name}.reg_weights": w,
+                        f"{which}.{name}.pos_idx": pos.astype(np.int32), f"{which}.{name}.pos_targets": tgt[pos]})
+        npos = {k: int((v[0] > 0).sum()) for k, v in res.items()}
+        # the cases do what they are for
+        assert npos["cancel_last"] < npos["cancel_control_moved"], npos                      # 1: the reference trims the cancelling row
+        for k in ("labels", "pos_idx", "pos_targets"):
+            assert np.array_equal(out[f"{which}.cancel_last.{k}"], out[f"{which}.cancel_then_zeros.{k}"])
+        assert npos["cancel_inside"] > npos["cancel_last"]
+        assert npos["only_padding"] == npos["g1_all_zero"] == 0 and npos["g1_real"] > 0
+        assert npos["twins_real_first"] == npos["twins_same_class"] > 0 and npos["twins_class0_first"] == 0   # 6: first maximum
+        assert np.array_equal(res["far_and_near"][0], res["near_only"][0]) and npos["near_only"] > 0          # 7: no positive from afar
+        iou = R.box_utils.boxes3d_nearest_bev_iou
+        k = 1 if which == "3c" else 0
+        flat = m.anchors[k].reshape(-1, 7)
+        assert float(iou(flat, torch.from_numpy(frames["on_anchor_exact"][:, :7].copy())).max()) == 1.0       # 10a: IoU exactly 1
+        lab_sq = res["on_anchor_square"][0].reshape(ny, nx, -1)
+        per_loc = (lab_sq > 0).sum(-1)
+        assert per_loc[cy, cx] >= 2, per_loc[cy, cx]                                          # 10b: both rotations forced at one location
+        v = iou(flat, torch.from_numpy(frames["on_anchor_square"][:, :7].copy()))[:, 0]
+        thr = unmatched[k]
+        assert float(v.max()) < thr and int((v == v.max()).sum()) == npos["on_anchor_square"]  # ... and ONLY forced: all below unmatched
+        if which == "3c":
+            lab8 = res["cyclist_sized_pedestrian"][0].reshape(ny, nx, 3, 2)
+            assert set(np.unique(lab8[:, :, 1][lab8[:, :, 1] > 0])) == {2} and set(np.unique(lab8[:, :, 2][lab8[:, :, 2] > 0])) == {3}
+            assert not (lab8[:, :, 0] > 0).any()                                             # 8: masks per class
+        for tag in ("pi4", "mpi4", "3pi4"):
+            assert npos["snap_" + tag] > 0
+        assert npos["random50"] >= 25
+        # the mixed batch: every frame padded to 50 rows; the reference treats frames independently
+        batch = np.zeros((len(frames), G18_PAD, 8), np.float32)
+        for i, gt in enumerate(frames.values()):
+            batch[i, :len(gt)] = gt
+        t = m.assign_targets(gt_boxes=torch.from_numpy(batch))
+        for i, name in enumerate(frames):
+            for k, v in zip(("box_cls_labels", "box_reg_targets", "reg_weights"), res[name]):
+                assert np.array_equal(t[k][i].numpy(), v), (which, name, k)
+        print(f"g18 {which}: positives per case", npos)
+    np.savez_compressed(os.path.join(OUT, "g18_assigner_edges.npz"), **out)
+
+
 def g9_onecycle(R):
     import collections
     import collections.abc
@@ -1150,6 +1330,7 @@ if __name__ == "__main__":
     g15_post_processing(R)
     g16_train_branch_gradients(R)
     g17_train_loop_protocol(R)
+    g18_assigner_edges(R)
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KB")

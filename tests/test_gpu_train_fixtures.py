@@ -1,5 +1,5 @@
 """GPU: the training rows a10 / a12 / a13 / a14 on cuda:0 against the SAME reference-generated fixtures the CPU suite uses
-(G8 target assigner + losses, G9 one-cycle + 3 optimiser steps, G10 train-branch memory + get_score): the device code paths
+(G8 target assigner + losses, G18 the assigner at its edges, G9 one-cycle + 3 optimiser steps, G10 train-branch memory + get_score): the device code paths
 (target assigner on device, top-k through the read-out kernel, scatter autograd) differ from the CPU ones."""
 import pytest
 
@@ -16,6 +16,10 @@ def test_g8_target_assignment_and_losses_on_gpu(golden_dir):
 def test_g8_no_ground_truth_on_gpu(golden_dir):
     C.run_g8_no_gt(golden_dir, DEV)
     C.run_g8_batch_passes(golden_dir, DEV)
+
+
+def test_g18_assigner_edges_on_gpu(golden_dir):
+    assert C.run_g18(golden_dir, DEV) == {"car": 21, "3c": 24}
 
 
 def test_g9_onecycle_three_steps_on_gpu(golden_dir):

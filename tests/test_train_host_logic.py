@@ -1,5 +1,5 @@
 """CPU: the torch-level training logic of the product (target assigner, losses, Adam-onecycle, train branches of the
-memory / point-pillar attention) against fixtures produced by the reference's own code (tests/golden/make_golden.py G8-G10).
+memory / point-pillar attention) against fixtures produced by the reference's own code (tests/golden/make_golden.py G8-G10, G18).
 The same cases run on cuda:0 in tests/test_gpu_train_fixtures.py."""
 import train_fixture_cases as C
 
@@ -14,6 +14,12 @@ def test_g8_no_ground_truth_is_all_background(golden_dir):
 
 def test_g8_batched_assigner_passes_equal_small_batches(golden_dir):
     C.run_g8_batch_passes(golden_dir)
+
+
+def test_g18_assigner_edges_equal_the_reference(golden_dir):
+    """tests/torch_forms.assign_targets — the comparator of the GPU assigner tests — against the reference's own assigner at its
+    edges (fixture G18), the padding trim by the SIGNED sum of the 7 box fields among them."""
+    assert C.run_g18(golden_dir) == {"car": 21, "3c": 24}
 
 
 def test_g9_onecycle_schedule_and_true_weight_decay(golden_dir):

@@ -224,9 +224,9 @@ def assign_targets(self, all_anchors, gt_boxes_with_classes):
     every tensor, four frames per pass (the (frames, ground truths, anchors) IoU intermediates are ~120 MB each at 147 k anchors)."""
     gt_all = gt_boxes_with_classes
     B, G = gt_all.shape[0], gt_all.shape[1]
-    nz = gt_all.abs().sum(dim=2) != 0
+    nz = gt_all[:, :, :-1].sum(dim=2) != 0             # the reference's rule: SIGNED sum of the 7 box fields, class excluded
     ar = torch.arange(G, device=gt_all.device)
-    last = torch.where(nz, ar[None, :], torch.zeros_like(ar)[None, :]).max(dim=1)[0]      # trailing zero rows are padding (:53-57)
+    last = torch.where(nz, ar[None, :], torch.zeros_like(ar)[None, :]).max(dim=1)[0]      # trailing such rows are padding, row 0 stays (:53-57)
     valid = ar[None, :] <= last[:, None]
     gcls = gt_all[:, :, -1].int()
     per_class = []
@@ -309,7 +309,7 @@ def _code_weights(values, dtype, device):
 
 
 def rpn_losses(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, num_class, num_anchors_per_loc, cfg_weights,
-               dir_offset, num_dir_bins):
+               dir_offset, num_dir_bins, beta=1.0 / 9.0):
     """Losses of ONE prediction stream.  cls/box/dir preds are NHWC head outputs; labels (B,A) i32, reg_targets (B,A,7).
     Returns (cls_loss, box_loss (loc + dir), parts dict)."""
     B = cls_preds.shape[0]
@@ -327,7 +327,7 @@ def rpn_losses(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, nu
     bp = box_preds.reshape(B, -1, box_preds.shape[-1] // num_anchors_per_loc)
     code_w = _code_weights(cfg_weights["code_weights"], bp.dtype, bp.device)
     bp_sin, tg_sin = add_sin_difference(bp, reg_targets)
-    loc_loss = weighted_smooth_l1(bp_sin, tg_sin, reg_w, code_w).sum() / B * cfg_weights["loc_weight"]
+    loc_loss = weighted_smooth_l1(bp_sin, tg_sin, reg_w, code_w, beta).sum() / B * cfg_weights["loc_weight"]
     parts = {"cls": cls_loss, "loc": loc_loss}
     box_loss = loc_loss
     if dir_preds is not None:

@@ -1,5 +1,5 @@
-"""Shared bodies of the training-row fixture checks (G8 target assigner + losses, G9 Adam-onecycle, G10 train-branch memory +
-get_score): run on CPU by tests/test_train_host_logic.py and on cuda:0 by tests/test_gpu_train_fixtures.py.  The fixtures come
+"""Shared bodies of the training-row fixture checks (G8 target assigner + losses, G18 the assigner at its edges, G9 Adam-onecycle,
+G10 train-branch memory + get_score): run on CPU by tests/test_train_host_logic.py and on cuda:0 by tests/test_gpu_train_fixtures.py.  The fixtures come
 from the reference's own classes (tests/golden/make_golden.py)."""
 import os
 
@@ -86,6 +86,68 @@ def run_g8_batch_passes(golden_dir, dev="cpu"):
         for k in ("box_cls_labels", "box_reg_targets", "reg_weights"):
             assert torch.equal(six[k][lo:lo + 2], two[k]), (lo, k)
     np.testing.assert_array_equal(_np(six["box_cls_labels"][:2]), z["target.box_cls_labels"])
+
+
+def _g18_head(z, which, dev):
+    """The head of one of G18's two class configurations, rebuilt from the fixture's plain values."""
+    names = [str(n) for n in z[which + ".class_names"]]
+    cfg = _head_cfg()
+    cfg.ANCHOR_GENERATOR_CONFIG = [dict(class_name=n, anchor_sizes=[[float(v) for v in s]], anchor_rotations=[float(r) for r in z["anchor_rotations"]],
+                                        anchor_bottom_heights=[float(h)], align_center=False, feature_map_stride=1,
+                                        matched_threshold=float(m), unmatched_threshold=float(u))
+                                   for n, s, h, m, u in zip(names, z[which + ".anchor_sizes"], z[which + ".anchor_bottom_heights"],
+                                                            z[which + ".matched"], z[which + ".unmatched"])]
+    head = anchor_head.AnchorHeadSingle(model_cfg=cfg, input_channels=8, num_class=len(names), class_names=names,
+                                        grid_size=np.array([int(z["nx"]), int(z["ny"]), 1]), point_cloud_range=z["point_cloud_range"])
+    head.anchors = [a.to(dev) for a in head.anchors]
+    head = head.to(dev)
+    if torch.device(dev).type == "cpu":
+        torch_forms.patch(head)
+    return head
+
+
+def run_g18(golden_dir, dev="cpu"):
+    """Fixture G18 — the reference's own assigner at its edges (make_golden.g18_frames: a trailing real box whose signed field sum
+    cancels to 0, zero boxes with a class, class 0, G = 1, padding only, twins, no overlap, foreign-sized boxes, the axis-snap
+    border, forced ties on an anchor centre, 50 random boxes), one- and three-class head.  Every frame alone and all frames of a
+    configuration as ONE batch (padded with zero rows): labels and reg_weights exact, targets rtol 1e-5 / atol 1e-6 (the bars of
+    run_g8), and the batch bit for bit what the frames alone gave.  On "cpu" the torch form of tests/torch_forms.py runs, on a GPU
+    device the product's kernels.  Returns {config: number of cases}."""
+    z = _load(golden_dir, "g18_assigner_edges.npz")
+    done = {}
+    for which in (str(c) for c in z["configs"]):
+        head = _g18_head(z, which, dev)
+        cases = [str(c) for c in z[which + ".cases"]]
+        pad = int(z["pad_rows"])
+        batch = np.zeros((len(cases), pad, 8), np.float32)
+        alone, bad = [], []
+        for i, name in enumerate(cases):
+            key = f"{which}.{name}."
+            gt = z[key + "gt"]
+            batch[i, :len(gt)] = gt
+            got = head.assign_targets(torch.from_numpy(gt)[None].to(dev))
+            alone.append(got)
+            lab = z[key + "labels"].astype(np.int32)
+            tgt = np.zeros((lab.shape[0], 7), np.float32)
+            tgt[z[key + "pos_idx"]] = z[key + "pos_targets"]
+            assert got["box_cls_labels"].shape == (1, lab.shape[0])
+            n_lab = int((_np(got["box_cls_labels"][0]) != lab).sum())
+            if n_lab:
+                bad.append(f"{which}.{name}: {n_lab} labels differ, positives {int((_np(got['box_cls_labels']) > 0).sum())} "
+                           f"against the reference's {int((lab > 0).sum())}")
+                continue
+            np.testing.assert_array_equal(_np(got["reg_weights"][0]), z[key + "reg_weights"], err_msg=key)
+            np.testing.assert_allclose(_np(got["box_reg_targets"][0]), tgt, rtol=1e-5, atol=1e-6, err_msg=key)
+            assert not _np(got["box_reg_targets"][0])[lab <= 0].any(), key
+            if "positives_per_frame" in got:
+                assert int(got["positives_per_frame"][0]) == int((lab > 0).sum()), key
+        assert not bad, "\n".join(bad)
+        whole = head.assign_targets(torch.from_numpy(batch).to(dev))
+        for i, name in enumerate(cases):
+            for k in ("box_cls_labels", "box_reg_targets", "reg_weights"):
+                assert torch.equal(whole[k][i], alone[i][k][0]), (which, name, k)
+        done[which] = len(cases)
+    return done
 
 
 def run_g9(golden_dir, dev="cpu", rtol=2e-5, make_optimizer=None):
