@@ -150,7 +150,8 @@ def edges_by_destination(dst, n_dst):
     not).  A destination's run of edges is cut into chunks of _SEG_CHUNK: chunk_ptr i32 [n_chunks_max + 1] are the chunk boundaries
     inside `order`, dest_ptr i32 [n_dst + 1] the chunks of each destination — a point picked by 2000 pillars becomes 63 short sums on
     63 waves and one sum of 63 partials instead of one 2000-term loop on one wave.  Everything stays on the device: the chunk count
-    is bounded by E / _SEG_CHUNK + min(n_dst, E), the unused tail of chunk_ptr is empty chunks.  Destinations outside [0, n_dst)
+    is bounded by E / _SEG_CHUNK + min(n_dst, E) (n_chunks_max is that bound plus one spare chunk, E counting the dropped edges too),
+    the unused tail of chunk_ptr is empty chunks.  Destinations outside [0, n_dst)
     are dropped (they sort to the two ends)."""
     dst = dst.reshape(-1).to(torch.int64)
     dev = dst.device
