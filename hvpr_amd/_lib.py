@@ -6,7 +6,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 7          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
+ABI_VERSION = 8          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
 LIB_PATH = os.environ.get("HVPR_AMD_LIB", os.path.join(_HERE, "libhvpr_amd.so"))   # override: kernel experiments only
 
 _c = ctypes
@@ -49,9 +49,7 @@ SIGNATURES = {
     "hvpr_ball_query_f32": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P]),
     "hvpr_three_nn_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "hvpr_group_points_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "hvpr_group_points_grad_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "hvpr_three_interpolate_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "hvpr_three_interpolate_grad_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "hvpr_group_rows_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "hvpr_max_samples_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P, _P]),
     "hvpr_max_samples_grad_f32": (_I, [_P, _P, _c.c_longlong, _I, _I, _P, _P]),
@@ -70,7 +68,6 @@ SIGNATURES = {
     "hvpr_memory_train_fwd_f32": (_I, [_P, _c.c_longlong, _P, _I, _F, _P, _P, _P, _Z, _P]),
     "hvpr_memory_train_bwd_f32": (_I, [_P, _P, _c.c_longlong, _P, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
     "hvpr_point_pillar_topk_f32": (_I, [_P, _I, _P, _P, _I, _I, _P, _P]),
-    "hvpr_scatter_add_rows_f32": (_I, [_P, _P, _c.c_longlong, _I, _I, _P, _P]),
     "hvpr_segment_sum_rows_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P, _P, _c.c_longlong, _P, _c.c_longlong, _P]),
     "hvpr_attend_rows_fwd_f32": (_I, [_P, _I, _P, _c.c_longlong, _P, _I, _I, _P, _P, _P]),
     "hvpr_fused_adam_truewd_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F, _F, _F, _F, _I, _P, _P]),

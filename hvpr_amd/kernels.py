@@ -191,6 +191,66 @@ def segment_sum_rows(src, src_off, C, edge_row, edge_w, chunk_ptr, dest_ptr, n_d
     return dst
 
 
+class EdgePlan:
+    """The edges e -> idx[e] of a scatter into n_dst rows, owned in one place: edges_by_destination's (order, chunk_ptr, dest_ptr) —
+    one stable argsort + a handful of scans — made on first use (build() forces it), kept, and shared by every gradient that
+    scatters along the SAME index tensor; sum_rows is segment_sum_rows over it.  EdgePlan(dst, n_dst): dst is an integer tensor of
+    any shape, read flat, edge e goes to row dst[e] (rows outside [0, n_dst) are dropped)."""
+
+    def __init__(self, dst, n_dst):
+        self.idx, self.n_dst, self._per_batch = dst, int(n_dst), None
+        self._plan, self._rows, self._i32 = None, {}, None
+
+    @classmethod
+    def batched(cls, idx, n_per_batch):
+        """idx (B, ...) picks among n_per_batch rows of ITS sample: edge e of sample b goes to row b * n_per_batch + idx[e] (the
+        backward of the point stream's gathers).  Depends on idx only, so the index plan of a batch (PointNet2MSG.index_plan,
+        computed ahead on a side stream) carries it built and the backward does not have to sort."""
+        plan = cls(idx, idx.shape[0] * int(n_per_batch))
+        plan._per_batch = int(n_per_batch)
+        return plan
+
+    def build(self):
+        if self._plan is None:
+            dst = self.idx
+            if self._per_batch is not None:
+                B = dst.shape[0]
+                dst = dst.reshape(B, -1).to(torch.int64) + torch.arange(B, device=dst.device, dtype=torch.int64).view(B, 1) * self._per_batch
+            self._plan = edges_by_destination(dst, self.n_dst)
+        return self
+
+    def tensors(self):
+        """Every device tensor the plan has made so far (a consumer on another stream than the builder's records them)."""
+        made = list(self._plan or ()) + list(self._rows.values())
+        return made if self._i32 is None else made + [self._i32]
+
+    def idx32(self):
+        """idx as the contiguous i32 tensor the forward kernels read (one copy for every op that shares the plan)."""
+        if self._i32 is None:
+            self._i32 = self.idx.to(torch.int32).contiguous()
+        return self._i32
+
+    def edge_rows(self, per=1):
+        """i32, in the plan's order: the source row e // per of edge e (per = 1: one edge per source row; 3: three_interpolate's
+        neighbours of a row; k: the picks of a pillar).  Cached per `per`."""
+        if per not in self._rows:
+            order = self.build()._plan[0]
+            self._rows[per] = order if per == 1 else torch.div(order, per, rounding_mode="floor")
+        return self._rows[per]
+
+    def edge_weights(self, weights):
+        """weights holds one value per edge in edge-id order (any shape): the same values in the plan's order."""
+        return torch.index_select(weights.reshape(-1), 0, self.build()._plan[0])
+
+    def sum_rows(self, src, src_off=0, C=None, *, per=1, weights=None):
+        """(n_dst, C): row d = the sum over d's edges, in ascending edge id, of weights[e] * src[e // per, src_off : src_off + C]
+        (weights None: 1; C None: up to the row's end) — a fixed order, no float atomics: the same bits every run."""
+        _, chunk_ptr, dest_ptr = self.build()._plan
+        C = src.shape[-1] - src_off if C is None else C
+        return segment_sum_rows(src, src_off, C, self.edge_rows(per), None if weights is None else self.edge_weights(weights),
+                                chunk_ptr, dest_ptr, self.n_dst)
+
+
 def attend_rows(q, rows, idx=None, k=None):
     """hvpr_attend_rows_fwd_f32: w[m] = softmax_j <q[m], rows[r(m,j)]>, out[m] = sum_j w[m,j] rows[r(m,j)] without the gathered
     (M, k, 64) tensor.  q (M, 64), rows (N, 64) f32; idx (M, k) i32 picks rows of the table, idx=None is the dense form over

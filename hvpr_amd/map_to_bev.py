@@ -69,7 +69,7 @@ class MemoryUnit_Agg(nn.Module):
         gathered, instead of once per (pillar, k) pair: a point is picked by 4.8 pillars on average at hvpr.yaml's sizes (16 384
         points against ~3 900 pillars x 20 per frame), some by hundreds.  Same values per row (a row's result does not depend on its
         neighbours in the launch); the gradients reach the points as J^T (sum of the picks' dy) instead of sum of J^T dy —
-        round-off apart the same thing.  idx (nv, k) int64 rows of `points`; plan: the shared _EdgePlan of idx (optional)."""
+        round-off apart the same thing.  idx (nv, k) int64 rows of `points`; plan: the shared kernels.EdgePlan of idx (optional)."""
         nv, d = idx.shape[0], points.shape[1]
         self._check_train(points, d)
         mem_points = _MemoryTrain.apply(points, self.weight, float(self.shrink_thres))      # (N, d)
@@ -116,67 +116,33 @@ class _MemoryTrain(torch.autograd.Function):
 
 class _GatherRows(torch.autograd.Function):
     """rows[idx] for a (N, C) feature matrix and an integer index tensor of any shape — `points[idx]` of get_score
-    (pointpillar_scatter.py:76): hvpr_gather_rows_f32 forward; backward = hvpr_segment_sum_rows_f32 over the picks sorted by point
-    (one stable argsort of the frame's picks; torch's own index backward took 26 ms of a training step, and float atomics,
-    hvpr_scatter_add_rows_f32, are not reproducible run to run)."""
+    (pointpillar_scatter.py:76): hvpr_gather_rows_f32 forward; backward = kernels.EdgePlan.sum_rows over the picks sorted by point
+    (one stable argsort of the frame's picks; torch's own index backward took 26 ms of a training step, and float atomics are not
+    reproducible run to run).  plan: the EdgePlan of idx when the caller shares one."""
 
     @staticmethod
     def forward(ctx, rows, idx, plan=None):
         rows = rows.contiguous()
-        flat = idx.reshape(-1).to(torch.int32).contiguous()
+        ctx.plan = plan if plan is not None else kernels.EdgePlan(idx, rows.shape[0])
+        flat = ctx.plan.idx32().reshape(-1)
         out = torch.empty((flat.numel(), rows.shape[1]), dtype=torch.float32, device=rows.device)
         kernels.check(kernels.lib().hvpr_gather_rows_f32(kernels._ptr(rows, torch.float32, "rows"), rows.shape[0], rows.shape[1], flat.data_ptr(),
                                                          flat.numel(), out.data_ptr(), kernels._stream()), "hvpr_gather_rows_f32")
-        ctx.save_for_backward(flat)
-        ctx.n = rows.shape[0]
-        ctx.plan = plan
         return out.view(*idx.shape, rows.shape[1])
 
     @staticmethod
     def backward(ctx, grad):
-        (flat,) = ctx.saved_tensors
-        grad = grad.contiguous()
-        c = grad.shape[-1]
         # a point may be picked by many pillars: its gradient is summed pick by pick in ascending order (no float atomics)
-        order, chunk_ptr, dest_ptr = ctx.plan.get() if ctx.plan is not None else kernels.edges_by_destination(flat.to(torch.int64), ctx.n)
-        g = kernels.segment_sum_rows(grad.reshape(-1, c), 0, c, order, None, chunk_ptr, dest_ptr, ctx.n)
-        return g, None, None
-
-
-class _EdgePlan:
-    """The picks idx -> rows of an (n, C) tensor grouped by destination (kernels.edges_by_destination: one stable argsort + a
-    handful of scans), built on first use and shared by every gather of the SAME index tensor — the training branch attends over the
-    point features and over the per-point memory read-out with one idx."""
-
-    def __init__(self, idx, n):
-        self.idx, self.n, self._plan, self._owner, self._i32 = idx, n, None, None, None
-
-    def get(self):
-        if self._plan is None:
-            self._plan = kernels.edges_by_destination(self.idx.reshape(-1).to(torch.int64), self.n)
-        return self._plan
-
-    def idx32(self):
-        """idx as the contiguous i32 tensor the kernels read."""
-        if self._i32 is None:
-            self._i32 = self.idx.to(torch.int32).contiguous()
-        return self._i32
-
-    def owner(self):
-        """For idx (M, k): the row m = pick / k of every pick in the plan's order (i32) — the edge_row of _AttendRows' backward, built
-        once and shared like the plan itself."""
-        if self._owner is None:
-            self._owner = torch.div(self.get()[0], self.idx.shape[-1], rounding_mode="floor")
-        return self._owner
+        return ctx.plan.sum_rows(grad.contiguous().reshape(-1, grad.shape[-1])), None, None
 
 
 class _AttendRows(torch.autograd.Function):
     """out[m] = sum_j w[m,j] rows[r(m,j)] with w[m] = softmax_j <q[m], rows[r(m,j)]> DETACHED — get_score's aggregate
     (pointpillar_scatter.py:76-81) and the memory's (memory_module.py:53-57) on hvpr_attend_rows_fwd_f32: the gathered (M, k, C)
     tensor exists neither forward nor backward.  apply(q, rows, idx, plan): idx (M, k) integer picks of rows (N, C) with their
-    _EdgePlan (optional: built here when absent); idx None = the dense form over rows (M*k, C), row m*k + j being pick j of m.
-    Backward: the weights are constants, so d rows[n] = sum over the picks e = (m, j) of n, in ascending e, of w[m,j] d out[m] —
-    hvpr_segment_sum_rows_f32 over the plan (fixed order, no atomics); dense: d rows[m*k+j] = w[m,j] d out[m].  No gradient to q."""
+    kernels.EdgePlan (optional: one of idx alone when absent); idx None = the dense form over rows (M*k, C), row m*k + j being pick j
+    of m.  Backward: the weights are constants, so d rows[n] = sum over the picks e = (m, j) of n, in ascending e, of w[m,j] d out[m] —
+    EdgePlan.sum_rows with per = k (fixed order, no atomics); dense: d rows[m*k+j] = w[m,j] d out[m].  No gradient to q."""
 
     @staticmethod
     def forward(ctx, q, rows, idx, plan=None):
@@ -187,7 +153,7 @@ class _AttendRows(torch.autograd.Function):
             out, w = kernels.attend_rows(q, rows, None, rows.shape[0] // q.shape[0] if q.shape[0] else 1)
         else:
             if plan is None:
-                plan = _EdgePlan(idx, rows.shape[0])
+                plan = kernels.EdgePlan(idx, rows.shape[0])
             out, w = kernels.attend_rows(q, rows, plan.idx32())
         ctx.save_for_backward(w)
         ctx.plan, ctx.n = plan, rows.shape[0]
@@ -201,10 +167,7 @@ class _AttendRows(torch.autograd.Function):
         grad = grad.contiguous()
         if ctx.plan is None:
             return None, (w.unsqueeze(2) * grad.unsqueeze(1)).reshape(ctx.n, grad.shape[1]), None, None
-        order, chunk_ptr, dest_ptr = ctx.plan.get()
-        edge_w = torch.index_select(w.reshape(-1), 0, order)
-        g = kernels.segment_sum_rows(grad, 0, grad.shape[1], ctx.plan.owner(), edge_w, chunk_ptr, dest_ptr, ctx.n)
-        return None, g, None, None
+        return None, ctx.plan.sum_rows(grad, per=w.shape[1], weights=w), None, None
 
 
 class _ScatterCanvas(torch.autograd.Function):
@@ -369,7 +332,7 @@ class PointPillarScatter_Agg_Memory_1_scale(_ScatterBase):
                 picks = [self._topk_points(pf[v0:v1].detach(), point_f[p0:p1].detach()) + p0
                          for (v0, v1), (p0, p1) in zip(vr, pr) if v1 > v0]
             idx = torch.cat(picks, 0) if picks else torch.zeros((0, self.k), dtype=torch.long, device=pf.device)
-            plan = _EdgePlan(idx, point_f.shape[0])
+            plan = kernels.EdgePlan(idx, point_f.shape[0])
             pos_point = _AttendRows.apply(pf, point_f, idx, plan)                              # get_score, :76-83, on point_f[idx]
             # the memory's second input IS positives = point_f[idx] (T1): addressed once per point, attended by index (MemoryUnit_Agg)
             pos_mem = self.memory.forward_train_indexed(pf, self.k, point_f, idx, plan)["output"]

@@ -2,7 +2,7 @@
 
   * the ops of the absent native package pcdet/ops/pointnet2/pointnet2_batch (setup.py:94-109), all HIP kernels behind the
     C-ABI: furthest point sampling, ball query, three-NN (indices) and grouping / gather / three-interpolate with their
-    backward (autograd.Function over hvpr_group_points_f32 / hvpr_three_interpolate_f32 and their _grad twins);
+    backward (autograd.Function over hvpr_group_points_f32 / hvpr_three_interpolate_f32; backward = kernels.EdgePlan.sum_rows);
   * PointnetSAModuleMSG / PointnetFPModule with the constructor kwargs used at
     pcdet/models/backbones_3d/pointnet2_backbone.py:27-34,43-47 and OpenPCDet's parameter names (mlps.{i}.{j}, mlp.{j}); their
     shared MLPs (1x1 convolution + train-mode BatchNorm + ReLU) run on the library's matrix-core convolution and BatchNorm kernels
@@ -51,7 +51,8 @@ def three_nn(unknown, known):
 
 # ------------------------------------------------------------------------------------------------ differentiable gathers (HIP)
 class _GroupPoints(torch.autograd.Function):
-    """grouping_operation of pointnet2_batch: features (B,C,N), idx (B,np,ns) i32 -> (B,C,np,ns); backward = scatter-add."""
+    """grouping_operation of pointnet2_batch: features (B,C,N), idx (B,np,ns) i32 -> (B,C,np,ns); backward = the sum per point over its picks,
+    in a fixed order (kernels.EdgePlan over rows (B*np*ns, C); one sort per call: the product chains _GroupRows, which has a plan)."""
 
     @staticmethod
     def forward(ctx, features, idx):
@@ -68,12 +69,10 @@ class _GroupPoints(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         (idx,) = ctx.saved_tensors
-        grad = grad.contiguous()
-        B, C, np_, ns = grad.shape
-        gf = torch.empty((B, C, ctx.N), dtype=torch.float32, device=grad.device)
-        check(lib().hvpr_group_points_grad_f32(kernels._ptr(grad, torch.float32, "grad_out"), idx.data_ptr(), B, C, ctx.N, np_, ns,
-                                               gf.data_ptr(), kernels._stream()), "hvpr_group_points_grad_f32")
-        return gf, None
+        B, C = grad.shape[:2]
+        rows = grad.permute(0, 2, 3, 1).reshape(-1, C).contiguous()
+        gf = kernels.EdgePlan.batched(idx, ctx.N).sum_rows(rows)
+        return gf.view(B, ctx.N, C).transpose(1, 2).contiguous(), None
 
 
 class _ThreeInterpolate(torch.autograd.Function):
@@ -96,12 +95,10 @@ class _ThreeInterpolate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         idx, weight = ctx.saved_tensors
-        grad = grad.contiguous()
-        B, C, n = grad.shape
-        gf = torch.empty((B, C, ctx.m), dtype=torch.float32, device=grad.device)
-        check(lib().hvpr_three_interpolate_grad_f32(kernels._ptr(grad, torch.float32, "grad_out"), idx.data_ptr(), weight.data_ptr(),
-                                                    B, C, ctx.m, n, gf.data_ptr(), kernels._stream()), "hvpr_three_interpolate_grad_f32")
-        return gf, None, None
+        B, C = grad.shape[:2]
+        rows = grad.transpose(1, 2).reshape(-1, C).contiguous()
+        gf = kernels.EdgePlan.batched(idx, ctx.m).sum_rows(rows, per=3, weights=weight)
+        return gf.view(B, ctx.m, C).transpose(1, 2).contiguous(), None, None
 
 
 def _i32(idx):
@@ -114,7 +111,7 @@ def gather_operation(features, idx):
 
 
 def grouping_operation(features, idx):
-    """features (B,C,N), idx (B,np,ns) -> (B,C,np,ns); backward scatter-adds into (B,C,N)."""
+    """features (B,C,N), idx (B,np,ns) -> (B,C,np,ns); backward sums into (B,C,N)."""
     return _GroupPoints.apply(features, _i32(idx))
 
 
@@ -128,25 +125,16 @@ def _cpad(c):
     return (c + 7) // 8 * 8
 
 
-@torch.no_grad()
-def group_edges(idx, n_per_batch):
-    """(order, chunk_ptr, dest_ptr) of kernels.edges_by_destination for an index tensor idx (B, ...) into n_per_batch rows per sample: the
-    edges of the backward of a gather, grouped by the row they scatter to.  Depends on idx only, so the index plan of a batch
-    (PointNet2MSG.index_plan, computed ahead on a side stream) carries it and the backward does not have to sort."""
-    B = idx.shape[0]
-    dst = idx.reshape(B, -1).to(torch.int64) + torch.arange(B, device=idx.device, dtype=torch.int64).view(B, 1) * n_per_batch
-    return kernels.edges_by_destination(dst, B * n_per_batch)
-
-
 class _GroupRows(torch.autograd.Function):
     """QueryAndGroup (use_xyz) in ROW layout: xyz (B,N,3), features (B,N,C) or None, new_xyz (B,np,3), idx (B,np,ns) i32 ->
-    (B*np*ns, cpad) rows [xyz[idx] - new_xyz | features[idx] | 0]; backward scatter-adds the feature columns (hvpr_group_rows_*)."""
+    (B*np*ns, cpad) rows [xyz[idx] - new_xyz | features[idx] | 0] (hvpr_group_rows_f32); backward sums the feature columns per point over
+    plan = kernels.EdgePlan.batched(idx, N) (made here when the caller has none)."""
 
     @staticmethod
-    def forward(ctx, xyz, features, new_xyz, idx, cpad, csr=None):
+    def forward(ctx, xyz, features, new_xyz, idx, cpad, plan=None):
         B, N, _ = xyz.shape
         _, np_, ns = idx.shape
-        ctx.csr = csr
+        ctx.plan = plan if plan is not None else kernels.EdgePlan.batched(idx, N)
         C = 0 if features is None else features.shape[-1]
         xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
         features = None if features is None else features.contiguous()
@@ -154,22 +142,17 @@ class _GroupRows(torch.autograd.Function):
         check(lib().hvpr_group_rows_f32(kernels._ptr(xyz, torch.float32, "xyz"), kernels._ptr(features, torch.float32, "features"),
                                         kernels._ptr(new_xyz, torch.float32, "new_xyz"), kernels._ptr(idx, torch.int32, "idx"), B, N, C, np_, ns,
                                         cpad, out.data_ptr(), kernels._stream()), "hvpr_group_rows_f32")
-        ctx.save_for_backward(idx)
-        ctx.dims = (B, N, C, np_, ns, cpad)
+        ctx.dims = (B, N, C)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        (idx,) = ctx.saved_tensors
-        B, N, C, np_, ns, cpad = ctx.dims
+        B, N, C = ctx.dims
         if C == 0 or not ctx.needs_input_grad[1]:
             return None, None, None, None, None, None
-        grad = grad.contiguous()
         # a point belongs to many groups: its gradient is the sum over the (group, sample) rows that picked it, taken row by row in
-        # ascending row order (kernels.edges_by_destination): no float atomics, the same bits every run
-        order, chunk_ptr, dest_ptr = ctx.csr if ctx.csr is not None else group_edges(idx, N)
-        gf = kernels.segment_sum_rows(grad, 3, C, order, None, chunk_ptr, dest_ptr, B * N).view(B, N, C)
-        return None, gf, None, None, None, None
+        # ascending row order: no float atomics, the same bits every run
+        return None, ctx.plan.sum_rows(grad.contiguous(), 3, C).view(B, N, C), None, None, None, None
 
 
 class _MaxSamples(torch.autograd.Function):
@@ -202,11 +185,11 @@ class _MaxSamples(torch.autograd.Function):
 
 class _FpRows(torch.autograd.Function):
     """PointnetFPModule's input in ROW layout: known (B,m,C1), idx / weight (B,n,3), skip (B,n,C2) or None -> (B*n, cpad) rows
-    [three_interpolate(known) | skip | 0]  (hvpr_fp_rows_*; the weights carry no gradient, as in the reference's op)."""
+    [three_interpolate(known) | skip | 0]  (hvpr_fp_rows_f32; the weights carry no gradient, as in the reference's op); plan =
+    kernels.EdgePlan.batched(idx, m) (made here when the caller has none)."""
 
     @staticmethod
-    def forward(ctx, known, idx, weight, skip, cpad, csr=None):
-        ctx.csr = csr
+    def forward(ctx, known, idx, weight, skip, cpad, plan=None):
         known, weight = known.contiguous(), weight.contiguous()
         skip = None if skip is None else skip.contiguous()
         B, m, C1 = known.shape
@@ -216,21 +199,19 @@ class _FpRows(torch.autograd.Function):
         check(lib().hvpr_fp_rows_f32(kernels._ptr(known, torch.float32, "known"), kernels._ptr(idx, torch.int32, "idx"),
                                      kernels._ptr(weight, torch.float32, "weight"), kernels._ptr(skip, torch.float32, "skip"), B, m, n, C1, C2, cpad,
                                      out.data_ptr(), kernels._stream()), "hvpr_fp_rows_f32")
-        ctx.save_for_backward(idx, weight)
-        ctx.dims = (B, m, n, C1, C2, cpad)
+        ctx.plan = plan if plan is not None else kernels.EdgePlan.batched(idx, m)
+        ctx.save_for_backward(weight)
+        ctx.dims = (B, m, n, C1, C2)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        idx, weight = ctx.saved_tensors
-        B, m, n, C1, C2, cpad = ctx.dims
+        (weight,) = ctx.saved_tensors
+        B, m, n, C1, C2 = ctx.dims
         grad = grad.contiguous()
         # a known point feeds many unknown ones: edge (row, k) carries weight[row, k] times the row's gradient to known point idx[row, k];
         # summed per known point in ascending edge order (no float atomics)
-        order, chunk_ptr, dest_ptr = ctx.csr if ctx.csr is not None else group_edges(idx, m)
-        edge_row = torch.div(order, 3, rounding_mode="floor").to(torch.int32)
-        edge_w = weight.reshape(-1)[order.long()].contiguous()
-        gk = kernels.segment_sum_rows(grad, 0, C1, edge_row, edge_w, chunk_ptr, dest_ptr, B * m).view(B, m, C1)
+        gk = ctx.plan.sum_rows(grad, 0, C1, per=3, weights=weight).view(B, m, C1)
         gs = grad[:, C1:C1 + C2].reshape(B, n, C2).contiguous() if (C2 > 0 and ctx.needs_input_grad[3]) else None
         return gk, None, None, gs, None, None
 
@@ -309,20 +290,20 @@ class PointnetSAModuleMSG(nn.Module):
 
     def indices(self, xyz):
         """The index half of forward — it depends on the coordinates only: (FPS idx, new_xyz, [ball-query idx per scale], [the
-        edges of each scale's backward grouped by point, group_edges])."""
+        built kernels.EdgePlan of each scale's backward])."""
         idx = furthest_point_sample(xyz, self.npoint)
         new_xyz = gather_operation(xyz.transpose(1, 2).contiguous(), idx).transpose(1, 2).contiguous()
         balls = [ball_query(g.radius, g.nsample, xyz, new_xyz) for g in self.groupers]
-        return idx, new_xyz, balls, [group_edges(b, xyz.shape[1]) for b in balls]
+        return idx, new_xyz, balls, [kernels.EdgePlan.batched(b, xyz.shape[1]).build() for b in balls]
 
     def forward_rows(self, xyz, features=None, pre=None):
         """xyz (B,N,3), features (B,N,C) rows or None -> new_xyz (B,npoint,3), features (B,npoint,C') rows."""
-        idx, new_xyz, balls, csrs = pre if pre is not None else self.indices(xyz)
+        idx, new_xyz, balls, plans = pre if pre is not None else self.indices(xyz)
         B = xyz.shape[0]
         C = 0 if features is None else features.shape[-1]
         outs = []
-        for grouper, mlp, bidx, csr in zip(self.groupers, self.mlps, balls, csrs):
-            x = _GroupRows.apply(xyz, features, new_xyz, bidx, _cpad(3 + C), csr)     # (B*npoint*nsample, cpad)
+        for grouper, mlp, bidx, plan in zip(self.groupers, self.mlps, balls, plans):
+            x = _GroupRows.apply(xyz, features, new_xyz, bidx, _cpad(3 + C), plan)    # (B*npoint*nsample, cpad)
             outs.append(_MaxSamples.apply(shared_mlp_rows(mlp, x), grouper.nsample))  # (B*npoint, C')
         return new_xyz, torch.cat(outs, dim=1).view(B, self.npoint, -1)
 
@@ -334,9 +315,9 @@ class PointnetSAModuleMSG(nn.Module):
 
 
 def three_nn_plan(unknown, known):
-    """(dist, idx) of three_nn + the edges of the interpolation's backward grouped by known point."""
+    """(dist, idx) of three_nn + the built kernels.EdgePlan of the interpolation's backward (edges grouped by known point)."""
     dist, idx = three_nn(unknown, known)
-    return dist, idx, group_edges(idx, known.shape[1])
+    return dist, idx, kernels.EdgePlan.batched(idx, known.shape[1]).build()
 
 
 class PointnetFPModule(nn.Module):
@@ -348,12 +329,12 @@ class PointnetFPModule(nn.Module):
 
     def forward_rows(self, unknown, known, unknow_feats, known_feats, pre=None):
         """unknown (B,n,3), known (B,m,3), unknow_feats (B,n,C2) rows or None, known_feats (B,m,C1) rows -> (B,n,C') rows."""
-        dist, idx, csr = pre if pre is not None else three_nn_plan(unknown, known)
+        dist, idx, plan = pre if pre is not None else three_nn_plan(unknown, known)
         w = 1.0 / (dist + 1e-8)
         w = w / w.sum(dim=2, keepdim=True)
         B, n = idx.shape[0], idx.shape[1]
         c = known_feats.shape[-1] + (0 if unknow_feats is None else unknow_feats.shape[-1])
-        x = _FpRows.apply(known_feats, _i32(idx), w.detach(), unknow_feats, _cpad(c), csr)
+        x = _FpRows.apply(known_feats, _i32(idx), w.detach(), unknow_feats, _cpad(c), plan)
         return shared_mlp_rows(self.mlp, x).view(B, n, -1)
 
     def forward(self, unknown, known, unknow_feats, known_feats, pre=None):
@@ -366,6 +347,8 @@ class PointnetFPModule(nn.Module):
 def _tensors_of(obj):
     if torch.is_tensor(obj):
         yield obj
+    elif isinstance(obj, kernels.EdgePlan):
+        yield from obj.tensors()
     elif isinstance(obj, dict):
         for v in obj.values():
             yield from _tensors_of(v)
@@ -400,8 +383,8 @@ class PointNet2MSG(nn.Module):
     @torch.no_grad()
     def index_plan(self, points, batch_size):
         """Every index tensor of the forward — furthest-point samples, ball-query groups, three nearest neighbours — from the
-        point coordinates alone (none of them depends on a weight): {"sa": [(fps idx, new_xyz, [ball idx], [backward edges])],
-        "fp": {i: (dist, idx, backward edges)}}.  A training loop can compute the plan of the NEXT batch on a side stream while the current step runs
+        point coordinates alone (none of them depends on a weight): {"sa": [(fps idx, new_xyz, [ball idx], [backward EdgePlan])],
+        "fp": {i: (dist, idx, backward EdgePlan)}}.  A training loop can compute the plan of the NEXT batch on a side stream while the current step runs
         (detector.prefetch_point_indices); forward() takes it from batch_dict["_pn2_plan"]."""
         xyz = points[:, 1:4].contiguous().view(batch_size, -1, 3)
         l_xyz, sa_plan = [xyz], []

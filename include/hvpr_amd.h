@@ -35,7 +35,7 @@ enum hvpr_status {
     HVPR_ERR_TIMEOUT = -5        /* hvpr_voxelize_workspace_status: a one-launch index kernel gave up a wait (workspace needs a reset) */
 };
 
-int hvpr_abi_version(void);     /* 7 (history: csrc/abi.hip); size every workspace / packed buffer with the *_bytes / *_floats functions */
+int hvpr_abi_version(void);     /* 8 (history: csrc/abi.hip); size every workspace / packed buffer with the *_bytes / *_floats functions */
 const char *hvpr_status_string(int status);
 
 /* SyncBatchNorm across ranks (reference: tools/train.py:119-120, --sync_bn -> torch.nn.SyncBatchNorm).  The training entry points
@@ -314,24 +314,18 @@ int hvpr_three_nn_f32(const float *unknown, const float *known, int B, int n, in
 
 /* ---------------------------------------------------------------------------------------------
  * a9 (training)  Differentiable gathers of the point stream, in the reference's channel-major layout.  Replace
- *     grouping_operation / gather_operation / three_interpolate (+ their backward) of the absent
+ *     grouping_operation / gather_operation / three_interpolate of the absent
  *     pcdet/ops/pointnet2/pointnet2_batch natives (setup.py:94-109; used by PointnetSAModuleMSG / PointnetFPModule,
  *     pcdet/models/backbones_3d/pointnet2_backbone.py:27-34,43-47,82,86-89).
  *     hvpr_group_points_f32:        features [B,C,N], idx [B,npoint,nsample] i32 -> out [B,C,npoint,nsample]
  *                                   (nsample == 1: gather_operation).
- *     hvpr_group_points_grad_f32:   grad_out [B,C,npoint,nsample] -> grad_features [B,C,N], overwritten (zeroed, then
- *                                   scatter-added: fp32 atomics, summation order unspecified).
  *     hvpr_three_interpolate_f32:   features [B,C,m], idx / weight [B,n,3] -> out [B,C,n] = (f0 w0 + f1 w1) + f2 w2.
- *     hvpr_three_interpolate_grad_f32: grad_out [B,C,n] -> grad_features [B,C,m], overwritten as above.
+ *     Their backward is hvpr_segment_sum_rows_f32 over the transposed gradient (rows [B*npoint*nsample, C] / [B*n, C]).
  * ------------------------------------------------------------------------------------------- */
 int hvpr_group_points_f32(const float *features, const int32_t *idx, int B, int C, int N, int npoint, int nsample, float *out,
                           hvpr_stream_t stream);
-int hvpr_group_points_grad_f32(const float *grad_out, const int32_t *idx, int B, int C, int N, int npoint, int nsample,
-                               float *grad_features, hvpr_stream_t stream);
 int hvpr_three_interpolate_f32(const float *features, const int32_t *idx, const float *weight, int B, int C, int m, int n,
                                float *out, hvpr_stream_t stream);
-int hvpr_three_interpolate_grad_f32(const float *grad_out, const int32_t *idx, const float *weight, int B, int C, int m, int n,
-                                    float *grad_features, hvpr_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * a9 (training)  Row-layout data movement around the shared MLPs of the point stream (PointnetSAModuleMSG,
  *     pcdet/models/backbones_3d/pointnet2_backbone.py:27-34; PointnetFPModule :40-47,86-89).  The MLPs themselves (1x1 convolution
@@ -374,19 +368,16 @@ int hvpr_spatial_gate_train_bwd_f32(const float *dgate, const float *gate, const
  * channel maxima).  Exact fp32 top-k through the same pre-filter + re-check scheme as hvpr_memory_readout_fwd_f32. */
 int hvpr_point_pillar_topk_f32(const float *pillars, int M, const float *points, const float *points_packed, int N, int k,
                                int32_t *idx, hvpr_stream_t stream);
-/* a10 (training)  backward of the row gather `points[idx]` of get_score (pointpillar_scatter.py:76): dst [n_dst, row_floats] is
- * overwritten with the scatter-add of src [m, row_floats] at rows idx [m] (fp32 atomics; out-of-range ids are ignored).  The
- * forward is hvpr_gather_rows_f32. */
-int hvpr_scatter_add_rows_f32(const float *src, const int32_t *idx, long long m, int row_floats, int n_dst, float *dst,
-                              hvpr_stream_t stream);
 
-/* a9 / a10 (training)  The scattering gradients WITHOUT atomics (a point belongs to many groups — backward of QueryAndGroup,
- * pointnet2_backbone.py:27-34; a known point feeds many unknown ones — backward of three_interpolate, :40-47; backward of the row
- * gather `points[idx]`, pointpillar_scatter.py:76): dst[d][c] = sum, over the edges e = rowptr[d] .. rowptr[d+1]-1 of destination d
+/* a9 / a10 (training)  Every scattering gradient, WITHOUT atomics (a point belongs to many groups — backward of QueryAndGroup /
+ * grouping_operation, pointnet2_backbone.py:27-34; a known point feeds many unknown ones — backward of three_interpolate, :40-47;
+ * backward of the row gather `points[idx]` (forward: hvpr_gather_rows_f32) and of the attend below, pointpillar_scatter.py:76-81):
+ * dst[d][c] = sum, over the edges e = rowptr[d] .. rowptr[d+1]-1 of destination d
  * and IN THAT ORDER, of edge_w[e] * src[edge_row[e] * src_stride + src_off + c], c < C (edge_w may be null: weights 1; edge_row
  * may be null: edge e reads row e).  One
- * sequential fp32 sum per output element: two runs give the same bits.  The caller sorts the edges by destination (stable) once;
- * dst [n_dst, dst_stride] is overwritten. */
+ * sequential fp32 sum per output element: two runs give the same bits.  The caller sorts the edges by destination (stable) once
+ * (the Python layer's kernels.EdgePlan holds that plan and calls this twice: per chunk of 32 edges, then per destination over its
+ * chunks); dst [n_dst, dst_stride] is overwritten. */
 int hvpr_segment_sum_rows_f32(const float *src, long long src_stride, int src_off, int C, const int32_t *edge_row,
                               const float *edge_w, const int32_t *rowptr, long long n_dst, float *dst, long long dst_stride,
                               hvpr_stream_t stream);
@@ -395,7 +386,8 @@ int hvpr_segment_sum_rows_f32(const float *src, long long src_stride, int src_of
  * memory's training branch (memory_module.py:53-57) in one launch, without the gathered (M, k, C) tensor:
  *     w[m][j] = softmax_j( <q[m], rows[r(m,j)]> ), j < k (row maximum subtracted);   out[m] = sum_j w[m][j] * rows[r(m,j)], ascending j
  * q [M,C], rows [N,C], out [M,C], w [M,k] (what the backward needs: the weights are constants for autograd, so d rows is
- * hvpr_segment_sum_rows_f32 with src = d out, edge_row = pick / k, edge_w = w, and there is no d q).  r(m,j) = idx[m*k+j] (i32), or
+ * hvpr_segment_sum_rows_f32 with src = d out, edge_row = pick / k, edge_w = w — kernels.EdgePlan.sum_rows(d out, per=k, weights=w) —
+ * and there is no d q).  r(m,j) = idx[m*k+j] (i32), or
  * with idx == NULL the dense form r(m,j) = m*k+j over the caller's (M,k,C) tensor (then N must be M*k).  An index outside [0, N)
  * reads as a row of zeros.  One fixed order per output element: two runs, and the dense and the indexed form on equal row values,
  * give the same bits.  C == 64 and 1 <= k <= 32, else HVPR_ERR_UNSUPPORTED; M == 0 is a no-op; every argument check is made on the

@@ -20,7 +20,7 @@ def test_symbol_is_exported_and_bound(L):
     assert NAME in _lib.SIGNATURES
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NAME)
     assert L.hvpr_status_string(INVALID_ARG) == b"invalid argument" and L.hvpr_status_string(UNSUPPORTED).startswith(b"unsupported")
-    assert L.hvpr_abi_version() == 7                       # a symbol was added, no signature changed
+    assert L.hvpr_abi_version() == 8                       # 8: the float-atomic scatters are gone, no signature changed
 
 
 def test_python_wrapper_has_no_cpu_fallback():

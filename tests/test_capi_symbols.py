@@ -28,12 +28,12 @@ def test_header_symbols_exported(built):
         assert hasattr(L, n), f"{n} declared in include/hvpr_amd.h but not exported"
 
 
-def test_binding_table_matches_header_at_abi_7(built):
+def test_binding_table_matches_header_and_abi_version(built):
     from hvpr_amd import _lib
     assert sorted(_lib.SIGNATURES) == _declared()
     L = _lib.lib()
     from hvpr_amd import _lib
-    assert L.hvpr_abi_version() == _lib.ABI_VERSION == 7
+    assert L.hvpr_abi_version() == _lib.ABI_VERSION == 8
     assert L.hvpr_status_string(0) == b"ok"
     assert L.hvpr_status_string(-2).startswith(b"unsupported")
 

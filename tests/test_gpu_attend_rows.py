@@ -94,7 +94,7 @@ def _grad_op(mode, q, rows, idx, cot):
     N = rows.shape[0]
     qq, rr = q.clone().requires_grad_(True), rows.clone().requires_grad_(True)
     if mode == "plan":
-        out = map_to_bev._AttendRows.apply(qq, rr, idx, map_to_bev._EdgePlan(idx, N))
+        out = map_to_bev._AttendRows.apply(qq, rr, idx, kernels.EdgePlan(idx, N))
     elif mode == "noplan":
         out = map_to_bev._AttendRows.apply(qq, rr, idx, None)
     else:               # dense over the materialised picks: autograd carries the gradient back through the torch index

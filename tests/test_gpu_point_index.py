@@ -1,6 +1,6 @@
 """GPU: the integer-producing ops of the training point stream at their edges — csrc/pointnet2.hip (k_fps<1|4|16|32>, k_ball_query,
 k_three_nn) against oracle/hvpr_oracle.py, and hvpr_segment_sum_rows_f32 over the plans of kernels.edges_by_destination against a
-float64 sum.  A wrong index here neither crashes nor gives NaN, it trains a slightly different network, so every comparison of
+float64 sum (and kernels.EdgePlan.sum_rows, the form every backward calls, over a plan of its own).  A wrong index here neither crashes nor gives NaN, it trains a slightly different network, so every comparison of
 indices is exact.
 
 Two kinds of cloud: "metric" = synthetic.hvpr_frame coordinates; "lattice" = multiples of 0.25 (queries: of 0.125) in a small cube,
@@ -378,3 +378,55 @@ def test_segment_sum_rows_of_small_integers_is_exact(plan, rows, weights):
     got = kernels.segment_sum_rows(**args).cpu().double()
     wrong = torch.nonzero((got != ref).any(dim=1)).flatten().tolist()
     assert not wrong, f"destinations {wrong[:5]}: {got[wrong[0], :4].tolist()} != {ref[wrong[0], :4].tolist()}"
+
+
+# ==================================================================================================== kernels.EdgePlan.sum_rows
+def test_edge_plan_sum_rows_per_3_with_weights_across_the_chunk_boundary():
+    """The three-interpolate form (per = 3, one weight per edge) of EdgePlan.sum_rows with every neighbour index on known point 0 or
+    1: fan-ins above 32, so every live destination is more than one chunk.  Same bound as
+    test_segment_sum_rows_within_the_summation_bound; known points 2..4 get exactly 0; a second plan and a column slice of a wider
+    source give the same bits."""
+    B, m, n, C = 2, 5, 70, 8
+    rng = np.random.default_rng(70)
+    idx = rng.integers(0, 2, (B, n, 3)).astype(np.int32)
+    w = rng.uniform(0.1, 1.0, (B, n, 3)).astype(np.float32)
+    src = rng.standard_normal((B * n, C)).astype(np.float32)
+    dst = (idx.astype(np.int64) + np.arange(B)[:, None, None] * m).reshape(-1)
+    term = src.astype(np.float64)[np.arange(B * n * 3) // 3] * w.astype(np.float64).reshape(-1, 1)
+    ref, _, fan, bound = _seg_reference(torch.from_numpy(dst), torch.from_numpy(term), B * m)
+    live = [b * m + j for b in range(B) for j in (0, 1)]
+    assert (fan[live] >= 33).all() and fan[live].sum() == fan.sum() == B * n * 3       # four destinations of two chunks and more
+    plan = kernels.EdgePlan.batched(_dev(idx), m)
+    got_t = plan.sum_rows(_dev(src), per=3, weights=_dev(w))
+    assert got_t.shape == (B * m, C) and got_t.dtype == torch.float32
+    got = got_t.cpu().double()
+    assert (got[fan == 0] == 0.0).all(), "a known point without edges is not exactly 0"
+    err = (got - ref).abs()
+    bad = torch.nonzero(err > bound)
+    assert bad.numel() == 0, f"destination {bad[0, 0].item()} (fan-in {int(fan[bad[0, 0]])}): err {err[tuple(bad[0])].item():.3e} > bound " \
+                             f"{bound[tuple(bad[0])].item():.3e}"
+    assert torch.equal(got_t, plan.sum_rows(_dev(src), per=3, weights=_dev(w))), "two calls differ"
+    wide = np.full((B * n, 2 + C + 3), np.nan, np.float32)
+    wide[:, 2:2 + C] = src
+    again = kernels.EdgePlan.batched(_dev(idx), m).sum_rows(_dev(wide), 2, C, per=3, weights=_dev(w))
+    assert torch.equal(got_t, again), "a fresh plan over a column slice differs"
+
+
+def test_every_tensor_of_the_prefetched_index_plan_reaches_record_stream():
+    """PointNet2MSG.forward keeps the prefetched plan's memory alive on the consumer stream through pointnet2._tensors_of: the tensors
+    of every EdgePlan inside the plan must be among them (a plan object that the walk skipped would leave its order / chunk tables
+    free for reuse by the side stream while the backward still reads them)."""
+    from hvpr_amd.config import AttrDict
+    cfg = AttrDict(SA_CONFIG=dict(NPOINTS=[16, 4], RADIUS=[[0.5, 1.0], [1.0, 2.0]], NSAMPLE=[[4, 8], [4, 8]],
+                                  MLPS=[[[8, 8], [8, 8]], [[8, 16], [8, 16]]]), FP_MLPS=[[8, 8], [16, 16]])
+    net = pointnet2.PointNet2MSG(cfg, input_channels=4)
+    B, N = 2, 64
+    pts = np.concatenate([np.repeat(np.arange(B, dtype=np.float32), N)[:, None], _lattice(31, B, N).reshape(-1, 3),
+                          np.zeros((B * N, 1), np.float32)], axis=1)
+    plan = net.index_plan(_dev(pts), B)
+    plans = [p for pre in plan["sa"] for p in pre[3]] + [pre[2] for pre in plan["fp"].values()]
+    assert len(plans) == 2 * 2 + 2 and all(isinstance(p, kernels.EdgePlan) for p in plans)
+    walked = {t.data_ptr() for t in pointnet2._tensors_of(plan)}
+    for p in plans:
+        assert len(p.tensors()) == 3, "index_plan hands over BUILT plans (the sort runs on the prefetch stream)"
+        assert all(t.numel() > 0 and t.data_ptr() in walked for t in p.tensors())

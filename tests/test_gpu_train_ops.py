@@ -38,7 +38,10 @@ def test_group_points_forward_and_backward(B, Cc, N, np_, ns):
     (gf,) = torch.autograd.grad(out, f, go)
     f2 = f.detach().clone().requires_grad_(True)
     (gr,) = torch.autograd.grad(_torch_group(f2, idx), f2, go)
-    np.testing.assert_allclose(gf.cpu().numpy(), gr.cpu().numpy(), rtol=1e-5, atol=1e-5)      # atomics: order differs
+    np.testing.assert_allclose(gf.cpu().numpy(), gr.cpu().numpy(), rtol=1e-5, atol=1e-5)
+    f3 = f.detach().clone().requires_grad_(True)           # a fresh leaf, a fresh plan: the sum has a fixed order, so the same bits
+    (gf3,) = torch.autograd.grad(pointnet2.grouping_operation(f3, idx), f3, go)
+    assert gf.shape == f.shape and gf.is_contiguous() and torch.equal(gf, gf3)
     # gather_operation = one sample per group
     i1 = idx[:, :, 0].contiguous()
     assert torch.equal(pointnet2.gather_operation(f, i1), f.gather(2, i1.long().unsqueeze(1).expand(-1, Cc, -1)))
@@ -59,6 +62,9 @@ def test_three_interpolate_forward_and_backward(B, Cc, m, n):
     (gf,) = torch.autograd.grad(out, f, go)
     (gr,) = torch.autograd.grad(ref, f2, go)
     np.testing.assert_allclose(gf.cpu().numpy(), gr.cpu().numpy(), rtol=1e-4, atol=1e-5)
+    f3 = f.detach().clone().requires_grad_(True)           # a fresh leaf, a fresh plan: the sum has a fixed order, so the same bits
+    (gf3,) = torch.autograd.grad(pointnet2.three_interpolate(f3, idx, w), f3, go)
+    assert gf.shape == f.shape and gf.is_contiguous() and torch.equal(gf, gf3)
 
 
 def test_fused_adam_reproduces_fixture_g9(golden_dir):
@@ -562,7 +568,7 @@ def test_memory_addressing_once_per_point_equals_once_per_pick():
     branch runs) against _forward_train on the materialised positives points[idx] (memory_module.py:31-59 as written, one row per
     (pillar, k) pair): the SAME bits forward (a row's result does not depend on its neighbours in the launch), gradients w.r.t. the
     points, the pillars and the bank equal to round-off (J^T applied to the summed dy of a point's picks instead of summed J^T dy)."""
-    from hvpr_amd import map_to_bev
+    from hvpr_amd import kernels, map_to_bev
     g = torch.Generator().manual_seed(77)
     N, M, k = 5000, 700, 20
     mem = map_to_bev.MemoryUnit_Agg(2000, 64, 0.0025).to(DEV).train()
@@ -577,7 +583,7 @@ def test_memory_addressing_once_per_point_equals_once_per_pick():
         pts, pil = points0.clone().requires_grad_(True), pillars0.clone().requires_grad_(True)
         mem.weight.grad = None
         if indexed:
-            out = mem.forward_train_indexed(pil, k, pts, idx, map_to_bev._EdgePlan(idx, N))["output"]
+            out = mem.forward_train_indexed(pil, k, pts, idx, kernels.EdgePlan(idx, N))["output"]
         else:
             out = mem(pil, k, map_to_bev._GatherRows.apply(pts, idx))["output"]
         (out * cot).sum().backward()

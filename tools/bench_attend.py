@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hvpr_amd import map_to_bev  # noqa: E402
+from hvpr_amd import kernels, map_to_bev  # noqa: E402
 
 DEV = "cuda:0"
 K, C = 20, 64
@@ -64,8 +64,8 @@ def run(name, frames, m_per_frame, n_per_frame, reps, rounds=5):
     q = torch.relu(torch.randn(M, C, generator=g)).to(DEV)
     rows = (torch.relu(torch.randn(N, C, generator=g)) * 0.5).to(DEV).requires_grad_(True)
     cot = torch.randn(M, C, generator=g).to(DEV)
-    plan = map_to_bev._EdgePlan(idx, N)
-    plan.get(), plan.owner(), plan.idx32()
+    plan = kernels.EdgePlan(idx, N)
+    plan.build().edge_rows(K), plan.idx32()
     forms = {"torch": torch_form, "op": op_form}
 
     def fwd(f):
