@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wino_walk.h"
 
 namespace {
 
@@ -56,7 +57,8 @@ struct WinoArgs {
     int cout, cout_pad;
     int out_cstride, out_coff, resid_cstride;
     int relu;
-    int tiles_x, tiles_y, n_ct;
+    WinoWalk walk;        // tile grid and edge pairing of this shape (wino_walk.h)
+    int n_ct;
     float *stats;         // optional [pixel tiles][2][cout]: per-tile sum / sum of squares of the raw output (train-mode BatchNorm)
 };
 
@@ -77,6 +79,12 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     constexpr int BNT = 32 * NB, W_V4T = 16 * 2 * BNT;
     constexpr int NLD_P = (PATCH_V4 + NT - 1) / NT, NLD_W = W_V4T / NT;
     constexpr int PATCH_PAD = NLD_P * NT;
+    // PAIR: two ragged right-edge tiles (<= 4 live block columns each) share the 20 column slots of one patch, two ragged bottom-edge
+    // tiles (<= 2 live block rows each) share 12 patch rows (wino_walk.h) — the padding of ROWP and PPAD, so the K loop below is the
+    // same for single and paired items: only what is staged where, two per-lane constants and the epilogue's pixel differ.
+    constexpr bool PAIR = NG == 1 && NB == 2 && !STATS;
+    constexpr int PH_S = PAIR ? 12 : PH, PW_S = PAIR ? 20 : PW;          // staged rows / columns
+    constexpr int BIAS_SLOT = PH_S * ROWP;
     static_assert(W_V4T % NT == 0 && (NB == 2 || NG == 1), "whole DMA pieces");
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     float4 *const s_w = smem;                                  // [2][W_V4T]; the output transform's exchange area afterwards
@@ -90,7 +98,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
 
     // ---- tile-independent staging descriptors ----
     int p_py[NLD_P], p_px[NLD_P], p_part[NLD_P];
-    bool p_live[NLD_P];
+    bool p_live[NLD_P], p_one[NLD_P];                          // inside the staged area / inside one tile's patch
 #pragma unroll
     for (int i = 0; i < NLD_P; ++i) {
         const int v = tid + i * NT;
@@ -98,29 +106,38 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         const int y = slot / ROWP, rem = slot % ROWP;
         const int x = 2 * (rem % 10) + rem / 10;
         p_py[i] = y; p_px[i] = x; p_part[i] = plane * 4;
-        p_live[i] = plane < 2 && y < PH && x < PW;
+        p_live[i] = plane < 2 && y < PH_S && x < PW_S;
+        p_one[i] = plane < 2 && y < PH && x < PW;
     }
     // ---- per-lane LDS read offsets (float4 units) ----
     // rows of the block's 4 x 4 patch that row `wa` of Bt combines:  a=0: d0 - d2   a=1: d1 + d2   a=2: d2 - d1   a=3: d1 - d3
     const int r0 = wa == 0 ? 0 : (wa == 2 ? 2 : 1), r1 = wa == 2 ? 1 : (wa == 3 ? 3 : 2);
     const float sgn = wa == 1 ? 1.f : -1.f;
     const int pbase = half * PPAD + (2 * (4 * grp + by)) * ROWP + bx;
-    const int p_off0 = pbase + r0 * ROWP, p_off1 = pbase + r1 * ROWP;
     const int u_off = (wa * 4 * 2 + half) * BNT + l31;
     const unsigned lds_w0 = lds_addr_of(s_w) + wave_s * 1024u;
     const unsigned lds_patch0 = lds_addr_of(s_patch) + wave_s * 1024u;
 
-    const int n_pt = a.tiles_x * a.tiles_y * a.N;
+    const int n_pt = a.walk.per_image * a.N;
     const int total_walk = ((n_pt + 7) / 8) * 8 * a.n_ct;
     const int n_chunks = a.Cin / KC;
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
-    const int xcd = it & 7, j = it >> 3;
-    const int ct = j % a.n_ct;
-    int pt = (j / a.n_ct) * 8 + xcd;
+    int ct;
+    int pt = wino_walk_step(it, a.n_ct, ct);
     if (pt >= n_pt) continue;
-    const int tx = pt % a.tiles_x; pt /= a.tiles_x;
-    const int ty = pt % a.tiles_y;
-    const int n = pt / a.tiles_y;
+    int tx, ty, n, mode = WINO_SINGLE;
+    if constexpr (PAIR) {
+        const WinoItem w = wino_walk_item(a.walk, pt);
+        tx = w.tx; ty = w.ty; n = w.n; mode = w.mode;
+    } else {
+        tx = pt % a.walk.tiles_x; pt /= a.walk.tiles_x;
+        ty = pt % a.walk.tiles_y;
+        n = pt / a.walk.tiles_y;
+    }
+    // tile B of a pair: its patch sits 10 columns right of / 6 rows below A's in LDS, its pixels TH rows below / TW columns right of A's
+    const bool pr = PAIR && mode == WINO_PAIR_RIGHT, pb = PAIR && mode == WINO_PAIR_BOTTOM;
+    const bool lane_b = pr ? bx >= 4 : (pb && by >= 2);
+    const int p_off0 = pbase + r0 * ROWP + (lane_b ? (pr ? 1 : 2 * ROWP) : 0), p_off1 = p_off0 + (r1 - r0) * ROWP;
     const int oy0 = ty * TH, ox0 = tx * TW;
     const int iy0 = oy0 - 1, ix0 = ox0 - 1;
     const int co0 = ct * BNT;
@@ -129,8 +146,11 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     bool pok[NLD_P];
 #pragma unroll
     for (int i = 0; i < NLD_P; ++i) {
-        const int iy = iy0 + p_py[i], ix = ix0 + p_px[i];
-        pok[i] = p_live[i] && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+        int iy = iy0 + p_py[i], ix = ix0 + p_px[i];
+        bool ok = PAIR ? p_one[i] : p_live[i];
+        if (pr) { ok = p_live[i] && p_py[i] < PH; if (p_px[i] >= 10) { iy += TH; ix -= 10; } }
+        if (pb) { ok = p_live[i] && p_px[i] < PW; if (p_py[i] >= 6) { iy -= 6; ix += TW; } }
+        pok[i] = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
         poff[i] = pok[i] ? (unsigned)(((iy * a.W + ix) * a.Cin + p_part[i]) * (int)sizeof(float)) : 0u;
     }
     const char *in_n = (const char *)(a.in + (size_t)n * a.H * a.W * a.Cin);                 // uniform
@@ -154,7 +174,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
         for (int i = 0; i < NLD_P + NLD_W; ++i) stage_piece(chunk, buf, i);
     };
-    const bool border = iy0 < 0 || ix0 < 0 || iy0 + PH > a.H || ix0 + PW > a.W;
+    const bool border = pr || pb || iy0 < 0 || ix0 < 0 || iy0 + PH > a.H || ix0 + PW > a.W;
     if (border) {
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -162,11 +182,11 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
             for (int i = 0; i < NLD_P; ++i) s_patch[b * PATCH_PAD + tid + i * NT] = make_float4(0.f, 0.f, 0.f, 0.f);
         __syncthreads();
     }
-    // This tile's bias row (BNT floats) is parked in the patch area's unused tail (slots PH * ROWP .. of plane 0, stage 0: never a DMA
+    // This tile's bias row (BNT floats) is parked in the patch area's unused tail (slots BIAS_SLOT .. of plane 0, stage 0: never a DMA
     // destination, never a K-loop operand) by sixteen lanes now; the epilogue then takes its eight float4 from LDS instead of issuing
     // eight global loads per lane between its stores — a vector-memory instruction costs the issuing wave ≈145 cycles on this part.
-    static_assert(PH * ROWP + BNT / 4 <= PPAD, "room for the bias row behind the patch");
-    if (tid < BNT / 4) s_patch[PH * ROWP + tid] = *(const float4 *)(a.bias + co0 + tid * 4);
+    static_assert(BIAS_SLOT + BNT / 4 <= PPAD, "room for the bias row behind the patch");
+    if (tid < BNT / 4) s_patch[BIAS_SLOT + tid] = *(const float4 *)(a.bias + co0 + tid * 4);
     f32x16 acc[4][NB];
 #pragma unroll
     for (int b = 0; b < 4; ++b)
@@ -238,7 +258,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     // ---- output transform + epilogue.  A lane holds block l31 and 16 channels per accumulator block (rows (r&3) + 8*(r>>2) +
     // 4*half: four runs of four).  Exchange area (float4): [grp][a][q][channel half of the pass][run][lane]. ----
     const int p = wa >> 1, q = wa & 1;
-    const int oy = oy0 + 2 * (4 * grp + by) + p, ox = ox0 + 2 * bx + q;
+    const int oy = oy0 + 2 * (4 * grp + by) + p + (lane_b ? (pr ? TH : -4) : 0), ox = ox0 + 2 * bx + q + (lane_b ? (pr ? -8 : TW) : 0);
     const bool live_px = oy < a.H && ox < a.W;
     const size_t pix = ((size_t)n * a.H + (live_px ? oy : 0)) * a.W + (live_px ? ox : 0);
     const float gate = a.gate && live_px ? a.gate[pix] : 0.f;
@@ -276,7 +296,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
                     const float4 x0 = s_w[((((grp * 4 + p) * 2 + q) * NBP + nl) * 4 + g) * 64 + lane];
                     const float4 x1 = s_w[((((grp * 4 + p + 1) * 2 + q) * NBP + nl) * 4 + g) * 64 + lane];
                     const float4 x2 = s_w[((((grp * 4 + p + 2) * 2 + q) * NBP + nl) * 4 + g) * 64 + lane];
-                    const float4 bias = s_patch[PH * ROWP + (col - co0) / 4];
+                    const float4 bias = s_patch[BIAS_SLOT + (col - co0) / 4];
                     float4 y = f4_add(f4_fma(sg, x2, f4_fma(sg, x1, x0)), bias);       // p = 0: x0 + x1 + x2;  p = 1: x1 - x2 - x3
                     if (a.relu) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
                     if (a.gate) {
@@ -319,7 +339,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
             const float *s_part = (const float *)(s_w + 2048);
             const int c = tid & 63, k = tid >> 6;
             const float v = (s_part[(0 * 2 + k) * 64 + c] + s_part[(1 * 2 + k) * 64 + c]) + (s_part[(2 * 2 + k) * 64 + c] + s_part[(3 * 2 + k) * 64 + c]);
-            const int pt_lin = (n * a.tiles_y + ty) * a.tiles_x + tx;
+            const int pt_lin = (n * a.walk.tiles_y + ty) * a.walk.tiles_x + tx;
             if (co0 + c < a.cout) a.stats[((size_t)pt_lin * 2 + k) * a.cout + co0 + c] = v;
         }
     }
@@ -367,12 +387,11 @@ int launch(WinoArgs a, hipStream_t s) {
     constexpr int PPAD = (PH * ROWP + 63) / 64 * 64;
     constexpr int NLD_P = (2 * PPAD + NT - 1) / NT;
     constexpr int lds = (2 * (16 * 2 * 32 * NB) + 2 * NLD_P * NT) * 16;
-    a.tiles_x = (a.W + TW - 1) / TW;
-    a.tiles_y = (a.H + TH - 1) / TH;
+    a.walk = wino_walk_make(a.H, a.W, TH, NG == 1 && NB == 2 && !STATS);
     a.n_ct = a.cout_pad / (32 * NB);
     static unsigned long long lds_set = 0ull;
     if (hvpr_ensure_dyn_lds((const void *)k_wino<NG, STATS, NB>, lds, &lds_set) != 0) return -1;
-    const long long tiles = (long long)a.N * a.tiles_x * a.tiles_y * a.n_ct;
+    const long long tiles = (long long)a.N * a.walk.per_image * a.n_ct;
     static int resident = 0;
     if (resident == 0) {
         int per_cu = 0, dev = 0, cus = 256;
@@ -392,6 +411,13 @@ int launch(WinoArgs a, hipStream_t s) {
 extern "C" int hvpr_conv2d_wino_stats_rows(int N, int H, int W) {     // rows of bn_partials: the 8 x 16 pixel tiles
     if (N < 1 || H < 1 || W < 1) return 0;
     return N * ((H + 7) / 8) * ((W + TW - 1) / TW);
+}
+
+extern "C" int hvpr_conv2d_wino_items(int N, int H, int W, int cout, int px_groups) {
+    if (N < 1 || H < 1 || W < 1 || cout < 1 || (px_groups != 1 && px_groups != 2 && px_groups != 4)) return 0;
+    const WinoWalk w = wino_walk_make(H, W, px_groups == 2 ? 16 : 8, px_groups == 1);
+    const long long items = (long long)N * w.per_image * ((cout + BN - 1) / BN * BN / (px_groups == 4 ? 32 : 64));
+    return items < (1ll << 31) ? (int)items : 0;
 }
 
 extern "C" size_t hvpr_conv2d_wino_packed_floats(int cin, int cout) {

@@ -556,7 +556,13 @@ int hvpr_fused_adam_truewd_f32(float *params, const float *grads, float *exp_avg
  *     hvpr_conv2d_wino_nhwc_f32: in [N,H,W,Cin] (Cin % 8 == 0), bias [cout_pad], gate / resid / out / out_cstride / out_coff as
  *         in hvpr_conv2d_nhwc_f32 (cout % 4 == 0).  px_groups: 1 = 8 x 16 output pixels x 64 channels per workgroup (4 waves),
  *         2 = 16 x 16 pixels x 64 channels (8 waves sharing the filter stage), 4 = 8 x 16 pixels x 32 channels (4 waves; twice
- *         the tiles for launches that do not fill the chip).
+ *         the tiles for launches that do not fill the chip).  With px_groups == 1 and no bn_partials, ragged edge tiles are
+ *         paired: where the last tile column has at most 4 live 2x2-block columns, the right-edge tiles of tile rows 2r and
+ *         2r + 1 are one workgroup item, and where the last tile row has at most 2 live block rows, so are bottom-edge tiles 2c
+ *         and 2c + 1 (csrc/wino_walk.h).  The result is bit-identical to the unpaired walk.
+ *     hvpr_conv2d_wino_items: the number of workgroup items (pixel tiles or tile pairs, times channel tiles) that launch walks;
+ *         px_groups == 1 describes the launch without bn_partials (the statistics launch walks hvpr_conv2d_wino_stats_rows x
+ *         cout_pad / 64 items).  0 for invalid arguments.
  * ------------------------------------------------------------------------------------------- */
 size_t hvpr_conv2d_wino_packed_floats(int cin, int cout);
 int hvpr_conv2d_wino_pack_f32(const float *weight, const float *scale, int cout, int cin, int adjoint, float *packed,
@@ -569,6 +575,7 @@ int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, int Cin, con
  * a pass over the written tensor; hvpr_bn_finalize_partials_f32 turns them into mean / biased variance / 1/sqrt(var + eps)
  * (count = N * H * W; sums finished in double, fixed order: deterministic). */
 int hvpr_conv2d_wino_stats_rows(int N, int H, int W);
+int hvpr_conv2d_wino_items(int N, int H, int W, int cout, int px_groups);
 
 /* ---------------------------------------------------------------------------------------------
  * a5 optional precision modes: 3x3 convolutions on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulation)
