@@ -183,25 +183,53 @@ __global__ void __launch_bounds__(64) k_pairwise(const float *__restrict__ a, in
     out[t] = r;
 }
 
+// ---- NMS: the segments of one call -------------------------------------------------------------------------
+// A call holds S independent candidate lists (frames, or the classes of a frame that rank one box table).  The segment is the last
+// grid dimension of every kernel below; a kernel finds everything that belongs to its segment from the segment id: the live count,
+// the order row, the box table, and the segment's private copy of the workspace (mask | prepared boxes | per-tile pair segments |
+// pair counts | ClipIndex, each part 256-byte aligned).  S = 1 is the single-list call, launch for launch.
+constexpr int kTileCap = 64 * 64;                     // pairs a tile can hold
+constexpr int kMaxTiles = 2080;                       // nb <= 64
+struct ClipIndex { int pre[kMaxTiles + 1]; unsigned char rb[kMaxTiles], cb[kMaxTiles]; };
+
+struct NmsCall {
+    const float *boxes; int box_stride; long long table_stride; int segs_per_table;
+    const int *order, *n_device;
+    int n_segments, n_max, nb;
+    char *ws; size_t seg_bytes, off_prepared, off_plist, off_pcount, off_ci;
+
+    __device__ __forceinline__ int n(int s) const { return n_device ? min(n_device[s], n_max) : n_max; }
+    __device__ __forceinline__ const int *order_row(int s) const { return order ? order + (size_t)s * n_max : nullptr; }
+    __device__ __forceinline__ const float *table(int s) const { return boxes + (long long)(s / segs_per_table) * table_stride; }
+    __device__ __forceinline__ unsigned long long *mask(int s) const { return (unsigned long long *)(ws + (size_t)s * seg_bytes); }
+    __device__ __forceinline__ Box *prepared(int s) const { return (Box *)(ws + (size_t)s * seg_bytes + off_prepared); }
+    __device__ __forceinline__ unsigned short *plist(int s) const { return (unsigned short *)(ws + (size_t)s * seg_bytes + off_plist); }
+    __device__ __forceinline__ int *pcount(int s) const { return (int *)(ws + (size_t)s * seg_bytes + off_pcount); }
+    __device__ __forceinline__ ClipIndex *clip_index(int s) const { return (ClipIndex *)(ws + (size_t)s * seg_bytes + off_ci); }
+};
+
 // ---- NMS: bit-mask tiles -------------------------------------------------------------------------------
 // k_nms_prep: candidate i = boxes[order ? order[i] : i] -> Box (corners + sin/cos computed once per box, not once per tile)
-__global__ void __launch_bounds__(256) k_nms_prep(const float *__restrict__ boxes, int box_stride, const int *__restrict__ order,
-                                                  const int *__restrict__ n_device, int n_max, Box *__restrict__ prepared) {
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+__global__ void __launch_bounds__(256) k_nms_prep(const NmsCall nc) {
+    const int seg = blockIdx.y;
+    const int n = nc.n(seg);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const int *order = nc.order_row(seg);
     Box B;
-    make_box(boxes + (size_t)(order ? order[i] : i) * box_stride, B);
-    prepared[i] = B;
+    make_box(nc.table(seg) + (size_t)(order ? order[i] : i) * nc.box_stride, B);
+    nc.prepared(seg)[i] = B;
 }
 
 // One wave per 64 x 64 tile.  Phase 1: every lane tests its row box against the 64 column boxes with the two exact
 // rejects only (circum-circle, then separating axes: a few flops on a 32-byte box record).  Phase 2: the surviving (row, col) pairs of the whole tile are compacted into
 // LDS and dealt out to the lanes round-robin, so the expensive polygon clip runs on densely packed lanes instead of
 // 64 divergent column iterations.  Results are identical to testing every pair (the reject is exact).
-__global__ void __launch_bounds__(64) k_nms_mask(const Box *__restrict__ prepared, const int *__restrict__ n_device, int n_max,
-                                                 float thresh, unsigned long long *__restrict__ mask, int nb) {
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+__global__ void __launch_bounds__(64) k_nms_mask(const NmsCall nc, float thresh) {
+    const int seg = blockIdx.z, nb = nc.nb;
+    const int n = nc.n(seg);
+    const Box *__restrict__ prepared = nc.prepared(seg);
+    unsigned long long *__restrict__ mask = nc.mask(seg);
     const int rb = blockIdx.y, cb = blockIdx.x;
     const int t = threadIdx.x;
     const int row = rb * 64 + t;
@@ -297,13 +325,15 @@ __global__ void __launch_bounds__(64) k_nms_mask(const Box *__restrict__ prepare
 // a global list (no atomics); k_nms_clip then walks the concatenation of all segments with every lane of the chip holding the
 // same number of pairs, and sets the mask bits with atomicOr (order-independent: the mask, and with it the survivors, are
 // identical to the one-launch form).
-constexpr int kTileCap = 64 * 64;                     // pairs a tile can hold
 __host__ __device__ inline int tri_index(int rb, int cb, int nb) { return rb * nb - rb * (rb - 1) / 2 + (cb - rb); }
 
-__global__ void __launch_bounds__(64) k_nms_pairs(const Box *__restrict__ prepared, const int *__restrict__ n_device, int n_max,
-                                                  unsigned long long *__restrict__ mask, int nb, unsigned short *__restrict__ plist,
-                                                  int *__restrict__ pcount) {
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+__global__ void __launch_bounds__(64) k_nms_pairs(const NmsCall nc) {
+    const int seg = blockIdx.z, nb = nc.nb;
+    const int n = nc.n(seg);
+    const Box *__restrict__ prepared = nc.prepared(seg);
+    unsigned long long *__restrict__ mask = nc.mask(seg);
+    unsigned short *__restrict__ plist = nc.plist(seg);
+    int *__restrict__ pcount = nc.pcount(seg);
     const int rb = blockIdx.y, cb = blockIdx.x;
     const int t = threadIdx.x;
     const int row = rb * 64 + t;
@@ -368,14 +398,13 @@ __global__ void __launch_bounds__(64) k_nms_pairs(const Box *__restrict__ prepar
     if (t == 0) pcount[tile] = n_out;
 }
 
-// exclusive prefix of the live tiles' pair counts, in (rb, cb >= rb) order, + the tile of every position: one workgroup
-constexpr int kMaxTiles = 2080;                       // nb <= 64
-struct ClipIndex { int pre[kMaxTiles + 1]; unsigned char rb[kMaxTiles], cb[kMaxTiles]; };
-
-__global__ void __launch_bounds__(1024) k_nms_scan(const int *__restrict__ n_device, int n_max, int nb, const int *__restrict__ pcount,
-                                                   ClipIndex *__restrict__ ci) {
+// exclusive prefix of the live tiles' pair counts, in (rb, cb >= rb) order, + the tile of every position: one workgroup per segment
+__global__ void __launch_bounds__(1024) k_nms_scan(const NmsCall nc) {
     __shared__ int s_wave[16];
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+    const int seg = blockIdx.x, nb = nc.nb;
+    const int n = nc.n(seg);
+    const int *__restrict__ pcount = nc.pcount(seg);
+    ClipIndex *__restrict__ ci = nc.clip_index(seg);
     const int nba = (n + 63) / 64, n_tiles = nba * (nba + 1) / 2;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     // thread t owns live tiles 3t .. 3t + 2  (3 * 1024 >= 2080)
@@ -413,21 +442,65 @@ __global__ void __launch_bounds__(1024) k_nms_scan(const int *__restrict__ n_dev
 }
 
 constexpr int kClipThreads = 128, kClipBlocks = 768;  // three workgroups per CU (a PolyStore per wave, 49 KB of LDS each)
-__global__ void __launch_bounds__(kClipThreads) k_nms_clip(const Box *__restrict__ prepared, const int *__restrict__ n_device, int n_max,
-                                                           float thresh, unsigned long long *__restrict__ mask, int nb,
-                                                           const unsigned short *__restrict__ plist, const ClipIndex *__restrict__ ci) {
+// Several segments share ONE grid of about kClipBlocks workgroups (S grids of that size would each reload a 12 KB ClipIndex for a
+// sliver of work, and the chip holds 768 of these workgroups at a time anyway).  Every workgroup serves one segment, and a
+// segment gets workgroups in proportion to the pairs it has to clip: one for being non-empty plus its floor share of the
+// gridDim.x - S others, so an empty frame costs nothing and a crowded one is not left to a fixed 1/S of the chip.  All
+// workgroups derive the same split from the S totals the scan left behind (wave 0: a prefix sum over the segments); workgroups
+// the floors leave over exit.  With one segment the split is the whole grid, as before.
+__device__ __forceinline__ int clip_total(const NmsCall &nc, int s) {
+    const int nba = (nc.n(s) + 63) / 64;
+    return nc.clip_index(s)->pre[nba * (nba + 1) / 2];
+}
+
+__global__ void __launch_bounds__(kClipThreads) k_nms_clip(const NmsCall nc, float thresh) {
     __shared__ int s_pre[kMaxTiles + 1];
     __shared__ unsigned char s_rb[kMaxTiles], s_cb[kMaxTiles];
     __shared__ PolyStore ps[kClipThreads / 64];
-    const int n = n_device ? min(*n_device, n_max) : n_max;
-    const int nba = (n + 63) / 64, n_tiles = nba * (nba + 1) / 2;
+    __shared__ int s_split[3];                        // segment, its first workgroup, its workgroup count
     const int t = threadIdx.x;
+    int seg = 0, wg = blockIdx.x, n_wg = gridDim.x;
+    if (nc.n_segments > 1) {
+        if (t == 0) s_split[0] = -1;
+        if (t < 64) {
+            const int S = nc.n_segments, spare = (int)gridDim.x - S;
+            long long all = 0;
+            for (int s = t; s < S; s += 64) all += clip_total(nc, s);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) all += __shfl_xor(all, o, 64);
+            int base = 0;
+            for (int s0 = 0; s0 < S; s0 += 64) {
+                const int s = s0 + t;
+                const int tot = s < S ? clip_total(nc, s) : 0;
+                const int mine = tot > 0 ? 1 + (int)((long long)spare * tot / all) : 0;
+                int incl = mine;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int u = __shfl_up(incl, o, 64);
+                    if (t >= o) incl += u;
+                }
+                const int first = base + incl - mine;
+                if ((int)blockIdx.x >= first && (int)blockIdx.x < first + mine) { s_split[0] = s; s_split[1] = first; s_split[2] = mine; }
+                base += __shfl(incl, 63, 64);
+            }
+        }
+        __syncthreads();
+        if (s_split[0] < 0) return;
+        seg = s_split[0]; wg = (int)blockIdx.x - s_split[1]; n_wg = s_split[2];
+    }
+    const int nb = nc.nb;
+    const Box *__restrict__ prepared = nc.prepared(seg);
+    unsigned long long *__restrict__ mask = nc.mask(seg);
+    const unsigned short *__restrict__ plist = nc.plist(seg);
+    const ClipIndex *__restrict__ ci = nc.clip_index(seg);
+    const int n = nc.n(seg);
+    const int nba = (n + 63) / 64, n_tiles = nba * (nba + 1) / 2;
     for (int i = t; i <= n_tiles; i += kClipThreads) s_pre[i] = ci->pre[i];
     for (int i = t; i < n_tiles; i += kClipThreads) { s_rb[i] = ci->rb[i]; s_cb[i] = ci->cb[i]; }
     __syncthreads();
     const int total = s_pre[n_tiles];
     PolyStore &my = ps[t >> 6];
-    for (long long gidx = (long long)blockIdx.x * kClipThreads + t; gidx < total; gidx += (long long)gridDim.x * kClipThreads) {
+    for (long long gidx = (long long)wg * kClipThreads + t; gidx < total; gidx += (long long)n_wg * kClipThreads) {
         // the tile holding pair gidx: largest i with s_pre[i] <= gidx
         int lo = 0, hi = n_tiles;
         while (hi - lo > 1) {
@@ -444,11 +517,13 @@ __global__ void __launch_bounds__(kClipThreads) k_nms_clip(const Box *__restrict
 
 // ---- NMS: sequential sweep, one wave ----------------------------------------------------------------------
 // keep[] receives positions in the sorted order (or order[pos] when `order` is given and map_through_order != 0).
-__global__ void __launch_bounds__(64) k_nms_sweep(const unsigned long long *__restrict__ mask, int nb_stride,
-                                                  const int *__restrict__ n_device, int n_max,
-                                                  const int *__restrict__ order, int map_through_order, int max_keep,
-                                                  int *__restrict__ keep, int *__restrict__ keep_count) {
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+__global__ void __launch_bounds__(64) k_nms_sweep(const NmsCall nc, int map_through_order, int max_keep,
+                                                  int *__restrict__ keep_all, int *__restrict__ keep_count) {
+    const int seg = blockIdx.x, nb_stride = nc.nb;
+    const unsigned long long *__restrict__ mask = nc.mask(seg);
+    const int *__restrict__ order = nc.order_row(seg);
+    int *__restrict__ keep = keep_all + (size_t)seg * max_keep;
+    const int n = nc.n(seg);
     const int lane = threadIdx.x;
     const int nb = (n + 63) / 64;
     int kept = 0;
@@ -523,7 +598,7 @@ __global__ void __launch_bounds__(64) k_nms_sweep(const unsigned long long *__re
             }
         }
     }
-    if (lane == 0) *keep_count = kept;
+    if (lane == 0) keep_count[seg] = kept;
 }
 
 // The greedy sweep for n <= 4096 candidates (nb <= 64 mask words per row).  The sweep is serial over the 64-box blocks and
@@ -542,17 +617,19 @@ constexpr int kRingDepth = (kRingThreads / 64 - 1) / kRingOwners;     // 2 phase
 constexpr int kRingWords = 64;                       // words per row in LDS (nb <= 64)
 constexpr int kRingPieces = (64 / kRingOwners) * (kRingWords / 2) / 64;   // 16-byte pieces per lane and phase: 8
 
-__global__ void __launch_bounds__(kRingThreads) k_nms_sweep_ring(const unsigned long long *__restrict__ mask, int nb_stride,
-                                                                 const int *__restrict__ n_device, int n_max,
-                                                                 const int *__restrict__ order, int map_through_order,
-                                                                 int max_keep, int *__restrict__ keep, int *__restrict__ keep_count) {
+__global__ void __launch_bounds__(kRingThreads) k_nms_sweep_ring(const NmsCall nc, int map_through_order, int max_keep,
+                                                                 int *__restrict__ keep_all, int *__restrict__ keep_count) {
+    const int seg = blockIdx.x, nb_stride = nc.nb, n_max = nc.n_max;
+    const unsigned long long *__restrict__ mask = nc.mask(seg);
+    const int *__restrict__ order = nc.order_row(seg);
+    int *__restrict__ keep = keep_all + (size_t)seg * max_keep;
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_rows[];   // [2][64][kRingWords]
     __shared__ int s_done;
     // per ring slot: the diagonal word of every row (row r of block b, word b: a column of s_rows — 64 lanes on one bank) and the
     // candidates' ids, so that the resolve reads both without a bank conflict / without a dependent global load
     __shared__ unsigned long long s_diag[2][64];
     __shared__ int s_ord[2][64];
-    const int n = n_device ? min(*n_device, n_max) : n_max;
+    const int n = nc.n(seg);
     const int nb = (n + 63) / 64;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // a loader lane holds pieces (row 32 * half + 2u + lane / 32, words 2c, 2c + 1 with c = lane % 32), u = 0..15, of its phase
@@ -654,7 +731,7 @@ __global__ void __launch_bounds__(kRingThreads) k_nms_sweep_ring(const unsigned 
         }
         lds_barrier();
     }
-    if (tid == 0) *keep_count = kept;
+    if (tid == 0) keep_count[seg] = kept;
 }
 
 }  // namespace
@@ -681,44 +758,67 @@ extern "C" size_t hvpr_nms_workspace_bytes(int n_max) {
     return bytes;
 }
 
-extern "C" int hvpr_nms_bev_f32(const float *boxes, int box_stride, const int32_t *order, const int32_t *n_device,
-                                int n_max, float thresh, int max_keep, int map_through_order, int32_t *keep,
-                                int32_t *keep_count, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
-    if (n_max < 0 || box_stride < 7 || max_keep < 0 || !keep_count) return HVPR_ERR_INVALID_ARG;
+// segment s of a call owns workspace bytes [s * stride, s * stride + hvpr_nms_workspace_bytes(n_max))
+static size_t nms_segment_stride(int n_max) { return (hvpr_nms_workspace_bytes(n_max) + 255) / 256 * 256; }
+
+extern "C" size_t hvpr_nms_bev_batched_workspace_bytes(int n_segments, int n_max) {
+    if (n_segments < 1 || n_max < 1) return 0;
+    return (size_t)(n_segments - 1) * nms_segment_stride(n_max) + hvpr_nms_workspace_bytes(n_max);
+}
+
+extern "C" int hvpr_nms_bev_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
+                                        const int32_t *order, const int32_t *n_device, int n_segments, int n_max, float thresh,
+                                        int max_keep, int map_through_order, int32_t *keep, int32_t *keep_count, void *workspace,
+                                        size_t workspace_bytes, hvpr_stream_t stream) {
+    if (n_segments < 0 || segments_per_table < 1 || n_max < 0 || box_stride < 7 || max_keep < 0) return HVPR_ERR_INVALID_ARG;
+    if (n_segments == 0) return HVPR_OK;
+    if (!keep_count) return HVPR_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (n_max == 0) {
-        if (hipMemsetAsync(keep_count, 0, sizeof(int), s) != hipSuccess) return HVPR_ERR_LAUNCH;
+        if (hipMemsetAsync(keep_count, 0, (size_t)n_segments * sizeof(int), s) != hipSuccess) return HVPR_ERR_LAUNCH;
         return HVPR_OK;
     }
     if (!boxes || !keep || !workspace) return HVPR_ERR_INVALID_ARG;
-    if (n_max > 16384) return HVPR_ERR_UNSUPPORTED;
-    if (workspace_bytes < hvpr_nms_workspace_bytes(n_max)) return HVPR_ERR_WORKSPACE;
-    const int nb = (n_max + 63) / 64;
-    unsigned long long *mask = (unsigned long long *)workspace;
-    Box *prepared = (Box *)((char *)workspace + (((size_t)n_max * nb * sizeof(unsigned long long) + 255) / 256) * 256);
-    hipLaunchKernelGGL(k_nms_prep, dim3(hvpr_cdiv(n_max, 256)), dim3(256), 0, s, boxes, box_stride, order, n_device, n_max, prepared);
+    if (n_max > 16384 || n_segments > 65535) return HVPR_ERR_UNSUPPORTED;
+    if (workspace_bytes < hvpr_nms_bev_batched_workspace_bytes(n_segments, n_max)) return HVPR_ERR_WORKSPACE;
+    const int nb = (n_max + 63) / 64, S = n_segments;
+    const size_t nbl = nb < 64 ? nb : 64, tiles = nbl * (nbl + 1) / 2;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    NmsCall nc;
+    nc.boxes = boxes; nc.box_stride = box_stride; nc.table_stride = table_stride; nc.segs_per_table = segments_per_table;
+    nc.order = order; nc.n_device = n_device;
+    nc.n_segments = S; nc.n_max = n_max; nc.nb = nb;
+    nc.ws = (char *)workspace; nc.seg_bytes = nms_segment_stride(n_max);
+    nc.off_prepared = up((size_t)n_max * nb * sizeof(unsigned long long));
+    nc.off_plist = nc.off_prepared + up((size_t)n_max * sizeof(Box));
+    nc.off_pcount = nc.off_plist + up(tiles * kTileCap * sizeof(unsigned short));
+    nc.off_ci = nc.off_pcount + up(tiles * sizeof(int));
+    hipLaunchKernelGGL(k_nms_prep, dim3(hvpr_cdiv(n_max, 256), S), dim3(256), 0, s, nc);
     if (nb <= 64) {
-        const size_t tiles = (size_t)nb * (nb + 1) / 2;
-        char *p = (char *)prepared + (((size_t)n_max * sizeof(Box) + 255) / 256) * 256;
-        unsigned short *plist = (unsigned short *)p;
-        int *pcount = (int *)(p + ((tiles * kTileCap * sizeof(unsigned short) + 255) / 256) * 256);
-        ClipIndex *ci = (ClipIndex *)((char *)pcount + ((tiles * sizeof(int) + 255) / 256) * 256);
-        hipLaunchKernelGGL(k_nms_pairs, dim3(nb, nb), dim3(64), 0, s, prepared, n_device, n_max, mask, nb, plist, pcount);
-        hipLaunchKernelGGL(k_nms_scan, dim3(1), dim3(1024), 0, s, n_device, n_max, nb, pcount, ci);
-        hipLaunchKernelGGL(k_nms_clip, dim3(kClipBlocks), dim3(kClipThreads), 0, s, prepared, n_device, n_max, thresh, mask, nb, plist, ci);
+        hipLaunchKernelGGL(k_nms_pairs, dim3(nb, nb, S), dim3(64), 0, s, nc);
+        hipLaunchKernelGGL(k_nms_scan, dim3(S), dim3(1024), 0, s, nc);
+        // one grid for all segments; k_nms_clip needs at least one workgroup per segment beside the ones it deals out by load
+        const int clip_blocks = S == 1 || 2 * S <= kClipBlocks ? kClipBlocks : 2 * S;
+        hipLaunchKernelGGL(k_nms_clip, dim3(clip_blocks), dim3(kClipThreads), 0, s, nc, thresh);
     } else {
-        hipLaunchKernelGGL(k_nms_mask, dim3(nb, nb), dim3(64), 0, s, prepared, n_device, n_max, thresh, mask, nb);
+        hipLaunchKernelGGL(k_nms_mask, dim3(nb, nb, S), dim3(64), 0, s, nc, thresh);
     }
     if (nb <= kRingWords) {
         const size_t lds = (size_t)2 * 64 * kRingWords * sizeof(unsigned long long);
         static unsigned long long lds_set = 0ull;   // per device
-    if (hvpr_ensure_dyn_lds((const void *)k_nms_sweep_ring, (int)lds, &lds_set) != 0) return HVPR_ERR_LAUNCH;
-        hipLaunchKernelGGL(k_nms_sweep_ring, dim3(1), dim3(kRingThreads), lds, s, mask, nb, n_device, n_max, order, map_through_order,
-                           max_keep, keep, keep_count);
+        if (hvpr_ensure_dyn_lds((const void *)k_nms_sweep_ring, (int)lds, &lds_set) != 0) return HVPR_ERR_LAUNCH;
+        hipLaunchKernelGGL(k_nms_sweep_ring, dim3(S), dim3(kRingThreads), lds, s, nc, map_through_order, max_keep, keep, keep_count);
     } else {
-        hipLaunchKernelGGL(k_nms_sweep, dim3(1), dim3(64), 0, s, mask, nb, n_device, n_max, order, map_through_order, max_keep,
-                           keep, keep_count);
+        hipLaunchKernelGGL(k_nms_sweep, dim3(S), dim3(64), 0, s, nc, map_through_order, max_keep, keep, keep_count);
     }
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
+}
+
+extern "C" int hvpr_nms_bev_f32(const float *boxes, int box_stride, const int32_t *order, const int32_t *n_device,
+                                int n_max, float thresh, int max_keep, int map_through_order, int32_t *keep,
+                                int32_t *keep_count, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
+    if (!keep_count) return HVPR_ERR_INVALID_ARG;
+    return hvpr_nms_bev_batched_f32(boxes, box_stride, 0, 1, order, n_device, 1, n_max, thresh, max_keep, map_through_order, keep,
+                                    keep_count, workspace, workspace_bytes, stream);
 }

@@ -373,36 +373,52 @@ __global__ void __launch_bounds__(256) k_rank_place(const unsigned long long *__
     }
 }
 
-// The tail of post_processing (detector3d_template.py:255-259): selected boxes / scores / labels of one frame in one launch
-// (five small torch gathers otherwise).  Rows past *keep_count read keep[] as it is (the caller zero-fills it: anchor 0).
-__global__ void __launch_bounds__(256) k_gather_predictions(const float *__restrict__ boxes, int box_stride, const float *__restrict__ scores,
-                                                            const int *__restrict__ labels, const int *__restrict__ keep, int max_keep,
+// The tail of post_processing (detector3d_template.py:255-259): selected boxes / scores / labels of every segment (frame) in one
+// launch (five small torch gathers per frame otherwise).  Rows past a segment's keep_count read keep[] as it is (the caller
+// zero-fills it: anchor 0).  Segment s = blockIdx.y reads the box table s / segs_per_table and its own score and label row.
+__global__ void __launch_bounds__(256) k_gather_predictions(const float *__restrict__ boxes, int box_stride, long long table_stride,
+                                                            int segs_per_table, const float *__restrict__ scores,
+                                                            const int *__restrict__ labels, long long score_stride,
+                                                            const int *__restrict__ keep, int max_keep,
                                                             float *__restrict__ out_boxes, float *__restrict__ out_scores,
                                                             long long *__restrict__ out_labels, long long *__restrict__ out_selected) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= max_keep * 8) return;
+    const int seg = blockIdx.y;
+    const size_t o = (size_t)seg * max_keep;
     const int r = t >> 3, c = t & 7;
-    const int src = keep[r];
-    if (c < 7) out_boxes[(size_t)r * 7 + c] = boxes[(size_t)src * box_stride + c];
+    const int src = keep[o + r];
+    if (c < 7) out_boxes[(o + r) * 7 + c] = boxes[(long long)(seg / segs_per_table) * table_stride + (size_t)src * box_stride + c];
     else {
-        out_scores[r] = scores[src];
-        out_labels[r] = (long long)labels[src];
-        out_selected[r] = (long long)src;
+        out_scores[o + r] = scores[(long long)seg * score_stride + src];
+        out_labels[o + r] = (long long)labels[(long long)seg * score_stride + src];
+        out_selected[o + r] = (long long)src;
     }
 }
 
 }  // namespace
 
+extern "C" int hvpr_gather_predictions_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
+                                                   const float *scores, const int32_t *labels, long long score_stride,
+                                                   const int32_t *keep, int n_segments, int max_keep, float *out_boxes,
+                                                   float *out_scores, int64_t *out_labels, int64_t *out_selected,
+                                                   hvpr_stream_t stream) {
+    if (n_segments < 0 || segments_per_table < 1 || max_keep < 0 || box_stride < 7) return HVPR_ERR_INVALID_ARG;
+    if (n_segments == 0 || max_keep == 0) return HVPR_OK;
+    if (!boxes || !scores || !labels || !keep || !out_boxes || !out_scores || !out_labels || !out_selected) return HVPR_ERR_INVALID_ARG;
+    if (n_segments > 65535) return HVPR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_gather_predictions, dim3(hvpr_cdiv(max_keep * 8, 256), n_segments), dim3(256), 0, (hipStream_t)stream, boxes,
+                       box_stride, table_stride, segments_per_table, scores, labels, score_stride, keep, max_keep, out_boxes,
+                       out_scores, (long long *)out_labels, (long long *)out_selected);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
 extern "C" int hvpr_gather_predictions_f32(const float *boxes, int box_stride, const float *scores, const int32_t *labels,
                                            const int32_t *keep, int max_keep, float *out_boxes, float *out_scores,
                                            int64_t *out_labels, int64_t *out_selected, hvpr_stream_t stream) {
-    if (max_keep < 0 || box_stride < 7) return HVPR_ERR_INVALID_ARG;
-    if (max_keep == 0) return HVPR_OK;
-    if (!boxes || !scores || !labels || !keep || !out_boxes || !out_scores || !out_labels || !out_selected) return HVPR_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(k_gather_predictions, dim3(hvpr_cdiv(max_keep * 8, 256)), dim3(256), 0, (hipStream_t)stream, boxes, box_stride,
-                       scores, labels, keep, max_keep, out_boxes, out_scores, (long long *)out_labels, (long long *)out_selected);
-    HVPR_CHECK_LAUNCH();
-    return HVPR_OK;
+    return hvpr_gather_predictions_batched_f32(boxes, box_stride, 0, 1, scores, labels, 0, keep, 1, max_keep, out_boxes, out_scores,
+                                               out_labels, out_selected, stream);
 }
 
 extern "C" int hvpr_spatial_gate_f32(const float *y, int N, int H, int W, int C, const float *w18, float conv_bias,

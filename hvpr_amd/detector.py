@@ -36,18 +36,39 @@ def class_agnostic_nms(box_scores, box_preds, nms_config, score_thresh=None):
     return selected, box_scores[selected]
 
 
+def _nms_of_score_rows(scores, boxes, nms_config, score_thresh, ws, segments_per_table):
+    """Score filter, top NMS_PRE_MAXSIZE and rotated NMS of every row of scores (S, A) — a candidate list each, row s ranking the
+    box table boxes[s // segments_per_table] of boxes (T, A, >= 7) — in one score_topk and one batched NMS call per
+    kernels.MAX_NMS_SEGMENTS lists.  Both f32 and contiguous.  Returns keep (S, NMS_POST_MAXSIZE) i32 and the S counts as a host list
+    (ONE read)."""
+    pre = min(int(nms_config.NMS_PRE_MAXSIZE), scores.shape[1])
+    order, _, counts = kernels.score_topk(scores, score_thresh, pre, ws, want_scores=False)
+    keeps, kcs = [], []
+    for s0, s1, t0, t1, spt in kernels.nms_segment_chunks(boxes.shape[0], segments_per_table):
+        keep, kc = kernels.nms_bev_batched(boxes[t0:t1], order[s0:s1], counts[s0:s1], pre, float(nms_config.NMS_THRESH),
+                                           int(nms_config.NMS_POST_MAXSIZE), ws.nms, segments_per_table=spt)
+        keeps.append(keep)
+        kcs.append(kc)
+    one = len(keeps) == 1
+    return (keeps[0] if one else torch.cat(keeps)), (kcs[0] if one else torch.cat(kcs)).tolist()
+
+
 def multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh=None):
-    """model_nms_utils.py:28-65: per class k — score filter, top NMS_PRE_MAXSIZE, rotated NMS, first NMS_POST_MAXSIZE — on the
-    same kernels as the class-agnostic path.  cls_scores (N, num_class), box_preds (N, 7+).  Returns (scores, labels = class
-    index k as int64, boxes), classes concatenated in order."""
-    pred_scores, pred_labels, pred_boxes = [], [], []
-    for k in range(cls_scores.shape[1]):
-        col = cls_scores[:, k].contiguous()
-        selected, sc = class_agnostic_nms(col, box_preds, nms_config, score_thresh=score_thresh)
-        pred_scores.append(sc)
-        pred_labels.append(torch.full((selected.shape[0],), k, dtype=torch.long, device=col.device))
-        pred_boxes.append(box_preds[selected])
-    return torch.cat(pred_scores, dim=0), torch.cat(pred_labels, dim=0), torch.cat(pred_boxes, dim=0)
+    """model_nms_utils.py:28-65: per class k — score filter, top NMS_PRE_MAXSIZE, rotated NMS, first NMS_POST_MAXSIZE — the class
+    columns as the segments of one batched NMS call over the one box table.  cls_scores (N, num_class), box_preds (N, 7+).
+    Returns (scores, labels = class index k as int64, boxes), classes concatenated in order."""
+    n, nc = cls_scores.shape
+    dev = cls_scores.device
+    if n == 0 or nc == 0:
+        return cls_scores[:0, 0] if nc else cls_scores.reshape(0), torch.zeros((0,), dtype=torch.long, device=dev), box_preds[:0]
+    pre = min(int(nms_config.NMS_PRE_MAXSIZE), n)
+    ws = kernels.PostWorkspace(nc, n, pre, dev, segments=kernels.nms_call_segments(1, nc))
+    keep, ns = _nms_of_score_rows(cls_scores.float().t().contiguous(), box_preds.float().contiguous()[None], nms_config, score_thresh,
+                                  ws, nc)
+    sel = [keep[k, :ns[k]].long() for k in range(nc)]
+    pred_scores = [cls_scores[:, k][sel[k]] for k in range(nc)]
+    pred_labels = [torch.full((ns[k],), k, dtype=torch.long, device=dev) for k in range(nc)]
+    return torch.cat(pred_scores, dim=0), torch.cat(pred_labels, dim=0), box_preds[torch.cat(sel)]
 
 
 # ---------------------------------------------------------------------------------------------- detectors
@@ -179,44 +200,73 @@ class Detector3DTemplate(nn.Module):
             labels = (lab + 1).to(torch.int32)
         A = scores.shape[1]
         pre, post = min(int(ncfg.NMS_PRE_MAXSIZE), A), int(ncfg.NMS_POST_MAXSIZE)
-        dev = scores.device
-        if self._post_ws is None or (self._post_ws.batch, self._post_ws.n_scores, self._post_ws.pre_max) != (B, A, pre) \
-                or self._post_ws.topk.device != dev:
-            self._post_ws = kernels.PostWorkspace(B, A, pre, dev)
-        order, _, counts = kernels.score_topk(scores.contiguous(), cfg.SCORE_THRESH, pre, self._post_ws, want_scores=False)
+        ws = self._post_workspace(B, A, pre, scores.device, kernels.nms_call_segments(B))
+        order, _, counts = kernels.score_topk(scores.contiguous(), cfg.SCORE_THRESH, pre, ws, want_scores=False)
+        fast = labels.dtype == torch.int32 and not cfg.OUTPUT_RAW_SCORE and boxes_all.is_contiguous()
+        boxes_nms = boxes_all if boxes_all.is_contiguous() else boxes_all.contiguous()
+        if fast:
+            scores_c, labels_c = scores.contiguous(), labels.contiguous()
         pred_dicts, recall_dict = [], {}
-        for b in range(B):
-            keep, kc = kernels.nms_bev(boxes_all[b], order[b], counts[b:b + 1], pre, float(ncfg.NMS_THRESH), post,
-                                       self._post_ws.nms)
-            if labels.dtype == torch.int32 and not cfg.OUTPUT_RAW_SCORE and boxes_all[b].is_contiguous():
-                pb, ps, pl, sel = kernels.gather_predictions(boxes_all[b], scores[b].contiguous(), labels[b].contiguous(), keep)
-                rec = {"pred_boxes": pb, "pred_labels": pl, "pred_scores": ps, "selected": sel, "pred_count": kc}
-            else:
-                sel = keep.long()
-                rec = {"pred_boxes": boxes_all[b].index_select(0, sel), "pred_labels": labels[b].index_select(0, sel).long(),
-                       "pred_scores": (cls_all[b].max(dim=-1)[0] if cfg.OUTPUT_RAW_SCORE else scores[b]).index_select(0, sel),
-                       "selected": sel, "pred_count": kc}
-            if sync:
-                n = int(kc.item())
-                rec = {k: (v[:n] if k != "pred_count" else v) for k, v in rec.items()}
-                recall_dict = self.generate_recall_record(rec["pred_boxes"], recall_dict, b, batch_dict, cfg.RECALL_THRESH_LIST)
-            pred_dicts.append(rec)
+        # the frames are the segments of one batched NMS and one gather per kernels.MAX_NMS_SEGMENTS frames; per-frame records are
+        # views into their outputs, and sync=True reads the counts of a chunk back once
+        for s0, s1, _, _, _ in kernels.nms_segment_chunks(B):
+            keep, kc = kernels.nms_bev_batched(boxes_nms[s0:s1], order[s0:s1], counts[s0:s1], pre, float(ncfg.NMS_THRESH), post, ws.nms)
+            if fast:
+                pb, ps, pl, sel = kernels.gather_predictions_batched(boxes_nms[s0:s1], scores_c[s0:s1], labels_c[s0:s1], keep)
+            ns = kc.tolist() if sync else None
+            for b in range(s0, s1):
+                i = b - s0
+                if fast:
+                    rec = {"pred_boxes": pb[i], "pred_labels": pl[i], "pred_scores": ps[i], "selected": sel[i], "pred_count": kc[i:i + 1]}
+                else:
+                    sl = keep[i].long()
+                    rec = {"pred_boxes": boxes_all[b].index_select(0, sl), "pred_labels": labels[b].index_select(0, sl).long(),
+                           "pred_scores": (cls_all[b].max(dim=-1)[0] if cfg.OUTPUT_RAW_SCORE else scores[b]).index_select(0, sl),
+                           "selected": sl, "pred_count": kc[i:i + 1]}
+                if sync:
+                    rec = {k: (v[:ns[i]] if k != "pred_count" else v) for k, v in rec.items()}
+                    recall_dict = self.generate_recall_record(rec["pred_boxes"], recall_dict, b, batch_dict, cfg.RECALL_THRESH_LIST)
+                pred_dicts.append(rec)
         return pred_dicts, recall_dict, batch_dict
 
+    def _post_workspace(self, rows, n_scores, pre, device, segments):
+        """The detector's one PostWorkspace: `rows` score rows of `n_scores` anchors for the top-k, `segments` candidate lists per
+        batched NMS call.  Rebuilt only when a batch does not fit the one it has."""
+        ws = self._post_ws
+        if ws is None or (ws.batch, ws.n_scores, ws.pre_max) != (rows, n_scores, pre) or ws.nms_segments < segments \
+                or ws.topk.device != device:
+            self._post_ws = ws = kernels.PostWorkspace(rows, n_scores, pre, device, segments=segments)
+        return ws
+
     def _post_processing_multi_class(self, batch_dict):
-        """MULTI_CLASSES_NMS branch, detector3d_template.py:214-239 (single head): one NMS per class on the sigmoid scores.
+        """MULTI_CLASSES_NMS branch, detector3d_template.py:214-239 (single head): one NMS per class on the sigmoid scores — every
+        (frame, class) a segment of one batched call, the classes of a frame ranking that frame's box table.
         Labels are 1-based class ids (the reference's single-head label mapping `arange(1, num_class)` is one short for its own
-        assert at :224; `arange(1, num_class + 1)` is what upstream OpenPCDet has).  Host-synchronising, like the reference."""
+        assert at :224; `arange(1, num_class + 1)` is what upstream OpenPCDet has).  Host-synchronising, like the reference: one
+        read of all the counts."""
         cfg = self.model_cfg.POST_PROCESSING
+        ncfg = cfg.NMS_CONFIG
+        B = batch_dict["batch_size"]
+        cls = batch_dict["batch_cls_preds"]
+        cls = (cls if batch_dict["cls_preds_normalized"] else torch.sigmoid(cls)).float()
+        boxes_all = batch_dict["batch_box_preds"]
+        A, nc = cls.shape[1], cls.shape[2]
+        dev = cls.device
         pred_dicts, recall_dict = [], {}
-        for b in range(batch_dict["batch_size"]):
-            cls = batch_dict["batch_cls_preds"][b]
-            cls = cls if batch_dict["cls_preds_normalized"] else torch.sigmoid(cls)
-            boxes = batch_dict["batch_box_preds"][b]
-            mapping = torch.arange(1, cls.shape[1] + 1, device=cls.device)
-            sc, lab, bx = multi_classes_nms(cls.float(), boxes, cfg.NMS_CONFIG, score_thresh=cfg.SCORE_THRESH)
-            rec = {"pred_boxes": bx, "pred_scores": sc, "pred_labels": mapping[lab]}
-            recall_dict = self.generate_recall_record(bx, recall_dict, b, batch_dict, cfg.RECALL_THRESH_LIST)
+        if A > 0 and nc > 0:
+            rows = cls.permute(0, 2, 1).reshape(B * nc, A).contiguous()          # class-major: row b * nc + k
+            ws = self._post_workspace(B * nc, A, min(int(ncfg.NMS_PRE_MAXSIZE), A), dev, kernels.nms_call_segments(B, nc))
+            keep, ns = _nms_of_score_rows(rows, boxes_all.float().contiguous(), ncfg, cfg.SCORE_THRESH, ws, nc)
+        for b in range(B):
+            if A > 0 and nc > 0:
+                r = range(b * nc, (b + 1) * nc)
+                sel = [keep[s, :ns[s]].long() for s in r]
+                rec = {"pred_boxes": boxes_all[b][torch.cat(sel)], "pred_scores": torch.cat([rows[s][sl] for s, sl in zip(r, sel)]),
+                       "pred_labels": torch.cat([torch.full((ns[s],), s - b * nc + 1, dtype=torch.long, device=dev) for s in r])}
+            else:
+                rec = {"pred_boxes": boxes_all[b][:0], "pred_scores": cls[b][:0, :0].reshape(0),
+                       "pred_labels": torch.zeros((0,), dtype=torch.long, device=dev)}
+            recall_dict = self.generate_recall_record(rec["pred_boxes"], recall_dict, b, batch_dict, cfg.RECALL_THRESH_LIST)
             pred_dicts.append(rec)
         return pred_dicts, recall_dict, batch_dict
 

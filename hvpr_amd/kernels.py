@@ -702,14 +702,24 @@ def head_decode(head_nhwc, n_anchor, n_class, n_dir_bins, x_shifts, y_shifts, an
     return cls, box, scores, labels
 
 
-class PostWorkspace:
-    """Device scratch for score top-k + NMS of `batch` frames with `n_scores` anchors each."""
+# Most segments (frames, or frame x class lists) one batched NMS call takes.  A segment's workspace is about 19.5 MB at
+# pre_max = 4096 (2 MB of mask, 17 MB of per-tile pair segments, the prepared boxes), so 16 segments are 312 MB and the 48 of
+# 16 frames x 3 classes would be 0.93 GB: callers walk longer batches in chunks of this many through one workspace.
+MAX_NMS_SEGMENTS = 16
 
-    def __init__(self, batch, n_scores, pre_max, device):
+
+class PostWorkspace:
+    """Device scratch for score top-k + NMS of `batch` score rows with `n_scores` anchors each.  `segments` (default: `batch`) is the
+    number of candidate lists a batched NMS call will be given; `.nms` holds min(segments, MAX_NMS_SEGMENTS) of them
+    (`.nms_segments`): hvpr_nms_bev_batched_workspace_bytes(segments, pre_max) bytes, about 19.5 MB per segment at pre_max = 4096,
+    312 MB at the cap of 16.  It serves kernels.nms_bev (one list) as well."""
+
+    def __init__(self, batch, n_scores, pre_max, device, segments=None):
         self.batch, self.n_scores, self.pre_max = batch, n_scores, pre_max
+        self.nms_segments = max(1, min(batch if segments is None else int(segments), MAX_NMS_SEGMENTS))
         # zero-filled once: every hvpr_score_topk_f32 call leaves its counters and histogram zeroed again
         self.topk = torch.zeros(lib().hvpr_score_topk_workspace_bytes(batch, n_scores), dtype=torch.uint8, device=device)
-        self.nms = torch.empty(lib().hvpr_nms_workspace_bytes(pre_max), dtype=torch.uint8, device=device)
+        self.nms = torch.empty(lib().hvpr_nms_bev_batched_workspace_bytes(self.nms_segments, pre_max), dtype=torch.uint8, device=device)
 
 
 def score_topk(scores, score_thresh, pre_max, ws, want_scores=True):
@@ -752,6 +762,71 @@ def gather_predictions(boxes, scores, labels, keep):
     check(lib().hvpr_gather_predictions_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[1], _ptr(scores, torch.float32, "scores"),
                                             _ptr(labels, torch.int32, "labels"), _ptr(keep, torch.int32, "keep"), K, ob.data_ptr(),
                                             os_.data_ptr(), ol.data_ptr(), osel.data_ptr(), _stream()), "hvpr_gather_predictions_f32")
+    return ob, os_, ol, osel
+
+
+def nms_segment_chunks(n_tables, segments_per_table=1):
+    """The calls that walk n_tables * segments_per_table candidate lists with at most MAX_NMS_SEGMENTS per call: yields (first
+    list, end list, first table, end table, segments_per_table of the call).  Whole tables per call; a table with more lists than
+    the cap is walked on its own, a run of its lists at a time."""
+    cap, spt = max(int(MAX_NMS_SEGMENTS), 1), int(segments_per_table)
+    if spt <= cap:
+        step = cap // spt
+        for t0 in range(0, n_tables, step):
+            t1 = min(n_tables, t0 + step)
+            yield t0 * spt, t1 * spt, t0, t1, spt
+    else:
+        for t in range(n_tables):
+            for k0 in range(0, spt, cap):
+                k1 = min(spt, k0 + cap)
+                yield t * spt + k0, t * spt + k1, t, t + 1, k1 - k0
+
+
+def nms_call_segments(n_tables, segments_per_table=1):
+    """Lists in the largest call of nms_segment_chunks: what a PostWorkspace for them is sized for (`segments=`)."""
+    return max((s1 - s0 for s0, s1, _, _, _ in nms_segment_chunks(n_tables, segments_per_table)), default=1)
+
+
+def nms_bev_batched(boxes, order, n_device, n_max, thresh, max_keep, ws_nms, map_through_order=True, segments_per_table=1):
+    """Rotated NMS of S candidate lists in one call (hvpr_nms_bev_batched_f32): boxes (T, R, >=7) f32, T box tables; order
+    (S, n_max) i32 or None; n_device (S,) i32 or None (every list holds n_max); list s ranks table s // segments_per_table, so
+    S = T * segments_per_table.  Returns keep (S, max_keep) i32, zero-initialised like the single form's, and keep_count (S,) i32:
+    per list what nms_bev gives for it alone.  ws_nms holds hvpr_nms_bev_batched_workspace_bytes(S, n_max) bytes (about 19.5 MB
+    per list at n_max = 4096; PostWorkspace(...).nms); callers keep S <= MAX_NMS_SEGMENTS and walk longer batches in chunks."""
+    if boxes.dim() != 3:
+        raise ValueError("nms_bev_batched: boxes must be (tables, rows, >= 7)")
+    S = boxes.shape[0] * int(segments_per_table)
+    if order is not None and tuple(order.shape) != (S, n_max):
+        raise ValueError(f"nms_bev_batched: order must be ({S}, {n_max}), got {tuple(order.shape)}")
+    if n_device is not None and tuple(n_device.shape) != (S,):
+        raise ValueError(f"nms_bev_batched: n_device must be ({S},), got {tuple(n_device.shape)}")
+    dev = boxes.device
+    keep = torch.zeros((S, max(max_keep, 1)), dtype=torch.int32, device=dev)   # rows past keep_count stay valid ids
+    kc = torch.empty((S,), dtype=torch.int32, device=dev)
+    check(lib().hvpr_nms_bev_batched_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
+                                         int(segments_per_table), _ptr(order, torch.int32), _ptr(n_device, torch.int32), S, int(n_max),
+                                         float(thresh), int(max_keep), 1 if map_through_order else 0, keep.data_ptr(), kc.data_ptr(),
+                                         ws_nms.data_ptr(), ws_nms.numel(), _stream()), "hvpr_nms_bev_batched_f32")
+    return keep, kc
+
+
+def gather_predictions_batched(boxes, scores, labels, keep, segments_per_table=1):
+    """boxes (T, A, >=7), scores (S, A), labels (S, A) i32, keep (S, K) i32 -> pred_boxes (S, K, 7), pred_scores (S, K), pred_labels
+    (S, K) i64, selected (S, K) i64 in one launch; list s reads table s // segments_per_table."""
+    S, K = keep.shape
+    if boxes.dim() != 3 or boxes.shape[0] * int(segments_per_table) != S or tuple(scores.shape) != (S, boxes.shape[1]) \
+            or labels.shape != scores.shape:
+        raise ValueError("gather_predictions_batched: shapes do not match")
+    dev = boxes.device
+    ob = torch.empty((S, K, 7), dtype=torch.float32, device=dev)
+    os_ = torch.empty((S, K), dtype=torch.float32, device=dev)
+    ol = torch.empty((S, K), dtype=torch.int64, device=dev)
+    osel = torch.empty((S, K), dtype=torch.int64, device=dev)
+    check(lib().hvpr_gather_predictions_batched_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
+                                                    int(segments_per_table), _ptr(scores, torch.float32, "scores"),
+                                                    _ptr(labels, torch.int32, "labels"), scores.shape[1], _ptr(keep, torch.int32, "keep"),
+                                                    S, K, ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), osel.data_ptr(), _stream()),
+          "hvpr_gather_predictions_batched_f32")
     return ob, os_, ol, osel
 
 

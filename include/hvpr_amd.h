@@ -298,6 +298,30 @@ int hvpr_boxes_pairwise_f32(const float *boxes_a, int n, const float *boxes_b, i
                             hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * a8  Batched rotated NMS: S independent candidate lists (the frames of a batch, or every (frame, class) of the
+ *     MULTI_CLASSES_NMS branch) in ONE call, five launches whatever S is.  The single forms above are this with one segment.
+ *     Segment s reads the box table at boxes + (s / segments_per_table) * table_stride floats; its candidate i is row
+ *     order ? order[s * n_max + i] : i of that table; n_device[s] candidates are live (clamped to n_max; NULL: all n_max).
+ *     segments_per_table = 1: one table per segment (a batch of frames); = num_class: the classes of a frame rank one table.
+ *     keep [S, max_keep], keep_count [S]: per segment exactly what hvpr_nms_bev_f32 gives for that segment alone.
+ *     n_segments == 0: nothing is done; n_max == 0: the S counts are zeroed.  n_max <= 16384, n_segments <= 65535.
+ *     Workspace: S private copies of the single form's layout, 256-byte aligned each (about 19.5 MB per segment at
+ *     n_max = 4096); hvpr_nms_bev_batched_workspace_bytes(1, n) == hvpr_nms_workspace_bytes(n), and a workspace sized for
+ *     (S, n) serves every call with at most S segments and n_max <= n.
+ *     hvpr_gather_predictions_batched_f32: out_*[s, r] = *[keep[s, r]] for r < max_keep; boxes are addressed like the NMS's
+ *     (table_stride, segments_per_table); scores and labels are one row per segment, score_stride elements apart.
+ * ------------------------------------------------------------------------------------------- */
+size_t hvpr_nms_bev_batched_workspace_bytes(int n_segments, int n_max);
+int hvpr_nms_bev_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
+                             const int32_t *order, const int32_t *n_device, int n_segments, int n_max, float thresh,
+                             int max_keep, int map_through_order, int32_t *keep, int32_t *keep_count, void *workspace,
+                             size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_gather_predictions_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
+                                        const float *scores, const int32_t *labels, long long score_stride,
+                                        const int32_t *keep, int n_segments, int max_keep, float *out_boxes,
+                                        float *out_scores, int64_t *out_labels, int64_t *out_selected, hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a9 (training)  PointNet++ index ops.  Replace the absent natives of pcdet/ops/pointnet2/pointnet2_batch (setup.py:94-109)
  *     behind PointnetSAModuleMSG / PointnetFPModule (pcdet/models/backbones_3d/pointnet2_backbone.py:27-34,43-47,82,86-89).
  *     Indices only (no gradient); tie rule: lowest index.  Distances are fp32 (dx*dx + dy*dy) + dz*dz.
