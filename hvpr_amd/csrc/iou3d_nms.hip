@@ -183,6 +183,30 @@ __global__ void __launch_bounds__(64) k_pairwise(const float *__restrict__ a, in
     out[t] = r;
 }
 
+// Ragged form of mode 0: F independent (n_f, m_f) problems packed end to end in ONE launch.  Pair p of frame f (pair_off[f] <= p <
+// pair_off[f + 1], frames without pairs own nothing) is (i, j) = divmod(p - pair_off[f], m_f): row a_off[f] + i of table A against
+// row b_off[f] + j of table B.  A pair is one lane running the same make_box / box_overlap sequence on the same two rows as in
+// k_pairwise, so out[pair_off[f] ...] holds exactly the bits hvpr_boxes_pairwise_f32 gives for frame f alone.
+__global__ void __launch_bounds__(64) k_pairwise_ragged(const float *__restrict__ a, const float *__restrict__ b,
+                                                        const int64_t *__restrict__ a_off, const int64_t *__restrict__ b_off,
+                                                        const int64_t *__restrict__ pair_off, int n_frames, long long n_pairs,
+                                                        float *__restrict__ out) {
+    __shared__ PolyStore ps;
+    const int ln = threadIdx.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_pairs) return;
+    int lo = 0, hi = n_frames;                           // the largest f with pair_off[f] <= t
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pair_off[mid] <= t) lo = mid; else hi = mid;
+    }
+    const long long m = b_off[lo + 1] - b_off[lo], r = t - pair_off[lo];
+    Box A, B;
+    make_box(a + (size_t)(a_off[lo] + r / m) * 7, A);
+    make_box(b + (size_t)(b_off[lo] + r % m) * 7, B);
+    out[t] = box_overlap(A, B, ps, ln);
+}
+
 // ---- NMS: the segments of one call -------------------------------------------------------------------------
 // A call holds S independent candidate lists (frames, or the classes of a frame that rank one box table).  The segment is the last
 // grid dimension of every kernel below; a kernel finds everything that belongs to its segment from the segment id: the live count,
@@ -743,6 +767,18 @@ extern "C" int hvpr_boxes_pairwise_f32(const float *boxes_a, int n, const float 
     if (!boxes_a || !boxes_b || !out) return HVPR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_pairwise, dim3(hvpr_cdiv((long long)n * m, 64)), dim3(64), 0, (hipStream_t)stream, boxes_a, n,
                        boxes_b, m, mode, out);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_boxes_pairwise_ragged_f32(const float *boxes_a, const float *boxes_b, const int64_t *a_off, const int64_t *b_off,
+                                              const int64_t *pair_off, int n_frames, long long n_pairs, float *out,
+                                              hvpr_stream_t stream) {
+    if (n_frames < 0 || n_pairs < 0 || n_pairs > (1ll << 36)) return HVPR_ERR_INVALID_ARG;
+    if (n_frames == 0 || n_pairs == 0) return HVPR_OK;
+    if (!boxes_a || !boxes_b || !a_off || !b_off || !pair_off || !out) return HVPR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_pairwise_ragged, dim3(hvpr_cdiv(n_pairs, 64)), dim3(64), 0, (hipStream_t)stream, boxes_a, boxes_b, a_off,
+                       b_off, pair_off, n_frames, n_pairs, out);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }

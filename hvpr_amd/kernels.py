@@ -838,3 +838,59 @@ def boxes_pairwise(a, b, mode):
     check(lib().hvpr_boxes_pairwise_f32(_ptr(a, torch.float32, "boxes_a"), a.shape[0], _ptr(b, torch.float32, "boxes_b"),
                                         b.shape[0], int(mode), out.data_ptr(), _stream()), "hvpr_boxes_pairwise_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ KITTI AP (f3)
+def boxes_pairwise_ragged(a, b, a_off, b_off, pair_off, n_pairs):
+    """BEV overlap areas (mode 0) of F independent frames in one launch.  a (NA,7), b (NB,7) f32; a_off, b_off, pair_off (F+1,)
+    int64 cuda -> (n_pairs,) f32, frame f at pair_off[f] as its (n_f, m_f) matrix, bit-equal to boxes_pairwise on that frame."""
+    out = torch.empty((int(n_pairs),), dtype=torch.float32, device=pair_off.device)
+    check(lib().hvpr_boxes_pairwise_ragged_f32(_ptr(a, torch.float32, "boxes_a"), _ptr(b, torch.float32, "boxes_b"),
+                                               _ptr(a_off, torch.int64, "a_off"), _ptr(b_off, torch.int64, "b_off"),
+                                               _ptr(pair_off, torch.int64, "pair_off"), pair_off.numel() - 1, int(n_pairs),
+                                               out.data_ptr(), _stream()), "hvpr_boxes_pairwise_ragged_f32")
+    return out
+
+
+def kitti_overlaps(gt_rows, dt_rows, inter, gt_off, dt_off, pair_off, n_pairs, metric):
+    """The host's frame_overlap for every frame: (n_pairs,) f64, frame f at pair_off[f] as its (nd_f, ng_f) matrix."""
+    out = torch.empty((int(n_pairs),), dtype=torch.float64, device=pair_off.device)
+    check(lib().hvpr_kitti_overlaps_f64(_ptr(gt_rows, torch.float64, "gt_rows"), _ptr(dt_rows, torch.float64, "dt_rows"),
+                                        _ptr(inter, torch.float32, "inter"), _ptr(gt_off, torch.int64, "gt_off"),
+                                        _ptr(dt_off, torch.int64, "dt_off"), _ptr(pair_off, torch.int64, "pair_off"),
+                                        pair_off.numel() - 1, int(n_pairs), int(metric), out.data_ptr(), _stream()),
+          "hvpr_kitti_overlaps_f64")
+    return out
+
+
+def kitti_match(gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, pair_off, overlaps, metric, classes, min_overlaps,
+                thresholds=None, thresh_count=None, compute_aos=False, out=None):
+    """Greedy matching of every (frame, class, difficulty, overlap set).  classes: class ids; min_overlaps [n_sets, n_classes]
+    (host).  Without thresholds, the threshold pass -> (tp_score [combos, NG] f64, n_valid [n_classes, 3] i32); with thresholds
+    [combos, T] f64 and thresh_count [combos] i32 (cuda), the counting pass -> (counts [combos, T, 3] i32, sim [combos, T] f64).
+    `out`: the pair of tensors to fill instead of new ones."""
+    import ctypes
+    dev = pair_off.device
+    F, NG = pair_off.numel() - 1, gt_rows.shape[0]
+    C, K = len(classes), len(min_overlaps)
+    combos = C * 3 * K
+    c_classes = (ctypes.c_int32 * C)(*[int(c) for c in classes])
+    c_mo = (ctypes.c_double * (K * C))(*[float(v) for row in min_overlaps for v in row])
+    if thresholds is None:
+        a, b = out if out is not None else (torch.empty((combos, NG), dtype=torch.float64, device=dev),
+                                            torch.empty((C, 3), dtype=torch.int32, device=dev))
+        args = (None, None, 1, 0, _ptr(a, torch.float64, "tp_score"), _ptr(b, torch.int32, "n_valid"), None, None, None, 0)
+    else:
+        T = thresholds.shape[1]
+        a, b = out if out is not None else (torch.empty((combos, T, 3), dtype=torch.int32, device=dev),
+                                            torch.empty((combos, T), dtype=torch.float64, device=dev))
+        ws = torch.empty((lib().hvpr_kitti_match_workspace_bytes(F, C, K, T),), dtype=torch.uint8, device=dev)
+        args = (_ptr(thresholds, torch.float64, "thresholds"), _ptr(thresh_count, torch.int32, "thresh_count"), T, int(bool(compute_aos)),
+                None, None, _ptr(a, torch.int32, "counts"), _ptr(b, torch.float64, "sim"), ws.data_ptr(), ws.numel())
+    check(lib().hvpr_kitti_match_f64(_ptr(gt_rows, torch.float64, "gt_rows"), _ptr(gt_cls, torch.int32, "gt_cls"),
+                                     _ptr(gt_dontcare, torch.uint8, "gt_dontcare"), _ptr(dt_rows, torch.float64, "dt_rows"),
+                                     _ptr(dt_cls, torch.int32, "dt_cls"), _ptr(gt_off, torch.int64, "gt_off"),
+                                     _ptr(dt_off, torch.int64, "dt_off"), _ptr(pair_off, torch.int64, "pair_off"), F, NG,
+                                     _ptr(overlaps, torch.float64, "overlaps"), int(metric), 0 if thresholds is None else 1,
+                                     c_classes, C, c_mo, K, *args, _stream()), "hvpr_kitti_match_f64")
+    return a, b

@@ -201,15 +201,19 @@ def get_mAP_R40(prec):
     return prec[..., 1:].sum(axis=-1) / 40 * 100
 
 
-def get_official_eval_result(gt_annos, dt_annos, current_classes, rotated_intersection=hip_rotated_intersection):
-    """-> (text, ret_dict) with the reference's keys ('Car_3d/moderate_R40', ...)."""
+def get_official_eval_result(gt_annos, dt_annos, current_classes, rotated_intersection=hip_rotated_intersection, eval_class_fn=None):
+    """-> (text, ret_dict) with the reference's keys ('Car_3d/moderate_R40', ...).  eval_class_fn(gt_annos, dt_annos, classes, metric,
+    min_overlaps, compute_aos), when given, stands in for eval_class (kitti_eval_device shares the table and key code this way)."""
     names = {v: k for k, v in CLASS_TO_NAME.items()}
     classes = [names[c] if isinstance(c, str) else c for c in (current_classes if isinstance(current_classes, (list, tuple)) else [current_classes])]
     mo = _OVERLAPS[:, :, classes]
     compute_aos = any(len(a["alpha"]) and a["alpha"][0] != -10 for a in dt_annos[:next((i + 1 for i, a in enumerate(dt_annos) if len(a["alpha"])), 0)])
     res, tables = {}, {}
     for metric, tag in ((0, "bbox"), (1, "bev"), (2, "3d")):
-        r = eval_class(gt_annos, dt_annos, classes, metric, mo, compute_aos and metric == 0, rotated_intersection)
+        if eval_class_fn is None:
+            r = eval_class(gt_annos, dt_annos, classes, metric, mo, compute_aos and metric == 0, rotated_intersection)
+        else:
+            r = eval_class_fn(gt_annos, dt_annos, classes, metric, mo, compute_aos and metric == 0)
         tables[tag] = (get_mAP(r["precision"]), get_mAP_R40(r["precision"]))
         if metric == 0 and compute_aos:
             tables["aos"] = (get_mAP(r["orientation"]), get_mAP_R40(r["orientation"]))

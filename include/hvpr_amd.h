@@ -322,6 +322,41 @@ int hvpr_gather_predictions_batched_f32(const float *boxes, int box_stride, long
                                         float *out_scores, int64_t *out_labels, int64_t *out_selected, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f3  KITTI AP on the device (hvpr_amd/kitti_eval_device.py; the host evaluator hvpr_amd/kitti_eval.py is the yardstick).
+ *     All F frames of a split lie end to end: frame f owns rows off[f] .. off[f + 1) of its table and the nd_f x ng_f pairs
+ *     pair_off[f] .. pair_off[f + 1), pair p = (detection i, ground truth j) = divmod(p - pair_off[f], ng_f).  The offset
+ *     arrays are DEVICE int64 [F + 1] and must be consistent (pair_off[F] == n_pairs); they are not checked on the device.
+ *     hvpr_boxes_pairwise_ragged_f32: mode 0 of hvpr_boxes_pairwise_f32 for every frame in one launch, bit for bit: out[p] =
+ *       overlap area of row a_off[f] + i of boxes_a and row b_off[f] + j of boxes_b (7 floats per row).
+ *     hvpr_kitti_overlaps_f64: out[p] = frame_overlap of the host in double.  Annotation rows are 16 doubles: bbox[4], alpha,
+ *       location[3], dimensions[3], rotation_y, occluded, truncated, score, pad.  metric 0 bbox IoU (inter may be NULL), 1 BEV,
+ *       2 3-D: `inter` is the ragged fp32 intersection of the (x, z, l, w, -rotation_y) rectangles.
+ *     hvpr_kitti_match_f64: greedy matching of every (frame, class m, difficulty l, overlap set k), combo = (m * 3 + l) * n_sets
+ *       + k.  classes [n_classes <= 8] (ids 0..5 of Car, Pedestrian, Cyclist, Van, Person_sitting, Truck) and min_overlaps
+ *       [n_sets <= 4][n_classes] (>= 0) are HOST arrays; gt_cls / dt_cls hold those ids (or -1), gt_dontcare one byte per box.
+ *       At most 4096 detections per frame (checked by the caller).
+ *       pass 0 (thresholds): tp_score [combos][n_gt_total] = score of the detection matched to each ground truth as a true
+ *         positive, else NaN; n_valid [n_classes][3] = ground truths to evaluate.  thresholds .. workspace are unused.
+ *       pass 1 (counts): thresholds [combos][n_thresh] with thresh_count [combos] live entries each (device); counts [combos]
+ *         [n_thresh][3] = tp, fp, fn summed over the frames, sim [combos][n_thresh] = the orientation similarity of the true
+ *         positives (zeros, and sim may be NULL, when compute_aos == 0), zeros past thresh_count.  Integer sums, and the similarity is summed in one fixed order:
+ *         two runs give the same bits.  workspace: hvpr_kitti_match_workspace_bytes(...) bytes.
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_boxes_pairwise_ragged_f32(const float *boxes_a, const float *boxes_b, const int64_t *a_off, const int64_t *b_off,
+                                   const int64_t *pair_off, int n_frames, long long n_pairs, float *out, hvpr_stream_t stream);
+int hvpr_kitti_overlaps_f64(const double *gt_rows, const double *dt_rows, const float *inter, const int64_t *gt_off,
+                            const int64_t *dt_off, const int64_t *pair_off, int n_frames, long long n_pairs, int metric,
+                            double *out, hvpr_stream_t stream);
+size_t hvpr_kitti_match_workspace_bytes(int n_frames, int n_classes, int n_sets, int n_thresh);
+int hvpr_kitti_match_f64(const double *gt_rows, const int32_t *gt_cls, const uint8_t *gt_dontcare, const double *dt_rows,
+                         const int32_t *dt_cls, const int64_t *gt_off, const int64_t *dt_off, const int64_t *pair_off,
+                         int n_frames, long long n_gt_total, const double *overlaps, int metric, int pass,
+                         const int32_t *classes, int n_classes, const double *min_overlaps, int n_sets,
+                         const double *thresholds, const int32_t *thresh_count, int n_thresh, int compute_aos,
+                         double *tp_score, int32_t *n_valid, int32_t *counts, double *sim, void *workspace,
+                         size_t workspace_bytes, hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a9 (training)  PointNet++ index ops.  Replace the absent natives of pcdet/ops/pointnet2/pointnet2_batch (setup.py:94-109)
  *     behind PointnetSAModuleMSG / PointnetFPModule (pcdet/models/backbones_3d/pointnet2_backbone.py:27-34,43-47,82,86-89).
  *     Indices only (no gradient); tie rule: lowest index.  Distances are fp32 (dx*dx + dy*dy) + dz*dz.
