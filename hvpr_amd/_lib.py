@@ -109,6 +109,12 @@ SIGNATURES = {
     "hvpr_bn_train_affine_f32": (_I, [_P, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hvpr_bn_finalize_partials_f32": (_I, [_P, _I, _I, _c.c_longlong, _F, _P, _P, _P, _P]),
     "hvpr_conv2d_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "hvpr_augment_block_points": (_I, []),
+    "hvpr_augment_collide_f32": (_I, [_P, _P, _I, _P, _P]),
+    "hvpr_augment_boxes_f32": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "hvpr_augment_points_workspace_bytes": (_Z, [_I, _I, _I, _c.c_longlong]),
+    "hvpr_augment_points_f32": (_I, [_P, _P, _I, _P, _P, _c.c_longlong, _I, _P, _c.c_longlong, _P, _I, _I, _P, _P, _c.c_longlong, _P,
+                                     _P, _Z, _P]),
 }
 
 _lib = None

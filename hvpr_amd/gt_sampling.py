@@ -5,7 +5,10 @@ signatures their call sites use:
   iou3d_nms_utils.boxes_bev_iou_cpu(boxes_a (N,7), boxes_b (M,7)) -> (N,M) float32     (database_sampler.py:184-185)
   box_utils.remove_points_in_boxes3d(points, boxes3d)                                   (box_utils.py:74-88)
 
-Host code (libhvpr_cpu.so, C++ through ctypes) for data-loader workers; numpy in, numpy out."""
+Host code (libhvpr_cpu.so, C++ through ctypes) for data-loader workers; numpy in, numpy out.
+
+The whole augmentation as a batched device op (GT sampling, flip, rotation, scaling, box trim) is hvpr_amd.augment.DeviceAugmentor;
+these natives stay as they are, for host pipelines and as the host leg of tools/bench_augment.py."""
 import ctypes
 import os
 

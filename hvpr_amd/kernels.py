@@ -894,3 +894,74 @@ def kitti_match(gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, p
                                      _ptr(overlaps, torch.float64, "overlaps"), int(metric), 0 if thresholds is None else 1,
                                      c_classes, C, c_mo, K, *args, _stream()), "hvpr_kitti_match_f64")
     return a, b
+
+
+# ------------------------------------------------------------------------------------------------ f4: training augmentation
+def augment_block_points():
+    """Scene points per workgroup of the point passes."""
+    return int(lib().hvpr_augment_block_points())
+
+
+def augment_collide(plan_host, plan_dev, words):
+    """valid (C,) int32: which candidates of the packed plan may be pasted.  `plan_host` is the (pinned) int32 host tensor the
+    device copy `plan_dev` was made from; the library checks it before it launches anything."""
+    C = int(plan_host.numpy()[4])
+    valid = torch.zeros((max(C, 1),), dtype=torch.int32, device=plan_dev.device)
+    check(lib().hvpr_augment_collide_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words), valid.data_ptr(),
+                                         _stream()), "hvpr_augment_collide_f32")
+    return valid[:C]
+
+
+def augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_outside, g_cap, out=None, count=None):
+    """(gt_boxes (B, g_cap, 8), count (B,) int32)."""
+    import numpy as np
+    B = int(plan_host.numpy()[1])
+    rng6 = np.ascontiguousarray(point_cloud_range, np.float32)
+    if out is None:
+        out = torch.empty((B, g_cap, 8), dtype=torch.float32, device=plan_dev.device)
+    if count is None:
+        count = torch.empty((B,), dtype=torch.int32, device=plan_dev.device)
+    check(lib().hvpr_augment_boxes_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words),
+                                       _ptr(valid, torch.int32, "valid"), rng6.ctypes.data, int(bool(remove_outside)), int(g_cap),
+                                       _ptr(out, torch.float32, "gt_boxes"), _ptr(count, torch.int32, "count"), _stream()),
+          "hvpr_augment_boxes_f32")
+    return out, count
+
+
+def augment_points(plan_host, plan_dev, words, valid, points, bank_points, bank_boxes, extra_width, out=None, out_off=None):
+    """(out_points (capacity, F), out_off (B+1,) int32).  capacity = scene points + the points of all candidates, known on the
+    host: nothing is read to allocate."""
+    import numpy as np
+    h = plan_host.numpy()                      # the host copy: header B, NG, G, C; pt_off and cand_n as csrc/augment.hip lays them out
+    B, NG, G, C = int(h[1]), int(h[2]), int(h[3]), int(h[4])
+    n, F = points.shape
+    ex = np.ascontiguousarray(extra_width, np.float32)
+    pt_off = h[8 + (B + 1) + (B * NG + 1):][: B + 1]
+    max_frame = int(np.diff(pt_off).max()) if B > 0 else 0
+    if out is None:
+        c5 = 8 + (B + 1) + (B * NG + 1) + (B + 1) + G + 4 * C
+        out = torch.empty((n + int(h[c5: c5 + C].sum()), F), dtype=torch.float32, device=points.device)
+    if out_off is None:
+        out_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
+    ws_bytes = lib().hvpr_augment_points_workspace_bytes(B, max_frame, C, n)
+    ws = torch.empty((max(int(ws_bytes), 256),), dtype=torch.uint8, device=points.device)
+    check(lib().hvpr_augment_points_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words),
+                                        _ptr(valid, torch.int32, "valid"), _ptr(points, torch.float32, "points"), n, F,
+                                        _ptr(bank_points, torch.float32, "bank points"), bank_points.shape[0],
+                                        _ptr(bank_boxes, torch.float32, "bank boxes"), bank_boxes.shape[0], bank_points.shape[1],
+                                        ex.ctypes.data, _ptr(out, torch.float32, "out_points"), out.shape[0],
+                                        _ptr(out_off, torch.int32, "out_off"), ws.data_ptr(), ws.numel(), _stream()),
+          "hvpr_augment_points_f32")
+    return out, out_off
+
+
+def augment_batch(plan_host, plan_dev, words, points, bank, extra_width, point_cloud_range, remove_outside, g_cap):
+    """All launches of one DeviceAugmentor call.  `counts` (2B+1,) int32 holds the point offsets, then the box counts: the one
+    buffer the caller reads."""
+    B = int(plan_host.numpy()[1])
+    arena, obj_box = bank.on_device()
+    counts = torch.empty((2 * B + 1,), dtype=torch.int32, device=points.device)
+    valid = augment_collide(plan_host, plan_dev, words)
+    gt, _ = augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_outside, g_cap, count=counts[B + 1:])
+    pts, off = augment_points(plan_host, plan_dev, words, valid, points, arena, obj_box, extra_width, out_off=counts[: B + 1])
+    return {"points": pts, "point_frame_offsets": off, "gt_boxes": gt, "valid": valid, "counts": counts}

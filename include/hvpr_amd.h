@@ -686,6 +686,50 @@ int hvpr_gather_rows_f32(const float *src, int n_src, int row_floats, const int3
 int hvpr_frame_offsets_f32(const float *points, int n_points, int point_stride, int batch, int32_t *frame_offsets,
                            hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * f4  Training augmentation on the device, a whole batch per call: GT sampling (database_sampler.py:118-200), world flip /
+ *     rotation / scaling (augmentor_utils.py:6-78), limit_period (data_augmentor.py:95-97) and the training-only box trim
+ *     (data_processor.py:24-28).  The random draws are the host's; they arrive as one packed plan of 32-bit words (layout:
+ *     csrc/augment.hip; packed by hvpr_amd/augment.py), given twice: `plan_host` (read and checked here, before any launch) and
+ *     `plan_dev` (the same words on the device, read by the kernels).  Every check is made on the host: a refused call returns
+ *     HVPR_ERR_INVALID_ARG / HVPR_ERR_UNSUPPORTED / HVPR_ERR_WORKSPACE and launches nothing, so no output is touched.  No entry
+ *     point synchronises or reads the device.
+ *     hvpr_augment_collide_f32  valid[c] = 1 when candidate c may be pasted: max IoU against the frame's existing boxes (ALL its
+ *                           ground truths, then what earlier groups accepted) plus max IoU against the other candidates of its
+ *                           group is exactly 0 (:184-188; an empty existing set takes the group table twice, :187).  The IoU is
+ *                           the rotated-BEV routine of hvpr_boxes_pairwise_f32.  A frame may hold 256 ground truths + candidates
+ *                           (else HVPR_ERR_UNSUPPORTED).
+ *     hvpr_augment_boxes_f32    gt_out [B, g_cap, 8]: per frame the ground truths of trained classes in order, then the accepted
+ *                           candidates in order; each row flipped / rotated / scaled, heading through limit_period(., 0.5, 2 pi),
+ *                           column 7 = class index + 1; with remove_outside, rows with none of their 8 corners inside range6
+ *                           (x0 y0 z0 x1 y1 z1, a HOST pointer, bounds inclusive) are dropped (box_utils.py:55-71); rows are compacted
+ *                           stably, zero rows follow, box_count[f] rows are live.  g_cap must hold every frame's rows even if all
+ *                           its candidates were accepted.
+ *     hvpr_augment_points_f32   out_points / out_off [B+1] i32: per frame the accepted candidates' points in candidate order (bank
+ *                           arena rows + the object's database box centre, z minus the road-plane move), then the scene points
+ *                           that lie in no accepted candidate's box enlarged by extra_width3 (a HOST pointer; inside means
+ *                           |z - cz| <= dz/2, |x| < dx/2 and |y| < dy/2 in the box frame), in their order; every written point is
+ *                           flipped / rotated / scaled, the other features pass through.  The rotation of a point is x' = fmaf(y, -s, x c),
+ *                           y' = fmaf(y, c, x s): the second product fused, as the reference's float32 gemm over a frame's points
+ *                           accumulates; a box row (hvpr_augment_boxes_f32) takes the unfused sum of torch's small-matrix path.  Count pass, one-workgroup scan, write
+ *                           pass: no atomics, stable, bit-reproducible.  out_capacity (rows) must be at least n_points + the
+ *                           points of ALL candidates; bank_floats must equal point_floats; candidate object ids must lie in
+ *                           [0, n_objects) and their rows inside bank_rows; 256 candidates per frame; rows are 32-bit offsets.
+ *     hvpr_augment_block_points scene points per workgroup of the count / write passes (tests put frame sizes around it).
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_augment_block_points(void);
+int hvpr_augment_collide_f32(const int32_t *plan_host, const int32_t *plan_dev, int plan_words, int32_t *valid,
+                             hvpr_stream_t stream);
+int hvpr_augment_boxes_f32(const int32_t *plan_host, const int32_t *plan_dev, int plan_words, const int32_t *valid,
+                           const float *range6, int remove_outside, int g_cap, float *gt_out, int32_t *box_count,
+                           hvpr_stream_t stream);
+size_t hvpr_augment_points_workspace_bytes(int n_frames, int max_frame_points, int n_candidates, long long n_points);
+int hvpr_augment_points_f32(const int32_t *plan_host, const int32_t *plan_dev, int plan_words, const int32_t *valid,
+                            const float *points, long long n_points, int point_floats, const float *bank_points,
+                            long long bank_rows, const float *bank_boxes, int n_objects, int bank_floats,
+                            const float *extra_width3, float *out_points, long long out_capacity, int32_t *out_off,
+                            void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
