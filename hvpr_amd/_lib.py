@@ -50,6 +50,8 @@ SIGNATURES = {
     "hvpr_kitti_match_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "hvpr_kitti_match_f64": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _c.c_longlong, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I,
                                   _P, _P, _P, _P, _P, _Z, _P]),
+    "hvpr_recall_record_f32": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "hvpr_prediction_annos_f32": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _c.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hvpr_nms_bev_batched_workspace_bytes": (_Z, [_I, _I]),
     "hvpr_nms_bev_batched_f32": (_I, [_P, _I, _c.c_longlong, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]),
     "hvpr_gather_predictions_batched_f32": (_I, [_P, _I, _c.c_longlong, _I, _P, _P, _c.c_longlong, _P, _I, _I, _P, _P, _P, _P, _P]),

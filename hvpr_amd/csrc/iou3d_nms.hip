@@ -28,15 +28,7 @@ __global__ void __launch_bounds__(64) k_pairwise(const float *__restrict__ a, in
     float r;
     if (mode == 0) r = box_overlap(A, B, ps, ln);
     else if (mode == 1) r = iou_bev(A, B, ps, ln);
-    else {
-        const float a_top = pa[2] + pa[5] / 2, a_bot = pa[2] - pa[5] / 2;
-        const float b_top = pb[2] + pb[5] / 2, b_bot = pb[2] - pb[5] / 2;
-        const float va = pa[3] * pa[4] * pa[5], vb = pb[3] * pb[4] * pb[5];
-        const float ob = box_overlap(A, B, ps, ln);
-        const float oh = fmaxf(fminf(a_top, b_top) - fmaxf(a_bot, b_bot), 0.0f);
-        const float o3 = ob * oh;
-        r = o3 / fmaxf(va + vb - o3, 1e-6f);
-    }
+    else r = iou_3d(pa, pb, A, B, ps, ln);
     out[t] = r;
 }
 

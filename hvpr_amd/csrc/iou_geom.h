@@ -1,5 +1,5 @@
-// The rotated-BEV geometry shared by the kernels that test boxes against boxes: iou3d_nms.hip (pairwise tables, NMS) and
-// augment.hip (the collision test of GT sampling).  ONE copy: the fp32 sequence below is the one the CPU oracle
+// The rotated-BEV geometry shared by the kernels that test boxes against boxes: iou3d_nms.hip (pairwise tables, NMS),
+// augment.hip (the collision test of GT sampling) and eval_tail.hip (the recall record).  ONE copy: the fp32 sequence below is the one the CPU oracle
 // (oracle/iou3d_nms_ref.c) runs, and every file that includes this header is compiled with -ffp-contract=off.
 #pragma once
 #include "common.h"
@@ -148,6 +148,19 @@ __device__ __forceinline__ float iou_bev(const Box &A, const Box &B, PolyStore &
     const float sa = A.dx * A.dy, sb = B.dx * B.dy;
     const float so = box_overlap(A, B, ps, ln);
     return so / fmaxf(sa + sb - so, kEps);
+}
+
+// 3-D IoU of the rows pa / pb that A / B were made from: BEV overlap times the common height over the union volume (the
+// upstream boxes_iou3d_gpu).  ONE copy for the pairwise table (iou3d_nms.hip) and the recall record (eval_tail.hip).
+__device__ __forceinline__ float iou_3d(const float *__restrict__ pa, const float *__restrict__ pb, const Box &A, const Box &B,
+                                        PolyStore &ps, int ln) {
+    const float a_top = pa[2] + pa[5] / 2, a_bot = pa[2] - pa[5] / 2;
+    const float b_top = pb[2] + pb[5] / 2, b_bot = pb[2] - pb[5] / 2;
+    const float va = pa[3] * pa[4] * pa[5], vb = pb[3] * pb[4] * pb[5];
+    const float ob = box_overlap(A, B, ps, ln);
+    const float oh = fmaxf(fminf(a_top, b_top) - fmaxf(a_bot, b_bot), 0.0f);
+    const float o3 = ob * oh;
+    return o3 / fmaxf(va + vb - o3, 1e-6f);
 }
 
 }  // namespace

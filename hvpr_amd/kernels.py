@@ -896,6 +896,53 @@ def kitti_match(gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, p
     return a, b
 
 
+# ------------------------------------------------------------------------------------------------ f5: evaluation epilogue
+def recall_record(pred_boxes, pred_count, gt_boxes, thresholds, counts=None, best_iou=None):
+    """generate_recall_record for every frame of a batch, no host read.  pred_boxes (B, P, 7) f32 with pred_count (B,) i32 live
+    rows; gt_boxes (B, G, C >= 7) f32; thresholds: at most 8 host floats.  -> counts (B, 1 + T) i32 = ground truths, then the
+    recalled ones per threshold.  best_iou: an optional (B, G) f32 tensor to fill."""
+    import ctypes
+    B, P = int(pred_boxes.shape[0]), int(pred_boxes.shape[1])
+    if pred_boxes.dim() != 3 or pred_boxes.shape[2] != 7 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or pred_count.numel() != B:
+        raise ValueError("recall_record: pred_boxes (B, P, 7), pred_count (B,) and gt_boxes (B, G, C) must agree")
+    G, C, T = int(gt_boxes.shape[1]), int(gt_boxes.shape[2]), len(thresholds)
+    if counts is None:
+        counts = torch.empty((B, 1 + T), dtype=torch.int32, device=pred_boxes.device)
+    if tuple(counts.shape) != (B, 1 + T) or (best_iou is not None and tuple(best_iou.shape) != (B, G)):
+        raise ValueError("recall_record: counts must be (B, 1 + T) and best_iou (B, G)")
+    thr = (ctypes.c_float * max(T, 1))(*[float(t) for t in thresholds])
+    check(lib().hvpr_recall_record_f32(_ptr(pred_boxes, torch.float32, "pred_boxes"), _ptr(pred_count, torch.int32, "pred_count"), B, P,
+                                       _ptr(gt_boxes, torch.float32, "gt_boxes"), G, C, thr, T, _ptr(counts, torch.int32, "counts"),
+                                       _ptr(best_iou, torch.float32, "best_iou"), _stream()), "hvpr_recall_record_f32")
+    return counts
+
+
+def prediction_annos(pred_boxes, pred_scores, pred_labels, pred_count, calib, class_of_label, row_base, frame_base, dt_rows, dt_cls,
+                     dt_label, dt_box7, boxes_lidar, dt_off, overflow):
+    """generate_prediction_dicts for a batch into the caller's split-wide tables, no host read: frame b's live rows follow frame
+    b - 1's from row_base[0] (a device int64 word, advanced here) on; dt_off[frame_base + b + 1] is set.  calib (B, 26) f32 cuda
+    (eval_loop.pack_calib), class_of_label: host ints, label - 1 -> evaluator class id."""
+    import ctypes
+    B, P = int(pred_boxes.shape[0]), int(pred_boxes.shape[1])
+    if tuple(pred_boxes.shape) != (B, P, 7) or tuple(pred_scores.shape) != (B, P) or tuple(pred_labels.shape) != (B, P) \
+            or pred_count.numel() != B or tuple(calib.shape) != (B, 26):
+        raise ValueError("prediction_annos: shapes do not match")
+    cap = int(dt_rows.shape[0])
+    if tuple(dt_rows.shape) != (cap, 16) or dt_cls.numel() != cap or dt_label.numel() != cap or tuple(dt_box7.shape) != (cap, 7) \
+            or tuple(boxes_lidar.shape) != (cap, 7):
+        raise ValueError("prediction_annos: the tables must hold the same number of rows")
+    n = len(class_of_label)
+    cmap = (ctypes.c_int32 * max(n, 1))(*[int(c) for c in class_of_label])
+    check(lib().hvpr_prediction_annos_f32(_ptr(pred_boxes, torch.float32, "pred_boxes"), _ptr(pred_scores, torch.float32, "pred_scores"),
+                                          _ptr(pred_labels, torch.int64, "pred_labels"), _ptr(pred_count, torch.int32, "pred_count"),
+                                          B, P, _ptr(calib, torch.float32, "calib"), cmap, n, _ptr(row_base, torch.int64, "row_base"),
+                                          cap, int(frame_base), dt_off.numel() - 1, _ptr(dt_rows, torch.float64, "dt_rows"),
+                                          _ptr(dt_cls, torch.int32, "dt_cls"), _ptr(dt_label, torch.int32, "dt_label"),
+                                          _ptr(dt_box7, torch.float32, "dt_box7"), _ptr(boxes_lidar, torch.float32, "boxes_lidar"),
+                                          _ptr(dt_off, torch.int64, "dt_off"), _ptr(overflow, torch.int32, "overflow"), _stream()),
+          "hvpr_prediction_annos_f32")
+
+
 # ------------------------------------------------------------------------------------------------ f4: training augmentation
 def augment_block_points():
     """Scene points per workgroup of the point passes."""

@@ -82,6 +82,36 @@ class AnnoTables:
         self.n_gt, self.n_dt, self.n_pairs = int(self.gt_off[-1]), int(self.dt_off[-1]), int(self.pair_off[-1])
         self._dev = None
 
+    @classmethod
+    def from_device(cls, gt_annos, dt_rows, dt_cls, dt_box7, dt_off, n_dt, n_pairs, pair_off=None):
+        """Tables whose detection side is ALREADY on the device (eval_loop.DeviceEvalEpilogue fills it batch by batch): dt_rows
+        [>= n_dt, 16] f64, dt_cls i32, dt_box7 [.., 7] f32, dt_off [F + 1] int64, all cuda.  The ground truths are laid out from the
+        host dicts as in the constructor and uploaded with them.  n_dt and n_pairs are the two HOST totals the launches are sized
+        with (the caller reads them; nothing is read here); pair_off, when the caller formed it for that read, is taken as it is.
+        The detection side has no host copy: `dt_rows`, `dt_cls`, `dt_box7` and the host `dt_off` / `pair_off` stay None."""
+        import torch
+        self = cls.__new__(cls)
+        self.n_frames = F = len(gt_annos)
+        if dt_off.numel() != F + 1:
+            raise ValueError("gt_annos and dt_off must hold the same frames")
+        ng = np.array([len(a["name"]) for a in gt_annos], np.int64)
+        if F and ng.max() > MAX_GT_PER_FRAME:
+            raise ValueError(f"at most {MAX_GT_PER_FRAME} ground truths per frame (got {int(ng.max())})")
+        self.gt_off = np.concatenate([[0], np.cumsum(ng)]).astype(np.int64)
+        self.n_gt, self.n_dt, self.n_pairs = int(self.gt_off[-1]), int(n_dt), int(n_pairs)
+        if self.n_gt >= 2 ** 31 or self.n_dt >= 2 ** 31 or self.n_pairs > 2 ** 36:
+            raise ValueError("too many boxes or pairs for one evaluation")
+        self.gt_rows, self.gt_cls, gnames = _rows(gt_annos, False)
+        self.gt_dontcare = np.array([s == "DontCare" for s in gnames], np.uint8).reshape(-1)
+        self.gt_box7 = _as7(self.gt_rows)
+        self.dt_rows = self.dt_cls = self.dt_box7 = self.dt_off = self.pair_off = None
+        dev = dt_off.device
+        up = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev) for k in ("gt_rows", "gt_cls", "gt_dontcare", "gt_box7", "gt_off")}
+        if pair_off is None:
+            pair_off = device_pair_off(dt_off, up["gt_off"])
+        self._dev = dict(up, dt_rows=dt_rows, dt_cls=dt_cls, dt_box7=dt_box7, dt_off=dt_off, pair_off=pair_off)
+        return self
+
     _FIELDS = ("gt_rows", "gt_cls", "gt_dontcare", "gt_box7", "dt_rows", "dt_cls", "dt_box7", "gt_off", "dt_off", "pair_off")
 
     @property
@@ -91,6 +121,13 @@ class AnnoTables:
             import torch
             self._dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).cuda() for k in self._FIELDS}
         return self._dev
+
+
+def device_pair_off(dt_off, gt_off):
+    """pair_off [F + 1] int64 on the device from the two device offset arrays: pair_off[f + 1] - pair_off[f] = nd_f * ng_f."""
+    import torch
+    pairs = (dt_off[1:] - dt_off[:-1]) * (gt_off[1:] - gt_off[:-1])
+    return torch.cat([torch.zeros((1,), dtype=torch.int64, device=dt_off.device), torch.cumsum(pairs, 0)])
 
 
 def _read(t):

@@ -357,6 +357,35 @@ int hvpr_kitti_match_f64(const double *gt_rows, const int32_t *gt_cls, const uin
                          size_t workspace_bytes, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f5  Evaluation epilogue on the device (hvpr_amd/eval_loop.py): from the padded records of post_processing(sync=False) to recall
+ *     counters and KITTI annotation rows, a batch of B frames per call.  Neither entry point synchronises or reads the device;
+ *     every check is made on the host and a refused call launches nothing.
+ *     hvpr_recall_record_f32: generate_recall_record (detector3d_template.py:276-318) for every frame.  pred_boxes [B, P, 7] with
+ *       pred_count[b] live rows (device, clamped to 0..P); gt_boxes [B, G, C >= 7] padded with zero rows; thresholds [T <= 8] is a
+ *       HOST array (more: HVPR_ERR_UNSUPPORTED).  counts [B, 1 + T] i32: the frame's ground-truth count, then per threshold the
+ *       ground truths whose best 3-D IoU (mode 2 of hvpr_boxes_pairwise_f32, bit for bit) over the live predictions is > t.
+ *       Ground-truth count: trailing rows whose left-to-right fp32 sum of the C columns is 0 are cut, row 0 never is (a table of
+ *       zero rows counts one box, as in the reference); G == 0 counts nothing.  A frame without live predictions recalls nothing.
+ *       best_iou [B, G] (may be NULL): that best IoU; 0 for cut rows and for frames without predictions.
+ *     hvpr_prediction_annos_f32: generate_prediction_dicts (kitti_dataset.py:246-320, box_utils.py:152-235) for every frame, in
+ *       fp32, widened at the store.  pred_boxes [B, P, 7], pred_scores [B, P], pred_labels [B, P] i64 (1-based), pred_count [B];
+ *       calib [B, 26] f32 on the device: the 4 x 3 product V2C^T R0^T row-major, P2 3 x 4 row-major, image height, image width;
+ *       class_of_label [n_labels <= 16] a HOST map from label - 1 to the evaluator's class id (other labels give -1).  Frame b's
+ *       live rows go to rows row_base[0] + (live rows of frames before b) .. of the caller's tables: dt_rows [cap, 16] f64 (the
+ *       annotation row of f3), dt_cls / dt_label [cap] i32, dt_box7 [cap, 7] f32 (x, z, 0, l, w, 1, -rotation_y), boxes_lidar
+ *       [cap, 7] f32 (z is the bottom centre's: the reference lowers it in the array it returns); dt_off[frame_base + b + 1] = the
+ *       row after frame b's (dt_off holds max_frames + 1 int64 words, dt_off[0] is the caller's).  row_base is a DEVICE word, advanced by a
+ *       second launch after the first.  Rows at or past cap are not written; *overflow is then set to 1 and offsets stop at cap.
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_recall_record_f32(const float *pred_boxes, const int32_t *pred_count, int B, int P, const float *gt_boxes, int G, int C,
+                           const float *thresholds, int T, int32_t *counts, float *best_iou, hvpr_stream_t stream);
+int hvpr_prediction_annos_f32(const float *pred_boxes, const float *pred_scores, const int64_t *pred_labels,
+                              const int32_t *pred_count, int B, int P, const float *calib, const int32_t *class_of_label,
+                              int n_labels, int64_t *row_base, long long cap, int frame_base, int max_frames, double *dt_rows,
+                              int32_t *dt_cls, int32_t *dt_label, float *dt_box7, float *boxes_lidar, int64_t *dt_off,
+                              int32_t *overflow, hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a9 (training)  PointNet++ index ops.  Replace the absent natives of pcdet/ops/pointnet2/pointnet2_batch (setup.py:94-109)
  *     behind PointnetSAModuleMSG / PointnetFPModule (pcdet/models/backbones_3d/pointnet2_backbone.py:27-34,43-47,82,86-89).
  *     Indices only (no gradient); tie rule: lowest index.  Distances are fp32 (dx*dx + dy*dy) + dz*dz.
