@@ -308,11 +308,24 @@ def _winograd(weight, stride, adjoint):
     return weight.shape[2] == 3 and stride == 1 and kernels.conv_algo() == "winograd" and cout % 4 == 0 and cin % 8 == 0
 
 
+def _pad_cin8(w):
+    """w (Cout, Cin, k, k) with zero input channels appended up to a multiple of 8 (the direct kernel walks 8 per chunk)."""
+    pad = -w.shape[1] % 8
+    return w if pad == 0 else torch.nn.functional.pad(w, (0, 0, 0, 0, 0, pad))
+
+
+def _pad_channels(x, c):
+    """x (N,H,W,C) with zero channels appended up to c."""
+    return x if x.shape[-1] == c else torch.nn.functional.pad(x, (0, c - x.shape[-1]))
+
+
 def conv_fwd_raw(x, weight, stride=1, adjoint=False, stats=False):
     """x (N,H,W,Cin) -> conv(x, weight) (N,OH,OW,Cout), no bias / activation.  weight (Cout,Cin,k,k), k in {1,3}, pad (k-1)/2.
     stats: return (z, partials) — partials = the batch statistics' per-tile sums when the Winograd kernel produced them, else None.
     adjoint: weight is the (Cin', Cout', 3, 3) filter of the layer whose data gradient is wanted and x its output gradient.
-    Stride-1 3x3: the Winograd kernel (packed on the device per call) unless HVPR_CONV_ALGO=direct."""
+    Stride-1 3x3: the Winograd kernel (packed on the device per call) unless HVPR_CONV_ALGO=direct.  The direct kernel takes input
+    channels in eights: a count that is no multiple of 8 (the data gradient of a layer with 12 output channels) is padded with zero
+    channels, in x (x may come padded already) and in the packed filter."""
     if _winograd(weight, stride, adjoint):
         g = _wino_groups()
         partials = None
@@ -324,9 +337,9 @@ def conv_fwd_raw(x, weight, stride=1, adjoint=False, stats=False):
         return (z, partials) if stats else z
     def build():
         w = weight.detach().permute(1, 0, 2, 3).flip(2, 3) if adjoint else weight       # (Cin, Cout, k, k): the adjoint kernel
-        return kernels.pack_conv(w, None, None, stride=stride, relu=False, tile_cfg=_tile_cfg(w.shape[0]))
+        return kernels.pack_conv(_pad_cin8(w), None, None, stride=stride, relu=False, tile_cfg=_tile_cfg(w.shape[0]))
     pc = _packed(weight, ("direct", int(stride), bool(adjoint)), build)
-    z = kernels.conv2d_nhwc(x, pc)
+    z = kernels.conv2d_nhwc(_pad_channels(x, pc.cin), pc)
     return (z, None) if stats else z
 
 
@@ -385,8 +398,8 @@ class _Conv(torch.autograd.Function):
             else:            # ... = conv_stride1(zero-upsampled dz, flipped w)
                 N, H, W, _ = x.shape
                 OH, OW = dz.shape[1], dz.shape[2]
-                up = torch.zeros((N, H, W, cout), dtype=torch.float32, device=dz.device)
-                up[:, 0:2 * OH:2, 0:2 * OW:2] = dz
+                up = torch.zeros((N, H, W, (cout + 7) // 8 * 8), dtype=torch.float32, device=dz.device)    # (channels in eights: conv_fwd_raw)
+                up[:, 0:2 * OH:2, 0:2 * OW:2, :cout] = dz
                 dx = conv_fwd_raw(up, weight, 1, adjoint=True)
         if ctx.needs_input_grad[1]:
             dw = conv_wgrad(x, dz, k * k, s, cout, cin)
@@ -419,8 +432,9 @@ class _Deconv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             def build():
                 g = weight.detach().permute(0, 2, 3, 1).reshape(cin, cols, 1, 1)     # dx[ci] = sum_col dzs[col] * g[ci][col]
-                return kernels.pack_conv(g, None, None, stride=1, relu=False, tile_cfg=_tile_cfg(cin))
-            dx = kernels.conv2d_nhwc(dzs, _packed(weight, "deconv_dgrad", build))
+                return kernels.pack_conv(_pad_cin8(g), None, None, stride=1, relu=False, tile_cfg=_tile_cfg(cin))
+            pc = _packed(weight, "deconv_dgrad", build)
+            dx = kernels.conv2d_nhwc(_pad_channels(dzs, pc.cin), pc)       # (columns in eights: conv_fwd_raw)
         if ctx.needs_input_grad[1]:
             dg = conv_wgrad(x, dzs, 1, 1, cols, cin)                              # (cols, Cin, 1, 1)
             dw = dg.reshape(s, s, cout, cin).permute(3, 2, 0, 1).contiguous()

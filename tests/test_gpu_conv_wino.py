@@ -49,6 +49,7 @@ def test_wino_conv_matches_float64(N, H, W, cin, cout, groups, relu, gated):
     err_w, err_d = float((y.double() - ref).abs().max()) / s, float((yd.double() - ref).abs().max()) / s
     print(f"winograd {err_w:.2e}  direct {err_d:.2e} (max abs error / output scale)")
     assert err_w < 5e-6, (err_w, err_d)
+    assert err_d < 5e-6, (err_w, err_d)
     # written into a channel slice of a wider tensor (the concat of the 2D backbone)
     wide = torch.full((N, H, W, cout + 24), 7.0, device=DEV)
     kernels.conv2d_wino_nhwc(x, pc, out=wide, out_coff=12, gate=gate, resid=resid)
