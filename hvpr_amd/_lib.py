@@ -117,6 +117,11 @@ SIGNATURES = {
     "hvpr_augment_points_workspace_bytes": (_Z, [_I, _I, _I, _c.c_longlong]),
     "hvpr_augment_points_f32": (_I, [_P, _P, _I, _P, _P, _c.c_longlong, _I, _P, _c.c_longlong, _P, _I, _I, _P, _P, _c.c_longlong, _P,
                                      _P, _Z, _P]),
+    "hvpr_gt_database_block_points": (_I, []),
+    "hvpr_gt_database_workspace_bytes": (_Z, [_I, _I, _I]),
+    "hvpr_gt_database_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
+    "hvpr_gt_database_extract_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _c.c_longlong,
+                                          _P, _Z, _P]),
 }
 
 _lib = None

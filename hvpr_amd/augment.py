@@ -81,6 +81,28 @@ class ObjectBank:
         kw.setdefault("num_point_features", int(points[0].shape[1]) if len(points) else 4)
         return cls(infos, None, class_names, **kw)
 
+    @classmethod
+    def from_device(cls, db_infos, arena, rows_of, class_names, **kw):
+        """A bank over points that are already on the device (hvpr_amd.gt_database.DatabaseBuilder).  `arena` (rows, F) float32
+        device tensor; `rows_of[id(record)]` = (first row, rows) of that record's points in it.  The PREPARE filters run on the
+        records as ever; the survivors' segments are gathered into the bank's order on the device, and the host copy
+        (`host_points`) is made from that only when someone asks."""
+        from . import preprocess
+        kw.setdefault("num_point_features", int(arena.shape[1]))
+        kw.setdefault("device", arena.device)
+        bank = cls(db_infos, None, class_names, **kw)
+        seg = np.asarray([rows_of[id(r)] for r in bank.records], np.int64).reshape(-1, 2)
+        off = np.zeros((len(bank.records) + 1,), np.int64)
+        off[1:] = np.cumsum(seg[:, 1])
+        idx = np.arange(off[-1], dtype=np.int64) + np.repeat(seg[:, 0] - off[:-1], seg[:, 1])     # bank row -> arena row
+        if off[-1] > 0:
+            pts = preprocess.gather_rows(arena, torch.from_numpy(idx.astype(np.int32)).to(arena.device))
+        else:
+            pts = torch.zeros((0, bank.num_point_features), dtype=torch.float32, device=arena.device)
+        bank._dev = (pts, torch.from_numpy(bank.obj_box).to(arena.device))
+        bank._dev_off = off
+        return bank
+
     @staticmethod
     def filter_by_difficulty(db_infos, removed_difficulty):
         return {k: [i for i in v if i["difficulty"] not in removed_difficulty] for k, v in db_infos.items()}
@@ -99,6 +121,8 @@ class ObjectBank:
 
     def host_points(self):
         """(arena (P_total, F) f32, obj_off (n+1) i64): every object's points, loaded once (database_sampler.py:132-134)."""
+        if self._host is None and getattr(self, "_dev_off", None) is not None:       # from_device: the arena is the source
+            self._host = (np.ascontiguousarray(self._dev[0].cpu().numpy(), np.float32), self._dev_off)
         if self._host is None:
             F, parts = self.num_point_features, []
             for r in self.records:

@@ -1012,3 +1012,56 @@ def augment_batch(plan_host, plan_dev, words, points, bank, extra_width, point_c
     gt, _ = augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_outside, g_cap, count=counts[B + 1:])
     pts, off = augment_points(plan_host, plan_dev, words, valid, points, arena, obj_box, extra_width, out_off=counts[: B + 1])
     return {"points": pts, "point_frame_offsets": off, "gt_boxes": gt, "valid": valid, "counts": counts}
+
+
+# ------------------------------------------------------------------------------------------------ f6: the GT-sampling database
+def gt_database_block_points():
+    """Scene points per workgroup of the count and write passes."""
+    return int(lib().hvpr_gt_database_block_points())
+
+
+def _gt_database_workspace(pt_off_host, n_obj, device, workspace):
+    import numpy as np
+    off = pt_off_host.numpy()
+    max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
+    need = int(lib().hvpr_gt_database_workspace_bytes(off.shape[0] - 1, max_frame, int(n_obj)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=device)
+    return workspace
+
+
+def gt_database_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off, obj_count=None, workspace=None):
+    """(obj_count (n_obj,) int32, workspace).  points (sum N, F) and boxes (n_obj, 7) float32 on the device; `pt_off_host` /
+    `box_off_host` are the int32 host tensors (B + 1,) the device copies `pt_off` / `box_off` were made from: the library checks
+    them before it launches anything.  The workspace goes to gt_database_extract of the same chunk."""
+    n, F = points.shape
+    n_obj, B = int(boxes.shape[0]), pt_off_host.numel() - 1
+    if obj_count is None:
+        obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=points.device)[:n_obj]
+    workspace = _gt_database_workspace(pt_off_host, n_obj, points.device, workspace)
+    check(lib().hvpr_gt_database_count_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
+                                           _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
+                                           box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"), n_obj,
+                                           _ptr(obj_count, torch.int32, "obj_count"), workspace.data_ptr(), workspace.numel(), _stream()),
+          "hvpr_gt_database_count_f32")
+    return obj_count, workspace
+
+
+def gt_database_extract(points, pt_off_host, pt_off, boxes, box_off_host, box_off, centres, obj_count_host, obj_count, arena,
+                        workspace, obj_off=None):
+    """obj_off (n_obj + 1,) int32; writes `arena` (capacity, F) rows obj_off[k] .. obj_off[k + 1] for every box k.  `workspace`
+    is the one gt_database_count filled for this chunk, `obj_count_host` the int32 host tensor of the counts read back."""
+    n, F = points.shape
+    n_obj, B = int(boxes.shape[0]), pt_off_host.numel() - 1
+    if arena.shape[1] != F:
+        raise ValueError("gt_database_extract: the arena must have the points' feature width")
+    if obj_off is None:
+        obj_off = torch.empty((n_obj + 1,), dtype=torch.int32, device=points.device)
+    check(lib().hvpr_gt_database_extract_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
+                                             _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
+                                             box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"),
+                                             _ptr(centres, torch.float64, "centres"), n_obj, obj_count_host.data_ptr(),
+                                             _ptr(obj_count, torch.int32, "obj_count"), _ptr(obj_off, torch.int32, "obj_off"),
+                                             _ptr(arena, torch.float32, "arena"), arena.shape[0], workspace.data_ptr(),
+                                             workspace.numel(), _stream()), "hvpr_gt_database_extract_f32")
+    return obj_off

@@ -759,6 +759,43 @@ int hvpr_augment_points_f32(const int32_t *plan_host, const int32_t *plan_dev, i
                             const float *extra_width3, float *out_points, long long out_capacity, int32_t *out_off,
                             void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * f6  The GT-sampling database from raw frames, a chunk of frames per call: the loop of KittiDataset.
+ *     create_groundtruth_database (kitti_dataset.py:205-238).  A chunk is one ragged point array `points` [n_points,
+ *     point_floats] f32 (3 <= point_floats <= 8, x y z first) with `pt_off` [n_frames + 1] i32, and the frames' annotated boxes
+ *     `boxes` [n_obj, 7] f32 (x y z dx dy dz heading) with `box_off` [n_frames + 1] i32.  Both offset arrays are given twice: the
+ *     `_host` copy is read and checked here, before any launch, the other is the same words on the device, read by the kernels.
+ *     Every check is made on the host: a refused call returns HVPR_ERR_INVALID_ARG / HVPR_ERR_UNSUPPORTED / HVPR_ERR_WORKSPACE
+ *     and launches nothing, so no output is touched.  No entry point synchronises or reads the device.  A frame may hold 256
+ *     boxes and a chunk 65535 frames (else HVPR_ERR_UNSUPPORTED); rows are 32-bit offsets.
+ *     A point is inside a box when |z - cz| <= dz/2 and, turned by -heading about the centre, |x| < dx/2 and |y| < dy/2: the
+ *     fp32 operations of hvpr_points_in_boxes_cpu (include/hvpr_cpu.h) in their order.
+ *     hvpr_gt_database_count_f32    obj_count[k] = points of box k's frame inside box k.  Per box and block of scene points the
+ *                           count stays in `workspace` for the extract call.  Usable alone, as the count-only mode.
+ *     hvpr_gt_database_extract_f32  after the host has read obj_count (`obj_count_host`, checked against `arena_capacity` rows:
+ *                           their sum must fit) and with the workspace the count call of the SAME chunk filled: obj_off
+ *                           [n_obj + 1] i32 = the exclusive prefix of obj_count, and arena rows obj_off[k] .. obj_off[k+1] = box
+ *                           k's points in the ascending order they have in their frame (a point inside two boxes appears in
+ *                           both).  Columns 0..2 are (float)((double)p - centres[k]) with `centres` [n_obj, 3] f64: numpy's
+ *                           float32 array minus float64 box (:226) rounds once; the other columns are copied.  Count pass,
+ *                           scans, write pass: no atomics, stable, bit-reproducible.  A row at or past arena_capacity is never
+ *                           written, whatever the device counts hold.
+ *     hvpr_gt_database_workspace_bytes  for frames of at most max_frame_points points and n_obj boxes in all; 0 for an empty
+ *                           chunk.  Needs no GPU.
+ *     hvpr_gt_database_block_points scene points per workgroup of the count / write passes (tests put frame sizes around it).
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_gt_database_block_points(void);
+size_t hvpr_gt_database_workspace_bytes(int n_frames, int max_frame_points, int n_obj);
+int hvpr_gt_database_count_f32(const float *points, long long n_points, int point_floats, const int32_t *pt_off_host,
+                               const int32_t *pt_off, int n_frames, const float *boxes, const int32_t *box_off_host,
+                               const int32_t *box_off, int n_obj, int32_t *obj_count, void *workspace, size_t workspace_bytes,
+                               hvpr_stream_t stream);
+int hvpr_gt_database_extract_f32(const float *points, long long n_points, int point_floats, const int32_t *pt_off_host,
+                                 const int32_t *pt_off, int n_frames, const float *boxes, const int32_t *box_off_host,
+                                 const int32_t *box_off, const double *centres, int n_obj, const int32_t *obj_count_host,
+                                 const int32_t *obj_count, int32_t *obj_off, float *arena, long long arena_capacity,
+                                 void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
