@@ -122,6 +122,11 @@ SIGNATURES = {
     "hvpr_gt_database_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
     "hvpr_gt_database_extract_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _c.c_longlong,
                                           _P, _Z, _P]),
+    "hvpr_ragged_select_tile_rows": (_I, []),
+    "hvpr_ragged_select_workspace_bytes": (_Z, [_c.c_longlong, _I]),
+    "hvpr_ragged_select_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "hvpr_ragged_select_write_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _P, _P, _c.c_longlong, _I, _P, _c.c_longlong,
+                                          _P, _P, _Z, _P]),
 }
 
 _lib = None

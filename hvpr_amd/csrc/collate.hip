@@ -1,0 +1,306 @@
+// f7 — training batches on the device: ragged select / shuffle / collate, a whole batch per launch.  The frames of a batch lie
+// end to end in one (rows, F) float32 array with DEVICE-resident offsets (B + 1,) int32 (after hvpr_augment_points_f32 the host
+// does not know them yet); rows at or past off[B] are capacity and are ignored.  Covers, for all frames at once,
+//   KittiDataset.get_fov_flag + points[fov_flag]                  pcdet/datasets/kitti/kitti_dataset.py:100-116, 379-383
+//   mask_points_by_range + points[mask]                           pcdet/datasets/processor/data_processor.py:20-23
+//   shuffle_points (points[permutation], drawn on the host)       data_processor.py:32-39
+//   collate_batch's `points` branch (batch index in column 0)     pcdet/datasets/dataset.py:161-166
+// The keep decisions are the expressions of point_pred.h, shared with hvpr_point_flags_f32.
+//
+// A flat stable compaction over tiles of kTile rows.  Lane l of wave w looks at rows tile + (4 w + k) 64 + l, k = 0..3, so one
+// ballot per k gives a group of 64 consecutive rows and the popcount of the lanes below gives a row's rank in it: loads and
+// (unpermuted) stores stay coalesced.  A row's frame is the binary search over the offsets staged in LDS.
+//   count pass   per-tile counts, and for every offset the count of kept rows in front of it inside the tile that contains it
+//                (lane-masked ballot)
+//   scan         one workgroup: exclusive prefix of the tile counts; new_off[b] = prefix of off[b]'s tile + that partial count
+//   write pass   recomputes the decisions, places each kept row by its flat rank
+// No atomics, no flag array, no spin-waits: bit-reproducible.
+#include "common.h"
+#include "point_pred.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kItems = 4;
+constexpr int kGroups = kWaves * kItems;       // ballots of 64 rows per tile
+constexpr int kTile = kThreads * kItems;
+constexpr int kMaxFrames = 1024;
+constexpr int kCalib = 26;                     // eval_loop.pack_calib: a (4x3), P2 (3x4), image height, image width
+
+struct SelArgs {
+    const float *pts;
+    int rows, F;
+    const int *off;
+    int B, mask, tiles;
+    const float *calib;
+    float x0, y0, x1, y1;
+};
+
+struct Staged {
+    int off[kMaxFrames + 1];
+    float cal[kCalib];       // the tile's first frame, p transposed to the 4 x 3 layout point_pred.h reads
+    int b0;
+};
+
+// largest b in [0, B) with off[b] <= row, for off[0] <= row < off[B] (an empty frame repeats its offset and is never found)
+__device__ __forceinline__ int frame_of(const int *off, int B, int row) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= row) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void load_calib(const float *row, float *dst, int i) {
+    // words 12..23 hold P2 (3 x 4, row-major); dst[12 + r*3 + c] = P2^T[r][c] = P2[c][r]
+    if (i < 12 || i >= 24) dst[i] = row[i];
+    else { const int r = (i - 12) / 3, c = (i - 12) % 3; dst[i] = row[12 + c * 4 + r]; }
+}
+
+// offsets clamped into [0, rows]: whatever the device words hold, no row outside the array is read
+__device__ __forceinline__ void stage(const SelArgs &a, Staged &s, int tile_base) {
+    for (int i = threadIdx.x; i <= a.B; i += kThreads) s.off[i] = min(max(a.off[i], 0), a.rows);
+    __syncthreads();
+    if (threadIdx.x == 0) s.b0 = (tile_base >= s.off[0] && tile_base < s.off[a.B]) ? frame_of(s.off, a.B, tile_base) : 0;
+    __syncthreads();
+    if ((a.mask & 1) && threadIdx.x < kCalib) load_calib(a.calib + (size_t)s.b0 * kCalib, s.cal, threadIdx.x);
+    __syncthreads();
+}
+
+__device__ __forceinline__ bool decide(const SelArgs &a, const Staged &s, int b, float x, float y, float z) {
+    bool f = true;
+    if (a.mask & 2) f = hvpr_pred_range_xy(x, y, a.x0, a.y0, a.x1, a.y1);
+    if (f && (a.mask & 1)) {
+        if (b == s.b0) {
+            f = hvpr_pred_fov(x, y, z, s.cal, s.cal + 12, s.cal[24], s.cal[25]);
+        } else {                                                     // a tile that spans frames: the later frames' rows
+            float c[kCalib];
+            const float *row = a.calib + (size_t)b * kCalib;
+#pragma unroll
+            for (int i = 0; i < kCalib; ++i) load_calib(row, c, i);
+            f = hvpr_pred_fov(x, y, z, c, c + 12, c[24], c[25]);
+        }
+    }
+    return f;
+}
+
+__global__ void __launch_bounds__(kThreads) k_select_count(SelArgs a, int *__restrict__ tile_count, int *__restrict__ partial) {
+    __shared__ Staged s;
+    __shared__ unsigned long long s_bal[kGroups];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int tile_base = blockIdx.x * kTile;
+    stage(a, s, tile_base);
+    const int lo = s.off[0], hi = s.off[a.B];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const int row = tile_base + (wid * kItems + k) * 64 + lane;
+        bool f = false;
+        if (row >= lo && row < hi) {
+            const float *p = a.pts + (size_t)row * a.F;
+            f = decide(a, s, frame_of(s.off, a.B, row), p[0], p[1], p[2]);
+        }
+        const unsigned long long bal = __ballot(f);
+        if (lane == 0) s_bal[wid * kItems + k] = bal;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+#pragma unroll
+        for (int g = 0; g < kGroups; ++g) c += __popcll(s_bal[g]);
+        tile_count[blockIdx.x] = c;
+    }
+    // the offsets that fall into this tile (the array's end belongs to the last tile)
+    for (int b = threadIdx.x; b <= a.B; b += kThreads) {
+        const int o = s.off[b];
+        if (min(o / kTile, a.tiles - 1) != (int)blockIdx.x) continue;
+        const int local = o - tile_base, g_end = local >> 6;           // 0 .. kTile
+        int c = 0;
+        for (int g = 0; g < g_end; ++g) c += __popcll(s_bal[g]);
+        if (g_end < kGroups) c += __popcll(s_bal[g_end] & ((1ull << (local & 63)) - 1ull));
+        partial[b] = c;
+    }
+}
+
+// one workgroup: tile_first[t] = kept rows in front of tile t, tile_first[tiles] = all; then the new offsets
+__global__ void __launch_bounds__(kThreads) k_select_scan(const int *__restrict__ off, int B, int rows, int tiles,
+                                                          const int *__restrict__ tile_count, int *__restrict__ tile_first,
+                                                          const int *__restrict__ partial, int *__restrict__ new_off) {
+    __shared__ int s_w[kWaves];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int carry = 0;
+    for (int c0 = 0; c0 < tiles; c0 += kThreads) {
+        const int t = c0 + threadIdx.x;
+        const int v = t < tiles ? tile_count[t] : 0;
+        int inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+        if (lane == 63) s_w[wid] = inc;
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < wid; ++w) before += s_w[w];
+        if (t < tiles) tile_first[t] = before + inc - v;
+        carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tile_first[tiles] = carry;
+    __syncthreads();                                                   // this workgroup's own global writes, read below
+    for (int b = threadIdx.x; b <= B; b += kThreads) {
+        if (tiles == 0) { new_off[b] = 0; continue; }
+        const int o = min(max(off[b], 0), rows);
+        new_off[b] = tile_first[min(o / kTile, tiles - 1)] + partial[b];
+    }
+}
+
+template <bool VEC4>
+__global__ void __launch_bounds__(kThreads) k_select_write(SelArgs a, const int *__restrict__ tile_first,
+                                                           const int *__restrict__ new_off, const int *__restrict__ inv_perm,
+                                                           long long n_perm, int batch_column, float *__restrict__ out,
+                                                           long long out_capacity, int *__restrict__ flag) {
+    __shared__ Staged s;
+    __shared__ int s_noff[kMaxFrames + 1];
+    __shared__ int s_w[kWaves];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int tile_base = blockIdx.x * kTile;
+    for (int i = threadIdx.x; i <= a.B; i += kThreads) s_noff[i] = new_off[i];
+    stage(a, s, tile_base);
+    const int lo = s.off[0], hi = s.off[a.B];
+    unsigned long long bal[kItems];
+    int frame[kItems];
+    bool keep[kItems];
+    float4 v[kItems];
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const int row = tile_base + (wid * kItems + k) * 64 + lane;
+        keep[k] = false;
+        frame[k] = 0;
+        v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row >= lo && row < hi) {
+            if (VEC4) {
+                v[k] = *reinterpret_cast<const float4 *>(a.pts + (size_t)row * 4);       // one 16-byte access per lane
+            } else {
+                const float *p = a.pts + (size_t)row * a.F;
+                v[k].x = p[0]; v[k].y = p[1]; v[k].z = p[2];
+            }
+            frame[k] = frame_of(s.off, a.B, row);
+            keep[k] = decide(a, s, frame[k], v[k].x, v[k].y, v[k].z);
+        }
+        bal[k] = __ballot(keep[k]);
+        total += __popcll(bal[k]);
+    }
+    if (lane == 0) s_w[wid] = total;
+    __syncthreads();
+    long long pos = tile_first[blockIdx.x];
+    for (int w = 0; w < wid; ++w) pos += s_w[w];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int W = a.F + (batch_column ? 1 : 0);
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const long long rank = pos + __popcll(bal[k] & below);
+        pos += __popcll(bal[k]);
+        if (!keep[k]) continue;
+        const int b = frame[k];
+        long long d = rank;
+        if (inv_perm) {
+            const int first = s_noff[b], m = s_noff[b + 1] - first;
+            if (rank >= n_perm) { *flag = 1; continue; }
+            const int q = inv_perm[rank];
+            if (q < 0 || q >= m) { *flag = 1; continue; }               // never a row of another frame, never out of bounds
+            d = (long long)first + q;
+        }
+        if (d < 0 || d >= out_capacity) { *flag = 1; continue; }
+        float *o = out + (size_t)d * W;
+        if (batch_column) *o++ = (float)b;
+        if (VEC4) {
+            if (!batch_column) {
+                *reinterpret_cast<float4 *>(o) = v[k];
+            } else {
+                o[0] = v[k].x; o[1] = v[k].y; o[2] = v[k].z; o[3] = v[k].w;
+            }
+        } else {
+            const float *p = a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F;
+            o[0] = v[k].x; o[1] = v[k].y; o[2] = v[k].z;
+            for (int j = 3; j < a.F; ++j) o[j] = p[j];
+        }
+    }
+}
+
+struct Carved {
+    int *tile_count, *tile_first, *partial;
+    size_t bytes;
+};
+
+Carved carve(void *ws, int tiles, int B) {
+    hvpr_carver c(ws);
+    Carved r;
+    r.tile_count = c.take<int>((size_t)tiles + 1);
+    r.tile_first = c.take<int>((size_t)tiles + 1);
+    r.partial = c.take<int>((size_t)B + 1);
+    r.bytes = c.off;
+    return r;
+}
+
+int check_args(const float *points, long long rows, int F, const int32_t *off, int B, int mask, const float *calib,
+               const float *range_xy, void *workspace, size_t workspace_bytes, SelArgs *a) {
+    if (rows < 0 || F < 3 || B < 1 || mask < 0 || mask > 3 || !off || !workspace) return HVPR_ERR_INVALID_ARG;
+    if ((rows > 0 && !points) || ((mask & 1) && !calib) || ((mask & 2) && !range_xy)) return HVPR_ERR_INVALID_ARG;
+    if (B > kMaxFrames || F > 64 || rows > 0x7fffffffLL - kTile) return HVPR_ERR_UNSUPPORTED;
+    if (workspace_bytes < hvpr_ragged_select_workspace_bytes(rows, B)) return HVPR_ERR_WORKSPACE;
+    a->pts = points; a->rows = (int)rows; a->F = F; a->off = off; a->B = B; a->mask = mask;
+    a->tiles = hvpr_cdiv(rows, kTile);
+    a->calib = calib;
+    a->x0 = (mask & 2) ? range_xy[0] : 0.f; a->y0 = (mask & 2) ? range_xy[1] : 0.f;
+    a->x1 = (mask & 2) ? range_xy[2] : 0.f; a->y1 = (mask & 2) ? range_xy[3] : 0.f;
+    return HVPR_OK;
+}
+
+}  // namespace
+
+extern "C" int hvpr_ragged_select_tile_rows(void) { return kTile; }
+
+extern "C" size_t hvpr_ragged_select_workspace_bytes(long long rows, int n_frames) {
+    if (rows < 0 || n_frames < 1) return 0;
+    return carve(nullptr, hvpr_cdiv(rows, kTile), n_frames).bytes;
+}
+
+extern "C" int hvpr_ragged_select_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, int32_t *new_off, void *workspace,
+                                            size_t workspace_bytes, hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, workspace, workspace_bytes, &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off) return HVPR_ERR_INVALID_ARG;
+    const Carved w = carve(workspace, a.tiles, n_frames);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.tiles > 0) hipLaunchKernelGGL(k_select_count, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_count, w.partial);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kThreads), 0, s, off, n_frames, a.rows, a.tiles, w.tile_count, w.tile_first,
+                       w.partial, new_off);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_ragged_select_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, const int32_t *new_off,
+                                            const int32_t *inv_perm, long long n_perm, int batch_column, float *out,
+                                            long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
+                                            hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, workspace, workspace_bytes, &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off || !flag || out_capacity < 0 || n_perm < 0 || (out_capacity > 0 && !out)) return HVPR_ERR_INVALID_ARG;
+    if (out_capacity > 0x7fffffffLL) return HVPR_ERR_UNSUPPORTED;
+    if (a.tiles == 0) return HVPR_OK;
+    const Carved w = carve(workspace, a.tiles, n_frames);
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec4 = point_floats == 4 && ((uintptr_t)points & 15) == 0 && (batch_column || ((uintptr_t)out & 15) == 0);
+    if (vec4)
+        hipLaunchKernelGGL(k_select_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_first, new_off, inv_perm, n_perm,
+                           batch_column ? 1 : 0, out, out_capacity, flag);
+    else
+        hipLaunchKernelGGL(k_select_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_first, new_off, inv_perm, n_perm,
+                           batch_column ? 1 : 0, out, out_capacity, flag);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}

@@ -9,6 +9,7 @@
 // fp32 arithmetic in a fixed order without FMA contraction (the reference's BLAS order for the K=4 products is
 // unspecified: the defined order here is left to right).
 #include "common.h"
+#include "point_pred.h"
 
 namespace {
 
@@ -23,11 +24,6 @@ struct FovArgs {
     int enabled;
 };
 
-__device__ __forceinline__ float dot4(float x, float y, float z, const float *m, int j) {
-    // ((x*m0 + y*m1) + z*m2) + 1*m3, no contraction (this file is compiled with -ffp-contract=off)
-    return ((x * m[j] + y * m[3 + j]) + z * m[6 + j]) + m[9 + j];
-}
-
 __global__ void __launch_bounds__(kThreads) k_point_flags(const float *__restrict__ pts, int n, int stride, int mode, float x0,
                                                           float y0, float x1, float y1, float near_thresh, FovArgs fov,
                                                           unsigned char *__restrict__ flags) {
@@ -37,14 +33,9 @@ __global__ void __launch_bounds__(kThreads) k_point_flags(const float *__restric
     const float x = p[0], y = p[1], z = p[2];
     bool f;
     if (mode == 0) {
-        f = x >= x0 && x <= x1 && y >= y0 && y <= y1;
-        if (f && fov.enabled) {
-            const float rx = dot4(x, y, z, fov.a, 0), ry = dot4(x, y, z, fov.a, 1), rz = dot4(x, y, z, fov.a, 2);
-            const float hx = dot4(rx, ry, rz, fov.p, 0), hy = dot4(rx, ry, rz, fov.p, 1), hz = dot4(rx, ry, rz, fov.p, 2);
-            const float u = __fdiv_rn(hx, rz), v = __fdiv_rn(hy, rz);       // divided by the rect depth (calibration_kitti.py:82)
-            const float depth = hz - fov.p[11];                              // P2.T[3,2]
-            f = u >= 0.f && u < fov.img_w && v >= 0.f && v < fov.img_h && depth >= 0.f;
-        }
+        // the shared expressions of point_pred.h (no contraction: this file is compiled with -ffp-contract=off)
+        f = hvpr_pred_range_xy(x, y, x0, y0, x1, y1);
+        if (f && fov.enabled) f = hvpr_pred_fov(x, y, z, fov.a, fov.p, fov.img_h, fov.img_w);
     } else {
         f = __fsqrt_rn((x * x + y * y) + z * z) < near_thresh;
     }

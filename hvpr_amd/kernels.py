@@ -1065,3 +1065,54 @@ def gt_database_extract(points, pt_off_host, pt_off, boxes, box_off_host, box_of
                                              _ptr(arena, torch.float32, "arena"), arena.shape[0], workspace.data_ptr(),
                                              workspace.numel(), _stream()), "hvpr_gt_database_extract_f32")
     return obj_off
+
+
+# ------------------------------------------------------------------------------------------------ f7: ragged select / collate
+def ragged_select_tile_rows():
+    """Rows per workgroup of the count and write passes."""
+    return int(lib().hvpr_ragged_select_tile_rows())
+
+
+def _range_xy(range_xy):
+    import numpy as np
+    return None if range_xy is None else np.ascontiguousarray(range_xy, np.float32).reshape(4)
+
+
+def ragged_select_count(points, off, mask, calib=None, range_xy=None, new_off=None, workspace=None):
+    """(new_off (B+1,) int32, workspace).  points (rows, F) float32 and off (B+1,) int32 on the device, `calib` (B, 26) float32
+    on the device (eval_loop.pack_calib) for mask bit 1, `range_xy` four host floats (x0, y0, x1, y1) for mask bit 2.  Rows at or
+    past off[B] are ignored.  Nothing is read: the workspace goes to ragged_select_write of the same input."""
+    rows, F = points.shape
+    B = off.numel() - 1
+    r = _range_xy(range_xy)
+    if new_off is None:
+        new_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
+    need = int(lib().hvpr_ragged_select_workspace_bytes(rows, B))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=points.device)
+    check(lib().hvpr_ragged_select_count_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
+                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
+                                             _ptr(new_off, torch.int32, "new_off"), workspace.data_ptr(), workspace.numel(),
+                                             _stream()), "hvpr_ragged_select_count_f32")
+    return new_off, workspace
+
+
+def ragged_select_write(points, off, mask, new_off, workspace, calib=None, range_xy=None, inv_perm=None, batch_column=False,
+                        out=None, flag=None):
+    """(out, flag).  `out` (capacity, F + batch_column) float32: the kept rows, stable, each at its flat rank or, with the flat
+    int32 `inv_perm`, at new_off[b] + inv_perm[rank]; `flag` (1,) int32 is set when a row had to be dropped (an inv_perm entry
+    outside its frame, an output too small).  Without `out` the output is sized by the input rows: no read is needed."""
+    rows, F = points.shape
+    B = off.numel() - 1
+    r = _range_xy(range_xy)
+    if out is None:
+        out = torch.empty((rows, F + (1 if batch_column else 0)), dtype=torch.float32, device=points.device)
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=points.device)
+    check(lib().hvpr_ragged_select_write_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
+                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
+                                             _ptr(new_off, torch.int32, "new_off"), _ptr(inv_perm, torch.int32, "inv_perm"),
+                                             0 if inv_perm is None else inv_perm.numel(), int(bool(batch_column)),
+                                             _ptr(out, torch.float32, "out"), out.shape[0], _ptr(flag, torch.int32, "flag"),
+                                             workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_ragged_select_write_f32")
+    return out, flag

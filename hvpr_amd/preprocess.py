@@ -79,6 +79,14 @@ def gather_rows(rows, idx):
     return out
 
 
+def shuffle_points(points, rng=np.random):
+    """DataProcessor.shuffle_points (data_processor.py:32-39) for one frame: points[rng.permutation(N)], the permutation drawn
+    on the host as the reference draws it, the rows gathered on the device.  (A whole batch at once, fused with the range mask
+    and the collation: hvpr_amd.batch_loader.DeviceBatchLoader.)"""
+    perm = rng.permutation(points.shape[0])
+    return gather_rows(points, torch.from_numpy(np.ascontiguousarray(perm).astype(np.int32)).to(points.device))
+
+
 def sample_points_choice(near, num_points, rng=np.random):
     """Index selection of DataProcessor.sample_points (data_processor.py:77-108): same RNG call sequence, including the
     draw at :91 that happens before the size test (so, like the reference, this raises ValueError when more than

@@ -796,6 +796,44 @@ int hvpr_gt_database_extract_f32(const float *points, long long n_points, int po
                                  const int32_t *obj_count, int32_t *obj_off, float *arena, long long arena_capacity,
                                  void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * f7  Training batches on the device: ragged select / shuffle / collate, a whole batch per call (get_fov_flag,
+ *     mask_points_by_range, shuffle_points and the `points` branch of collate_batch).  The frames lie end to end in `points`
+ *     [rows, point_floats] f32 (3 <= point_floats <= 64, x y z first) with DEVICE-resident offsets `off` [n_frames + 1] i32,
+ *     ascending; rows at or past off[n_frames] are capacity and are ignored, and an offset outside [0, rows] is clamped into
+ *     it, so no row outside the array is ever read.  n_frames <= 1024, rows are 32-bit offsets (else HVPR_ERR_UNSUPPORTED).
+ *     `mask` picks the decision: bit 1 (value 1) the FOV test with the frame's row of `calib` [n_frames, 26] f32 on the device
+ *     (the layout of eval_loop.pack_calib: V2C^T R0^T 4x3, P2 3x4, image height, image width), bit 2 (value 2) the x/y range
+ *     `range_xy` (4 HOST floats x0 y0 x1 y1, both ends inclusive); both bits: the AND; 0 keeps every row in front of off[B].
+ *     The fp32 operations are those of hvpr_point_flags_f32 mode 0 in their order (one shared expression): the same decisions.
+ *     Every check is made on the host: a refused call returns HVPR_ERR_INVALID_ARG / HVPR_ERR_UNSUPPORTED /
+ *     HVPR_ERR_WORKSPACE and launches nothing.  No entry point synchronises or reads the device.
+ *     hvpr_ragged_select_count_f32  new_off [n_frames + 1] i32: new_off[b] = kept rows in front of off[b] (new_off[0] = 0), the
+ *                           offsets of the compacted batch.  Per-tile counts and their prefix stay in `workspace` for the
+ *                           write call of the SAME input.  Usable alone.
+ *     hvpr_ragged_select_write_f32  the kept rows, stable.  The kept row of flat rank r (0-based among all kept rows) in frame b
+ *                           goes to output row r, or with `inv_perm` [n_perm] i32 (flat, indexed by r) to row
+ *                           new_off[b] + inv_perm[r]: out[new_off[b] + i] = compacted_b[perm_b[i]] for inv_perm = the
+ *                           inverse of perm_b.  batch_column != 0 writes (float)b in front of the row: `out` is
+ *                           [out_capacity, point_floats + 1], else [out_capacity, point_floats].  A row whose inv_perm
+ *                           entry is outside [0, new_off[b+1] - new_off[b]), whose rank is at or past n_perm, or whose
+ *                           destination is at or past out_capacity is dropped and sets *flag = 1 (a device word the caller
+ *                           zeroes): nothing is ever written outside `out`.
+ *     Count pass, one-workgroup scan, write pass: no atomics, stable, bit-reproducible.
+ *     hvpr_ragged_select_workspace_bytes  for an array of `rows` rows and n_frames frames.  Needs no GPU.
+ *     hvpr_ragged_select_tile_rows  rows per workgroup of the count / write passes (tests put frame sizes around it).
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_ragged_select_tile_rows(void);
+size_t hvpr_ragged_select_workspace_bytes(long long rows, int n_frames);
+int hvpr_ragged_select_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                 int mask, const float *calib, const float *range_xy, int32_t *new_off, void *workspace,
+                                 size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_ragged_select_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                 int mask, const float *calib, const float *range_xy, const int32_t *new_off,
+                                 const int32_t *inv_perm, long long n_perm, int batch_column, float *out,
+                                 long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
+                                 hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
