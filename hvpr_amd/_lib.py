@@ -127,6 +127,10 @@ SIGNATURES = {
     "hvpr_ragged_select_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "hvpr_ragged_select_write_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _P, _P, _c.c_longlong, _I, _P, _c.c_longlong,
                                           _P, _P, _Z, _P]),
+    "hvpr_ragged_sample_workspace_bytes": (_Z, [_c.c_longlong, _I]),
+    "hvpr_ragged_sample_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "hvpr_ragged_sample_write_f32": (_I, [_P, _c.c_longlong, _I, _P, _I, _I, _P, _P, _F, _P, _P, _P, _P, _c.c_longlong, _I, _I, _P,
+                                          _c.c_longlong, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -15,6 +15,8 @@
 //   scan         one workgroup: exclusive prefix of the tile counts; new_off[b] = prefix of off[b]'s tile + that partial count
 //   write pass   recomputes the decisions, places each kept row by its flat rank
 // No atomics, no flag array, no spin-waits: bit-reproducible.
+// hvpr_ragged_sample_*: the same three passes with DataProcessor.sample_points (data_processor.py:77-108) between the mask and
+// the shuffle, see below.
 #include "common.h"
 #include "point_pred.h"
 
@@ -123,11 +125,11 @@ __global__ void __launch_bounds__(kThreads) k_select_count(SelArgs a, int *__res
     }
 }
 
-// one workgroup: tile_first[t] = kept rows in front of tile t, tile_first[tiles] = all; then the new offsets
-__global__ void __launch_bounds__(kThreads) k_select_scan(const int *__restrict__ off, int B, int rows, int tiles,
-                                                          const int *__restrict__ tile_count, int *__restrict__ tile_first,
-                                                          const int *__restrict__ partial, int *__restrict__ new_off) {
-    __shared__ int s_w[kWaves];
+// one workgroup: tile_first[t] = counted rows in front of tile t, tile_first[tiles] = all; then the new offsets.  Shared by the
+// scans of the select and of the sample count pass; ends with the workgroup's writes made.
+__device__ __forceinline__ void scan_counts(const int *__restrict__ off, int B, int rows, int tiles,
+                                            const int *__restrict__ tile_count, int *__restrict__ tile_first,
+                                            const int *__restrict__ partial, int *__restrict__ new_off, int *s_w) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     int carry = 0;
     for (int c0 = 0; c0 < tiles; c0 += kThreads) {
@@ -150,6 +152,29 @@ __global__ void __launch_bounds__(kThreads) k_select_scan(const int *__restrict_
         if (tiles == 0) { new_off[b] = 0; continue; }
         const int o = min(max(off[b], 0), rows);
         new_off[b] = tile_first[min(o / kTile, tiles - 1)] + partial[b];
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_select_scan(const int *__restrict__ off, int B, int rows, int tiles,
+                                                          const int *__restrict__ tile_count, int *__restrict__ tile_first,
+                                                          const int *__restrict__ partial, int *__restrict__ new_off) {
+    __shared__ int s_w[kWaves];
+    scan_counts(off, B, rows, tiles, tile_count, tile_first, partial, new_off, s_w);
+}
+
+// a kept row to its place in the output: (float)b in front when the batch column is on, one 16-byte store where it can be
+template <bool VEC4>
+__device__ __forceinline__ void store_row(float *o, int batch_column, int b, const float4 &v, const float *src, int F) {
+    if (batch_column) *o++ = (float)b;
+    if (VEC4) {
+        if (!batch_column) {
+            *reinterpret_cast<float4 *>(o) = v;
+        } else {
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+        }
+    } else {
+        o[0] = v.x; o[1] = v.y; o[2] = v.z;
+        for (int j = 3; j < F; ++j) o[j] = src[j];
     }
 }
 
@@ -211,19 +236,8 @@ __global__ void __launch_bounds__(kThreads) k_select_write(SelArgs a, const int 
             d = (long long)first + q;
         }
         if (d < 0 || d >= out_capacity) { *flag = 1; continue; }
-        float *o = out + (size_t)d * W;
-        if (batch_column) *o++ = (float)b;
-        if (VEC4) {
-            if (!batch_column) {
-                *reinterpret_cast<float4 *>(o) = v[k];
-            } else {
-                o[0] = v[k].x; o[1] = v[k].y; o[2] = v[k].z; o[3] = v[k].w;
-            }
-        } else {
-            const float *p = a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F;
-            o[0] = v[k].x; o[1] = v[k].y; o[2] = v[k].z;
-            for (int j = 3; j < a.F; ++j) o[j] = p[j];
-        }
+        store_row<VEC4>(out + (size_t)d * W, batch_column, b, v[k],
+                        a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F, a.F);
     }
 }
 
@@ -256,7 +270,228 @@ int check_args(const float *points, long long rows, int F, const int32_t *off, i
     return HVPR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ sample_points, a whole batch
+// DataProcessor.sample_points (data_processor.py:77-108) behind the range mask.  Its draws depend on a frame only through the
+// count n of kept rows and the count c of kept rows that are near (||xyz|| < 40, hvpr_pred_near): the host draws over ordinals
+// from those two counts and hands back, for every kept row, the output rows it goes to.  So the count pass takes a second
+// ballot (kept AND near) next to the first and the scan yields near_off next to new_off; the write pass recomputes both
+// decisions, derives the row's ordinal from the two ranks and scatters it through the destination table.
+
+struct TwoCounts {                              // begins with the layout of carve(): the select write pass can read it too
+    int *count[2], *first[2], *partial[2];      // 0: kept rows, 1: kept and near rows
+    size_t bytes;
+};
+
+TwoCounts carve_two(void *ws, int tiles, int B) {
+    hvpr_carver c(ws);
+    TwoCounts r;
+    for (int j = 0; j < 2; ++j) {
+        r.count[j] = c.take<int>((size_t)tiles + 1);
+        r.first[j] = c.take<int>((size_t)tiles + 1);
+        r.partial[j] = c.take<int>((size_t)B + 1);
+    }
+    r.bytes = c.off;
+    return r;
+}
+
+__global__ void __launch_bounds__(kThreads) k_sample_count(SelArgs a, float near, int *__restrict__ tile_count,
+                                                           int *__restrict__ partial, int *__restrict__ tile_near,
+                                                           int *__restrict__ partial_near) {
+    __shared__ Staged s;
+    __shared__ unsigned long long s_bal[kGroups], s_nbal[kGroups];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int tile_base = blockIdx.x * kTile;
+    stage(a, s, tile_base);
+    const int lo = s.off[0], hi = s.off[a.B];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const int row = tile_base + (wid * kItems + k) * 64 + lane;
+        bool f = false, g = false;
+        if (row >= lo && row < hi) {
+            const float *p = a.pts + (size_t)row * a.F;
+            const float x = p[0], y = p[1], z = p[2];
+            f = decide(a, s, frame_of(s.off, a.B, row), x, y, z);
+            g = f && hvpr_pred_near(x, y, z, near);
+        }
+        const unsigned long long bal = __ballot(f), nbal = __ballot(g);
+        if (lane == 0) { s_bal[wid * kItems + k] = bal; s_nbal[wid * kItems + k] = nbal; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0, n = 0;
+#pragma unroll
+        for (int g = 0; g < kGroups; ++g) { c += __popcll(s_bal[g]); n += __popcll(s_nbal[g]); }
+        tile_count[blockIdx.x] = c;
+        tile_near[blockIdx.x] = n;
+    }
+    for (int b = threadIdx.x; b <= a.B; b += kThreads) {
+        const int o = s.off[b];
+        if (min(o / kTile, a.tiles - 1) != (int)blockIdx.x) continue;
+        const int local = o - tile_base, g_end = local >> 6;           // 0 .. kTile
+        int c = 0, n = 0;
+        for (int g = 0; g < g_end; ++g) { c += __popcll(s_bal[g]); n += __popcll(s_nbal[g]); }
+        if (g_end < kGroups) {
+            const unsigned long long m = (1ull << (local & 63)) - 1ull;
+            c += __popcll(s_bal[g_end] & m);
+            n += __popcll(s_nbal[g_end] & m);
+        }
+        partial[b] = c;
+        partial_near[b] = n;
+    }
+}
+
+// scan_counts for both counts in turn, one workgroup
+__global__ void __launch_bounds__(kThreads) k_sample_scan(const int *__restrict__ off, int B, int rows, int tiles, TwoCounts w,
+                                                          int *__restrict__ new_off, int *__restrict__ near_off) {
+    __shared__ int s_w[kWaves];
+    scan_counts(off, B, rows, tiles, w.count[0], w.first[0], w.partial[0], new_off, s_w);
+    __syncthreads();
+    scan_counts(off, B, rows, tiles, w.count[1], w.first[1], w.partial[1], near_off, s_w);
+}
+
+struct SampleArgs {
+    const int *new_off, *near_off, *mode, *dest;
+    const int *tile_first, *tile_near_first;
+    long long n_dest, out_capacity;
+    float near;
+    int P, batch_column;
+};
+
+template <bool VEC4>
+__global__ void __launch_bounds__(kThreads) k_sample_write(SelArgs a, SampleArgs q, float *__restrict__ out, int *__restrict__ flag) {
+    __shared__ Staged s;
+    __shared__ int s_noff[kMaxFrames + 1], s_near[kMaxFrames + 1];
+    __shared__ int s_w[kWaves], s_wn[kWaves];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int tile_base = blockIdx.x * kTile;
+    for (int i = threadIdx.x; i <= a.B; i += kThreads) { s_noff[i] = q.new_off[i]; s_near[i] = q.near_off[i]; }
+    stage(a, s, tile_base);
+    const int lo = s.off[0], hi = s.off[a.B];
+    unsigned long long bal[kItems], nbal[kItems];
+    int frame[kItems];
+    bool keep[kItems], isnear[kItems];
+    float4 v[kItems];
+    int total = 0, ntotal = 0;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const int row = tile_base + (wid * kItems + k) * 64 + lane;
+        keep[k] = isnear[k] = false;
+        frame[k] = 0;
+        v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row >= lo && row < hi) {
+            if (VEC4) {
+                v[k] = *reinterpret_cast<const float4 *>(a.pts + (size_t)row * 4);       // one 16-byte access per lane
+            } else {
+                const float *p = a.pts + (size_t)row * a.F;
+                v[k].x = p[0]; v[k].y = p[1]; v[k].z = p[2];
+            }
+            frame[k] = frame_of(s.off, a.B, row);
+            keep[k] = decide(a, s, frame[k], v[k].x, v[k].y, v[k].z);
+            isnear[k] = keep[k] && hvpr_pred_near(v[k].x, v[k].y, v[k].z, q.near);
+        }
+        bal[k] = __ballot(keep[k]);
+        nbal[k] = __ballot(isnear[k]);
+        total += __popcll(bal[k]);
+        ntotal += __popcll(nbal[k]);
+    }
+    if (lane == 0) { s_w[wid] = total; s_wn[wid] = ntotal; }
+    __syncthreads();
+    long long pos = q.tile_first[blockIdx.x], npos = q.tile_near_first[blockIdx.x];
+    for (int w = 0; w < wid; ++w) { pos += s_w[w]; npos += s_wn[w]; }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int W = a.F + (q.batch_column ? 1 : 0);
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const long long rank = pos + __popcll(bal[k] & below), nrank = npos + __popcll(nbal[k] & below);
+        pos += __popcll(bal[k]);
+        npos += __popcll(nbal[k]);
+        if (!keep[k]) continue;
+        const int b = frame[k];
+        const long long first = s_noff[b], n_b = s_noff[b + 1] - first;
+        const long long r = rank - first, an = nrank - s_near[b], c_b = s_near[b + 1] - s_near[b];
+        const int mode = q.mode[b];
+        long long src = r;                                               // mode 0: the in-frame rank
+        if (mode == 1) src = isnear[k] ? an : c_b + (r - an);           // mode 1: near ordinals first, then the far ones
+        const long long t = first + src;
+        if ((mode != 0 && mode != 1) || src < 0 || src >= n_b || t < 0 || t >= q.n_dest) { *flag = 1; continue; }
+        const int2 d2 = *reinterpret_cast<const int2 *>(q.dest + 2 * t);
+        const int dd[2] = {d2.x, d2.y};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int d = dd[e];
+            if (d == -1) continue;
+            if (d < -1 || d >= q.P) { *flag = 1; continue; }
+            const long long at = (long long)b * q.P + d;
+            if (at >= q.out_capacity) { *flag = 1; continue; }           // never outside `out`
+            store_row<VEC4>(out + (size_t)at * W, q.batch_column, b, v[k],
+                            a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F, a.F);
+        }
+    }
+}
+
+int check_sample_args(const float *points, long long rows, int F, const int32_t *off, int B, int mask, const float *calib,
+                      const float *range_xy, float near, void *workspace, size_t workspace_bytes, SelArgs *a) {
+    // check_args' own size test is for the smaller layout of the select calls: the size is tested below
+    const int st = check_args(points, rows, F, off, B, mask, calib, range_xy, workspace, (size_t)-1, a);
+    if (st != HVPR_OK) return st;
+    if (!(near >= 0.f)) return HVPR_ERR_INVALID_ARG;
+    if (workspace_bytes < hvpr_ragged_sample_workspace_bytes(rows, B)) return HVPR_ERR_WORKSPACE;
+    return HVPR_OK;
+}
+
 }  // namespace
+
+extern "C" size_t hvpr_ragged_sample_workspace_bytes(long long rows, int n_frames) {
+    if (rows < 0 || n_frames < 1) return 0;
+    return carve_two(nullptr, hvpr_cdiv(rows, kTile), n_frames).bytes;
+}
+
+extern "C" int hvpr_ragged_sample_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, float near, int32_t *new_off,
+                                            int32_t *near_off, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_sample_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace,
+                                     workspace_bytes, &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off || !near_off) return HVPR_ERR_INVALID_ARG;
+    const TwoCounts w = carve_two(workspace, a.tiles, n_frames);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.tiles > 0)
+        hipLaunchKernelGGL(k_sample_count, dim3(a.tiles), dim3(kThreads), 0, s, a, near, w.count[0], w.partial[0], w.count[1],
+                           w.partial[1]);
+    hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kThreads), 0, s, off, n_frames, a.rows, a.tiles, w, new_off, near_off);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_ragged_sample_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, float near,
+                                            const int32_t *new_off, const int32_t *near_off, const int32_t *mode,
+                                            const int32_t *dest, long long n_dest, int num_points, int batch_column, float *out,
+                                            long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
+                                            hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_sample_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace,
+                                     workspace_bytes, &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off || !near_off || !mode || !flag || out_capacity < 0 || n_dest < 0 || num_points < 0) return HVPR_ERR_INVALID_ARG;
+    if ((out_capacity > 0 && !out) || (n_dest > 0 && !dest) || ((uintptr_t)dest & 7) != 0) return HVPR_ERR_INVALID_ARG;
+    if (out_capacity > 0x7fffffffLL || n_dest > 0x3fffffffLL) return HVPR_ERR_UNSUPPORTED;
+    if (a.tiles == 0) return HVPR_OK;
+    const TwoCounts w = carve_two(workspace, a.tiles, n_frames);
+    SampleArgs q;
+    q.new_off = new_off; q.near_off = near_off; q.mode = mode; q.dest = dest;
+    q.tile_first = w.first[0]; q.tile_near_first = w.first[1];
+    q.n_dest = n_dest; q.out_capacity = out_capacity; q.near = near; q.P = num_points; q.batch_column = batch_column ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec4 = point_floats == 4 && ((uintptr_t)points & 15) == 0 && (batch_column || ((uintptr_t)out & 15) == 0);
+    if (vec4)
+        hipLaunchKernelGGL(k_sample_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, q, out, flag);
+    else
+        hipLaunchKernelGGL(k_sample_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, q, out, flag);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
 
 extern "C" int hvpr_ragged_select_tile_rows(void) { return kTile; }
 

@@ -4,6 +4,7 @@
 //   mask_points_by_range    pcdet/utils/common_utils.py:59-62 (x and y only, both ends inclusive)
 //   FOV                     KittiDataset.get_fov_flag, pcdet/datasets/kitti/kitti_dataset.py:100-116 over
 //                           Calibration.lidar_to_rect / rect_to_img, pcdet/utils/calibration_kitti.py:65-84 (all float32)
+//   near flag               DataProcessor.sample_points, pcdet/datasets/processor/data_processor.py:87-88
 // Both including files are compiled with -ffp-contract=off: no product below may fuse with its sum.
 #pragma once
 
@@ -14,6 +15,11 @@ __device__ __forceinline__ float hvpr_dot4(float x, float y, float z, const floa
 
 __device__ __forceinline__ bool hvpr_pred_range_xy(float x, float y, float x0, float y0, float x1, float y1) {
     return x >= x0 && x <= x1 && y >= y0 && y <= y1;
+}
+
+// the near flag of DataProcessor.sample_points, data_processor.py:87-88: ||xyz||_2 < near, the squares summed left to right
+__device__ __forceinline__ bool hvpr_pred_near(float x, float y, float z, float near) {
+    return __fsqrt_rn((x * x + y * y) + z * z) < near;
 }
 
 // a: (V2C^T R0^T), rect_j = sum_i hom_i * a[i*3 + j];  p: P2^T, img_j = sum_i rhom_i * p[i*3 + j]

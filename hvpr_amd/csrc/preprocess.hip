@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(kThreads) k_point_flags(const float *__restric
         f = hvpr_pred_range_xy(x, y, x0, y0, x1, y1);
         if (f && fov.enabled) f = hvpr_pred_fov(x, y, z, fov.a, fov.p, fov.img_h, fov.img_w);
     } else {
-        f = __fsqrt_rn((x * x + y * y) + z * z) < near_thresh;
+        f = hvpr_pred_near(x, y, z, near_thresh);
     }
     flags[i] = f ? 1 : 0;
 }

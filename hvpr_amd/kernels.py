@@ -1116,3 +1116,50 @@ def ragged_select_write(points, off, mask, new_off, workspace, calib=None, range
                                              _ptr(out, torch.float32, "out"), out.shape[0], _ptr(flag, torch.int32, "flag"),
                                              workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_ragged_select_write_f32")
     return out, flag
+
+
+def ragged_sample_count(points, off, mask, calib=None, range_xy=None, near=40.0, new_off=None, near_off=None, workspace=None):
+    """(new_off, near_off, workspace): ragged_select_count with the second count sample_points needs.  near_off[b] = kept rows in
+    front of off[b] with ||xyz|| < near.  Nothing is read: the workspace goes to ragged_sample_write of the same input."""
+    rows, F = points.shape
+    B = off.numel() - 1
+    r = _range_xy(range_xy)
+    if new_off is None:
+        new_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
+    if near_off is None:
+        near_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
+    need = int(lib().hvpr_ragged_sample_workspace_bytes(rows, B))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=points.device)
+    check(lib().hvpr_ragged_sample_count_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
+                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
+                                             float(near), _ptr(new_off, torch.int32, "new_off"),
+                                             _ptr(near_off, torch.int32, "near_off"), workspace.data_ptr(), workspace.numel(),
+                                             _stream()), "hvpr_ragged_sample_count_f32")
+    return new_off, near_off, workspace
+
+
+def ragged_sample_write(points, off, mask, new_off, near_off, mode, dest, num_points, workspace, calib=None, range_xy=None,
+                        near=40.0, batch_column=False, out=None, flag=None):
+    """(out, flag).  `out` (B * num_points, F + batch_column) float32: every kept row at out[b * num_points + d] for each of its
+    two destinations d >= 0 in `dest` (total kept, 2) int32, indexed by new_off[b] + the row's source ordinal: its in-frame rank
+    where `mode` (B,) int32 is 0, near ordinals first and far ones behind them where it is 1.  `flag` (1,) int32 is set when a
+    store had to be dropped (a destination outside [-1, num_points), a table or an output too small)."""
+    rows, F = points.shape
+    B = off.numel() - 1
+    r = _range_xy(range_xy)
+    if out is None:
+        out = torch.empty((B * int(num_points), F + (1 if batch_column else 0)), dtype=torch.float32, device=points.device)
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=points.device)
+    if mode.numel() != B or dest.dim() != 2 or dest.shape[1] != 2:
+        raise ValueError("hvpr_amd: mode must be (B,) and dest (n, 2)")
+    check(lib().hvpr_ragged_sample_write_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
+                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
+                                             float(near), _ptr(new_off, torch.int32, "new_off"),
+                                             _ptr(near_off, torch.int32, "near_off"), _ptr(mode, torch.int32, "mode"),
+                                             _ptr(dest, torch.int32, "dest"), dest.shape[0], int(num_points),
+                                             int(bool(batch_column)), _ptr(out, torch.float32, "out"), out.shape[0],
+                                             _ptr(flag, torch.int32, "flag"), workspace.data_ptr(), workspace.numel(), _stream()),
+          "hvpr_ragged_sample_write_f32")
+    return out, flag

@@ -834,6 +834,38 @@ int hvpr_ragged_select_write_f32(const float *points, long long rows, int point_
                                  long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
                                  hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * f7b DataProcessor.sample_points for a whole batch, fused into the select / shuffle / collate above (same input layout, same
+ *     `mask`, same limits and refusals).  The reference's draws depend on a frame only through n, its kept rows, and c, its
+ *     kept rows with ||xyz||_2 < `near` (the expression of hvpr_point_flags_f32 mode 1, one shared copy; near >= 0): the host
+ *     reads both counts, draws over ordinals and hands back where every kept row goes.
+ *     hvpr_ragged_sample_count_f32  new_off as hvpr_ragged_select_count_f32 gives it, bit for bit, and near_off
+ *                           [n_frames + 1] i32: near_off[b] = kept-and-near rows in front of off[b].  Per-tile counts and
+ *                           prefixes of both stay in `workspace` for the write call of the SAME input.
+ *     hvpr_ragged_sample_write_f32  for a kept row of frame b with in-frame rank r (among the frame's kept rows) and near
+ *                           ordinal a (kept-and-near rows of the frame in front of it), c = the frame's near count: the
+ *                           source ordinal s is r when mode[b] == 0; when mode[b] == 1 it is a for a near row and
+ *                           c + (r - a) for a far one (near ordinals first, then the far ones, both ascending).  `mode`
+ *                           [n_frames] i32 and `dest` [n_dest, 2] i32 (8-byte aligned) are on the device; the row's two
+ *                           destinations are dest[new_off[b] + s][0..1], -1 for none, and for each d >= 0 the row is stored
+ *                           at out[b * num_points + d], with (float)b in front when batch_column != 0.  A destination
+ *                           outside [-1, num_points), a table index at or past n_dest, an output row at or past
+ *                           out_capacity or a mode other than 0 / 1 drops the store and sets *flag = 1 (a device word the
+ *                           caller zeroes): nothing is ever written outside `out`.  Output rows no entry names stay as
+ *                           they were.
+ *     No atomics, no flag array, no spin-waits: the same input gives the same bytes.
+ *     hvpr_ragged_sample_workspace_bytes  for both calls (twice the layout of hvpr_ragged_select_workspace_bytes).  Needs no GPU.
+ * ------------------------------------------------------------------------------------------- */
+size_t hvpr_ragged_sample_workspace_bytes(long long rows, int n_frames);
+int hvpr_ragged_sample_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                 int mask, const float *calib, const float *range_xy, float near, int32_t *new_off,
+                                 int32_t *near_off, void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+int hvpr_ragged_sample_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                 int mask, const float *calib, const float *range_xy, float near, const int32_t *new_off,
+                                 const int32_t *near_off, const int32_t *mode, const int32_t *dest, long long n_dest,
+                                 int num_points, int batch_column, float *out, long long out_capacity, int32_t *flag,
+                                 void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,13 @@ the algorithm needs: count pass rows * 16 read; write pass rows * 16 + kept * 4 
 "compact, then gather" (write pass without inv_perm + hvpr_gather_rows_f32 over the flat permutation) next to "scatter the
 stores" (write pass with inv_perm).
 
-    python tools/bench_batch_loader.py [--batch 16] [--bank-scale 0.1]
+With --sample-points P (off by default, the default output is unchanged) `sample_points` with NUM_POINTS P stands between the
+range mask and the shuffle on both legs (chain: PointPreprocessor.sample_points per frame, one more read each; loader:
+sample_points=True, still 2 reads), and the line gains `sample_points`: the count pass with the second ballot and the write
+pass through the destination table, timed alone against the count pass and the inv_perm write pass over the same kept rows, and
+"compact, then gather the B * P chosen rows" next to it.
+
+    python tools/bench_batch_loader.py [--batch 16] [--bank-scale 0.1] [--sample-points 16384]
 Prints ONE JSON line."""
 import argparse
 import json
@@ -37,7 +43,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_augment import CLASSES, RANGE, SIZES, synthetic_bank  # noqa: E402
 from hvpr_amd import kernels, preprocess, synthetic  # noqa: E402
 from hvpr_amd.augment import DeviceAugmentor  # noqa: E402
-from hvpr_amd.batch_loader import DeviceBatchLoader  # noqa: E402
+from hvpr_amd.batch_loader import DeviceBatchLoader, plan_sample_points, sample_destinations  # noqa: E402
 from hvpr_amd.config import cfg_from_yaml_file  # noqa: E402
 
 HBM_ACHIEVABLE = 6.3e12
@@ -98,6 +104,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--n-az", type=int, default=1900)
+    ap.add_argument("--sample-points", type=int, default=0, help="NUM_POINTS of a sample_points step on both legs (0: none)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_batch_loader: needs the GPU (there is no CPU path to time)")
@@ -106,6 +113,9 @@ def main():
     cfg = cfg_from_yaml_file(os.path.join(base, "dataset_configs", "kitti_dataset.yaml"))
     cfg["DATA_AUGMENTOR"] = cfg_from_yaml_file(os.path.join(base, "dataset_configs", "kitti_augmentor.yaml"))["DATA_AUGMENTOR_3CLASS"]
     cfg["DATA_AUGMENTOR"]["AUG_CONFIG_LIST"][0]["USE_ROAD_PLANE"] = False
+    P = a.sample_points
+    if P:
+        cfg["DATA_PROCESSOR"].insert(1, {"NAME": "sample_points", "NUM_POINTS": {"train": P, "test": P}})
     bank = synthetic_bank(a.bank_scale, rng)
     bank.on_device()
     B = a.batch
@@ -116,7 +126,8 @@ def main():
         g[:, 3:6], g[:, 6] = SIZES["Car"], rng.uniform(-np.pi, np.pi, 8)
         frames.append({"points": torch.from_numpy(synthetic.kitti_like_frame(100 + b, n_az=a.n_az)).cuda(), "gt_boxes": g,
                        "gt_names": np.array(["Car"] * 8), "calib": CALIB, "image_shape": SHAPE, "frame_id": str(b)})
-    loader = DeviceBatchLoader(cfg, CLASSES, lambda i: frames[i], B, bank=bank, training=True)
+    loader = DeviceBatchLoader(cfg, CLASSES, lambda i: frames[i], B, bank=bank, training=True, sample_points=bool(P))
+    sampler = preprocess.PointPreprocessor(RANGE, num_points=P, training=True) if P else None
     aug = DeviceAugmentor(cfg["DATA_AUGMENTOR"], CLASSES, bank, RANGE)
     pp = preprocess.PointPreprocessor(RANGE, num_points=-1, training=True)
     keep = {}
@@ -131,6 +142,8 @@ def main():
         parts = []
         for b in range(B):
             p = pp.mask_points_and_boxes_outside_range(out["points"][off[b]: off[b + 1]])
+            if sampler is not None:
+                p = sampler.sample_points(p, r)
             p = preprocess.shuffle_points(p, r)
             parts.append(torch.cat([torch.full((p.shape[0], 1), float(b), device=p.device), p], dim=1))
         keep["chain"] = (torch.cat(parts), out["gt_boxes"])
@@ -179,11 +192,46 @@ def main():
     bytes_count = live * F * 4
     bytes_write = live * F * 4 + m * 4 + m * (F + 1) * 4
 
+    sampled = None
+    if P:
+        n_off, c_off, ws2 = kernels.ragged_sample_count(pts, off, 2, range_xy=loader.range_xy)
+        table, modes, order = np.empty((m, 2), np.int32), np.empty((B,), np.int32), []
+        for b in range(B):
+            s, e = int(st["new_off"][b]), int(st["new_off"][b + 1])
+            plan = plan_sample_points(e - s, int(st["near_off"][b + 1] - st["near_off"][b]), P, np.random.RandomState(b), shuffle=True)
+            table[s:e], modes[b] = sample_destinations(plan["order"], e - s), plan["mode"]
+            order.append(plan["order"])
+        t0 = time.perf_counter()
+        for b in range(B):
+            s, e = int(st["new_off"][b]), int(st["new_off"][b + 1])
+            sample_destinations(plan_sample_points(e - s, int(st["near_off"][b + 1] - st["near_off"][b]), P, np.random.RandomState(b),
+                                                   shuffle=True)["order"], e - s)
+        plan_ms = (time.perf_counter() - t0) * 1e3
+        table_d, modes_d = torch.from_numpy(table).cuda(), torch.from_numpy(modes).cuda()
+        outp = torch.empty((B * P, F + 1), dtype=torch.float32, device=pts.device)
+        # "compact, then gather": the chosen rows by their flat compacted index (mode 0 frames only know it without the flags;
+        # the timing does not depend on which rows are named)
+        flat = torch.from_numpy(np.concatenate([int(st["new_off"][b]) + order[b] for b in range(B)]).astype(np.int32)).cuda()
+        ms_count2 = kernel_ms(lambda: kernels.ragged_sample_count(pts, off, 2, range_xy=loader.range_xy, new_off=n_off, near_off=c_off,
+                                                                  workspace=ws2), a.reps)
+        ms_write2 = kernel_ms(lambda: kernels.ragged_sample_write(pts, off, 2, n_off, c_off, modes_d, table_d, P, ws2,
+                                                                  range_xy=loader.range_xy, batch_column=True, out=outp, flag=flag),
+                              a.reps)
+        ms_gather2 = kernel_ms(lambda: preprocess.gather_rows(out4[:m], flat), a.reps)
+        bytes_write2 = live * F * 4 + m * 8 + B * P * (F + 1) * 4
+        sampled = {"num_points": P, "rows_out": B * P, "host_plan_ms": round(plan_ms, 3),
+                   "count_pass": {"ms": round(ms_count2, 5), "against_select_count_ms": round(ms_count, 5)},
+                   "write_pass_table": {"ms": round(ms_write2, 5), "against_inv_perm_write_ms": round(ms_scatter, 5),
+                                        "bytes": int(bytes_write2), "tb_per_s": round(bytes_write2 / ms_write2 / 1e9, 3),
+                                        "share_of_achievable_hbm": round(bytes_write2 / (ms_write2 * 1e-3) / HBM_ACHIEVABLE, 3)},
+                   "compact_then_gather": {"compact_ms": round(ms_compact, 5), "gather_ms": round(ms_gather2, 5),
+                                           "ms": round(ms_compact + ms_gather2, 5), "note": "without the batch column"}}
+
     def leg(t):
         return {"event_ms_median": pct(t[:, 0], 50), "event_ms_p10": pct(t[:, 0], 10), "event_ms_p90": pct(t[:, 0], 90),
                 "wall_ms_median": pct(t[:, 1], 50), "sync_calls": int(np.median(t[:, 2]))}
 
-    print(json.dumps({
+    line = {
         "bench": "batch_loader", "batch": B, "points_in": int(sum(f["points"].shape[0] for f in frames)), "points_augmented": live,
         "points_out": kept, "bank_objects": len(bank), "iters": a.iters, "chain": leg(t_chain), "loader": leg(t_load),
         "legs_agree": agree, "permutation_draws_host_ms": round(perm_ms, 3),
@@ -193,7 +241,10 @@ def main():
         "write_pass_scatter": {"ms": round(ms_scatter, 5), "bytes": int(bytes_write), "tb_per_s": round(bytes_write / ms_scatter / 1e9, 3),
                                "share_of_achievable_hbm": round(bytes_write / (ms_scatter * 1e-3) / HBM_ACHIEVABLE, 3)},
         "compact_then_gather": {"compact_ms": round(ms_compact, 5), "gather_ms": round(ms_gather, 5),
-                                "ms": round(ms_compact + ms_gather, 5), "note": "without the batch column"}}))
+                                "ms": round(ms_compact + ms_gather, 5), "note": "without the batch column"}}
+    if sampled is not None:
+        line["sample_points"] = sampled
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":
