@@ -223,6 +223,13 @@ class DeviceBatchLoader:
         V2C, R0, P2 = eval_loop._calib_parts(c)
         return {"Tr_velo2cam": V2C, "R0": R0, "P2": P2}
 
+    @staticmethod
+    def _batch(frames, points, offsets, flag, perms):
+        """The batch dict without the boxes: the device fields as given, the host fields from the frames."""
+        return {"points": points, "point_frame_offsets": offsets, "batch_size": len(frames), "overflow": flag,
+                "frame_id": [f.get("frame_id") for f in frames], "calib": [f.get("calib") for f in frames],
+                "image_shape": [f.get("image_shape") for f in frames], "permutations": perms}
+
     def _augment_stage(self, frames, rngs):
         """FOV select, read 1, the augmentor's draws, the augment kernels, the range count, read 2: the frames as ragged
         augmented points with everything the host has to know about them."""
@@ -312,9 +319,7 @@ class DeviceBatchLoader:
         flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         kernels.ragged_select_write(points, off_dev, mask, new_off_dev, ws, calib=calib, range_xy=self.range_xy, inv_perm=inv,
                                     batch_column=True, out=out, flag=flag)
-        return {"points": out, "point_frame_offsets": new_off_dev, "batch_size": len(frames), "overflow": flag,
-                "frame_id": [f.get("frame_id") for f in frames], "calib": [f.get("calib") for f in frames],
-                "image_shape": [f.get("image_shape") for f in frames], "permutations": perms}
+        return self._batch(frames, out, new_off_dev, flag, perms)
 
     def _finish_sampled(self, frames, points, off_dev, mask, new_off_dev, near_off_dev, new_off, near_off, ws, rngs, calib=None):
         """sample_points' draws and the permutations (host), then the write pass through the destination table: every frame
@@ -337,11 +342,9 @@ class DeviceBatchLoader:
         kernels.ragged_sample_write(points, off_dev, mask, new_off_dev, near_off_dev, table[2 * total:],
                                     table[: 2 * total].view(total, 2), P, ws, calib=calib, range_xy=self.range_xy, near=NEAR,
                                     batch_column=True, out=out, flag=flag)
-        batch = {"points": out, "point_frame_offsets": self._up(np.arange(B + 1, dtype=np.int32) * P), "batch_size": B,
-                 "overflow": flag, "frame_id": [f.get("frame_id") for f in frames], "calib": [f.get("calib") for f in frames],
-                 "image_shape": [f.get("image_shape") for f in frames], "permutations": perms}
+        batch = self._batch(frames, out, self._up(np.arange(B + 1, dtype=np.int32) * P), flag, perms)
         if self.debug_choices:                                                   # the near flags of the kept rows: one more read
-            # the workspace of the sample count begins with the layout the select write reads (csrc/collate.hip, carve_two)
+            # the workspace of the sample count begins with the layout the select write reads (csrc/collate.hip, carve)
             kept, _ = kernels.ragged_select_write(points, off_dev, mask, new_off_dev, ws, calib=calib, range_xy=self.range_xy)
             near = self._read(preprocess._flags(kept[:total].contiguous(), 1, near=NEAR)) if total else np.zeros((0,), np.uint8)
             batch["choices"] = [resolve_sample_choice(p, near[int(new_off[b]): int(new_off[b + 1])]) for b, p in enumerate(plans)]
@@ -395,9 +398,7 @@ class DeviceBatchLoader:
             out, flag = kernels.ragged_select_write(points, off, mask, new_off_dev, ws, calib=calib, range_xy=self.range_xy,
                                                     batch_column=True)          # sized by the input rows: enqueued before the read
             new_off = self._read(new_off_dev)                                    # the one read
-            batch = {"points": out[: int(new_off[B])], "point_frame_offsets": new_off_dev, "batch_size": B, "overflow": flag,
-                     "frame_id": [f.get("frame_id") for f in frames], "calib": [f.get("calib") for f in frames],
-                     "image_shape": [f.get("image_shape") for f in frames], "permutations": []}
+            batch = self._batch(frames, out[: int(new_off[B])], new_off_dev, flag, [])
         else:
             new_off = self._read(new_off_dev).astype(np.int64)
             batch = self._finish(frames, points, off, mask, new_off_dev, new_off, ws, rngs, calib=calib)

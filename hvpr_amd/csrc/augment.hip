@@ -18,6 +18,7 @@
 // the configured order, four bits each (1 flip x, 2 flip y, 3 rotation, 4 scaling), 0 ends the list.
 //
 // Built with -ffp-contract=off: the fp32 operation order below is the reference's.
+#include "box_cut.h"
 #include "common.h"
 #include "iou_geom.h"
 
@@ -241,16 +242,11 @@ __global__ void __launch_bounds__(64) k_boxes(const Plan p, const int32_t *__res
 
 // ---- points ----------------------------------------------------------------------------------------------------------------------
 // The accepted candidates of the frame, enlarged by REMOVE_EXTRA_WIDTH (box_utils.enlarge_box3d), for the inside test of
-// csrc_cpu/gt_sampling.cpp:95-107.  A rejected candidate gets a negative half height: nothing is inside it.
-struct Cut { float x, y, z, hx, hy, hz, cs, sn; };
-
-__device__ __forceinline__ void load_cuts(const Plan &p, const int32_t *valid, int c0, int nC, float ex, float ey, float ez, Cut *cut) {
+// box_cut.h.  A rejected candidate gets a negative half height: nothing is inside it.
+__device__ __forceinline__ void load_cuts(const Plan &p, const int32_t *valid, int c0, int nC, float ex, float ey, float ez,
+                                          hvpr_cut *cut) {
     for (int k = threadIdx.x; k < nC; k += blockDim.x) {
-        const float *b = p.cand_box + (size_t)(c0 + k) * 7;
-        Cut c;
-        c.x = b[0]; c.y = b[1]; c.z = b[2];
-        c.hx = (b[3] + ex) / 2.0f; c.hy = (b[4] + ey) / 2.0f; c.hz = (b[5] + ez) / 2.0f;
-        c.cs = cosf(-b[6]); c.sn = sinf(-b[6]);
+        hvpr_cut c = hvpr_make_cut(p.cand_box + (size_t)(c0 + k) * 7, ex, ey, ez);
         if (!valid[c0 + k]) c.hz = -1.0f;
         cut[k] = c;
     }
@@ -275,7 +271,7 @@ __device__ __forceinline__ int block_rank(bool keep, int *wave_n, int &total) {
 __global__ void __launch_bounds__(kBlk) k_points_count(const Plan p, const int32_t *__restrict__ valid, const float *__restrict__ pts,
                                                        int F, float ex, float ey, float ez, uint8_t *__restrict__ flag,
                                                        int32_t *__restrict__ blk_cnt) {
-    __shared__ Cut cut[kFrameBoxes];
+    __shared__ hvpr_cut cut[kFrameBoxes];
     __shared__ int wave_n[kBlk / 64];
     const int f = blockIdx.y;
     const int c0 = p.grp_off[f * p.NG], nC = p.grp_off[(f + 1) * p.NG] - c0;
@@ -287,14 +283,8 @@ __global__ void __launch_bounds__(kBlk) k_points_count(const Plan p, const int32
         const float *q = pts + (size_t)(p.pt_off[f] + j) * F;
         const float x = q[0], y = q[1], z = q[2];
         keep = true;
-        for (int k = 0; k < nC; ++k) {
-            const Cut c = cut[k];
-            if (fabsf(z - c.z) <= c.hz) {
-                const float sx = x - c.x, sy = y - c.y;
-                const float lx = sx * c.cs - sy * c.sn, ly = sx * c.sn + sy * c.cs;
-                if (fabsf(lx) < c.hx && fabsf(ly) < c.hy) { keep = false; break; }
-            }
-        }
+        for (int k = 0; k < nC; ++k)
+            if (hvpr_cut_inside(cut[k], x, y, z)) { keep = false; break; }
         flag[p.pt_off[f] + j] = keep ? 1 : 0;
     }
     int total;
@@ -302,34 +292,14 @@ __global__ void __launch_bounds__(kBlk) k_points_count(const Plan p, const int32
     if (threadIdx.x == 0) blk_cnt[(size_t)f * gridDim.x + blockIdx.x] = total;
 }
 
-// exclusive prefix of get(0..n) into dst[0..n], dst[n] = the sum; one workgroup, a contiguous piece per thread
-template <typename Get>
-__device__ __forceinline__ void block_scan(Get get, int n, int32_t *dst, int *part) {
-    const int T = blockDim.x, t = threadIdx.x, per = (n + T - 1) / T;
-    const int lo = min(n, t * per), hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += get(i);
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int i = 0; i < T; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        dst[n] = run;
-    }
-    __syncthreads();
-    int run = part[t];
-    for (int i = lo; i < hi; ++i) { dst[i] = run; run += get(i); }
-    __syncthreads();
-}
-
 // pass 2: where everything goes.  Frame f's output is its accepted candidates' points in candidate order, then its kept scene
 // points in their order (database_sampler.py:150-151).
 __global__ void __launch_bounds__(256) k_points_scan(const Plan p, const int32_t *__restrict__ valid, const int32_t *__restrict__ blk_cnt,
                                                      int max_blk, int32_t *__restrict__ blk_pre, int32_t *__restrict__ cand_pre,
                                                      int32_t *__restrict__ out_off) {
-    __shared__ int part[256];
-    block_scan([&](int i) { return blk_cnt[i]; }, p.B * max_blk, blk_pre, part);
-    block_scan([&](int i) { return valid[i] ? p.cand_n[i] : 0; }, p.C, cand_pre, part);
+    __shared__ int wave_sum[256 / 64];
+    hvpr_block_scan([&](int i) { return blk_cnt[i]; }, p.B * max_blk, 0, blk_pre, true, wave_sum);
+    hvpr_block_scan([&](int i) { return valid[i] ? p.cand_n[i] : 0; }, p.C, 0, cand_pre, true, wave_sum);
     for (int f = threadIdx.x; f <= p.B; f += blockDim.x)
         out_off[f] = f < p.B ? cand_pre[p.grp_off[f * p.NG]] + blk_pre[(size_t)f * max_blk] : cand_pre[p.C] + blk_pre[(size_t)p.B * max_blk];
 }

@@ -15,8 +15,12 @@
 //   scan         one workgroup: exclusive prefix of the tile counts; new_off[b] = prefix of off[b]'s tile + that partial count
 //   write pass   recomputes the decisions, places each kept row by its flat rank
 // No atomics, no flag array, no spin-waits: bit-reproducible.
-// hvpr_ragged_sample_*: the same three passes with DataProcessor.sample_points (data_processor.py:77-108) between the mask and
-// the shuffle, see below.
+// hvpr_ragged_sample_*: the same three passes, the same code with NEAR on, with DataProcessor.sample_points
+// (data_processor.py:77-108) between the mask and the shuffle.  Its draws depend on a frame only through the count n of kept
+// rows and the count c of kept rows that are near (||xyz|| < 40, hvpr_pred_near): the host draws over ordinals from those two
+// counts and hands back, for every kept row, the output rows it goes to.  So the count pass takes a second ballot (kept AND
+// near) next to the first and the scan yields near_off next to new_off; the write pass recomputes both decisions, derives the
+// row's ordinal from the two ranks and scatters it through the destination table.
 #include "common.h"
 #include "point_pred.h"
 
@@ -37,6 +41,7 @@ struct SelArgs {
     int B, mask, tiles;
     const float *calib;
     float x0, y0, x1, y1;
+    float near;              // the sample calls' radius; 0 in the select calls, which never read it
 };
 
 struct Staged {
@@ -88,9 +93,40 @@ __device__ __forceinline__ bool decide(const SelArgs &a, const Staged &s, int b,
     return f;
 }
 
-__global__ void __launch_bounds__(kThreads) k_select_count(SelArgs a, int *__restrict__ tile_count, int *__restrict__ partial) {
+// The workspace: per count set (0: kept rows, 1: kept and near rows) the tile counts, their prefix, and per offset the count in
+// front of it inside its tile.  Set 0 of the two-set layout lies where the one-set layout lies, because it is this code: the
+// select write pass can read the workspace of a sample count pass (batch_loader.py, debug_choices, does).
+struct Carved {
+    int *count[2], *first[2], *partial[2];
+    size_t bytes;
+};
+
+Carved carve(void *ws, int tiles, int B, int sets) {
+    hvpr_carver c(ws);
+    Carved r = {};
+    for (int j = 0; j < sets; ++j) {
+        r.count[j] = c.take<int>((size_t)tiles + 1);
+        r.first[j] = c.take<int>((size_t)tiles + 1);
+        r.partial[j] = c.take<int>((size_t)B + 1);
+    }
+    r.bytes = c.off;
+    return r;
+}
+
+// set bits of the tile's ballots in front of its row `local`, 0 .. kTile
+__device__ __forceinline__ int count_before(const unsigned long long *bal, int local) {
+    const int g_end = local >> 6;
+    int c = 0;
+    for (int g = 0; g < g_end; ++g) c += __popcll(bal[g]);
+    if (g_end < kGroups) c += __popcll(bal[g_end] & ((1ull << (local & 63)) - 1ull));
+    return c;
+}
+
+template <bool NEAR>
+__global__ void __launch_bounds__(kThreads) k_count(SelArgs a, Carved w) {
+    constexpr int kSets = NEAR ? 2 : 1;
     __shared__ Staged s;
-    __shared__ unsigned long long s_bal[kGroups];
+    __shared__ unsigned long long s_bal[kSets][kGroups];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int tile_base = blockIdx.x * kTile;
     stage(a, s, tile_base);
@@ -98,68 +134,46 @@ __global__ void __launch_bounds__(kThreads) k_select_count(SelArgs a, int *__res
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
         const int row = tile_base + (wid * kItems + k) * 64 + lane;
-        bool f = false;
+        bool f = false, g = false;
         if (row >= lo && row < hi) {
             const float *p = a.pts + (size_t)row * a.F;
-            f = decide(a, s, frame_of(s.off, a.B, row), p[0], p[1], p[2]);
+            const float x = p[0], y = p[1], z = p[2];
+            f = decide(a, s, frame_of(s.off, a.B, row), x, y, z);
+            if constexpr (NEAR) g = f && hvpr_pred_near(x, y, z, a.near);
         }
         const unsigned long long bal = __ballot(f);
-        if (lane == 0) s_bal[wid * kItems + k] = bal;
+        if (lane == 0) s_bal[0][wid * kItems + k] = bal;
+        if constexpr (NEAR) {
+            const unsigned long long nbal = __ballot(g);
+            if (lane == 0) s_bal[1][wid * kItems + k] = nbal;
+        }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0;
 #pragma unroll
-        for (int g = 0; g < kGroups; ++g) c += __popcll(s_bal[g]);
-        tile_count[blockIdx.x] = c;
-    }
-    // the offsets that fall into this tile (the array's end belongs to the last tile)
-    for (int b = threadIdx.x; b <= a.B; b += kThreads) {
-        const int o = s.off[b];
-        if (min(o / kTile, a.tiles - 1) != (int)blockIdx.x) continue;
-        const int local = o - tile_base, g_end = local >> 6;           // 0 .. kTile
-        int c = 0;
-        for (int g = 0; g < g_end; ++g) c += __popcll(s_bal[g]);
-        if (g_end < kGroups) c += __popcll(s_bal[g_end] & ((1ull << (local & 63)) - 1ull));
-        partial[b] = c;
+    for (int j = 0; j < kSets; ++j) {
+        if (threadIdx.x == 0) w.count[j][blockIdx.x] = count_before(s_bal[j], kTile);
+        // the offsets that fall into this tile (the array's end belongs to the last tile)
+        for (int b = threadIdx.x; b <= a.B; b += kThreads) {
+            const int o = s.off[b];
+            if (min(o / kTile, a.tiles - 1) == (int)blockIdx.x) w.partial[j][b] = count_before(s_bal[j], o - tile_base);
+        }
     }
 }
 
-// one workgroup: tile_first[t] = counted rows in front of tile t, tile_first[tiles] = all; then the new offsets.  Shared by the
-// scans of the select and of the sample count pass; ends with the workgroup's writes made.
-__device__ __forceinline__ void scan_counts(const int *__restrict__ off, int B, int rows, int tiles,
-                                            const int *__restrict__ tile_count, int *__restrict__ tile_first,
-                                            const int *__restrict__ partial, int *__restrict__ new_off, int *s_w) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int carry = 0;
-    for (int c0 = 0; c0 < tiles; c0 += kThreads) {
-        const int t = c0 + threadIdx.x;
-        const int v = t < tiles ? tile_count[t] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-        if (lane == 63) s_w[wid] = inc;
-        __syncthreads();
-        int before = carry;
-        for (int w = 0; w < wid; ++w) before += s_w[w];
-        if (t < tiles) tile_first[t] = before + inc - v;
-        carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tile_first[tiles] = carry;
-    __syncthreads();                                                   // this workgroup's own global writes, read below
-    for (int b = threadIdx.x; b <= B; b += kThreads) {
-        if (tiles == 0) { new_off[b] = 0; continue; }
-        const int o = min(max(off[b], 0), rows);
-        new_off[b] = tile_first[min(o / kTile, tiles - 1)] + partial[b];
-    }
-}
-
-__global__ void __launch_bounds__(kThreads) k_select_scan(const int *__restrict__ off, int B, int rows, int tiles,
-                                                          const int *__restrict__ tile_count, int *__restrict__ tile_first,
-                                                          const int *__restrict__ partial, int *__restrict__ new_off) {
-    __shared__ int s_w[kWaves];
-    scan_counts(off, B, rows, tiles, tile_count, tile_first, partial, new_off, s_w);
+// one workgroup: first[t] = counted rows in front of tile t, first[tiles] = all; then the new offsets.  Per count set.
+__global__ void __launch_bounds__(kThreads) k_scan(const int *__restrict__ off, int B, int rows, int tiles, Carved w, int sets,
+                                                   int *__restrict__ new_off, int *__restrict__ near_off) {
+    __shared__ int wave_sum[kWaves];
+    const auto scan_set = [&](const int *count, int *first, const int *partial, int *out) {
+        hvpr_block_scan([&](int t) { return count[t]; }, tiles, 0, first, true, wave_sum);
+        for (int b = threadIdx.x; b <= B; b += kThreads) {
+            if (tiles == 0) { out[b] = 0; continue; }
+            const int o = min(max(off[b], 0), rows);
+            out[b] = first[min(o / kTile, tiles - 1)] + partial[b];
+        }
+    };
+    scan_set(w.count[0], w.first[0], w.partial[0], new_off);
+    if (sets == 2) scan_set(w.count[1], w.first[1], w.partial[1], near_off);
 }
 
 // a kept row to its place in the output: (float)b in front when the batch column is on, one 16-byte store where it can be
@@ -178,193 +192,16 @@ __device__ __forceinline__ void store_row(float *o, int batch_column, int b, con
     }
 }
 
-template <bool VEC4>
-__global__ void __launch_bounds__(kThreads) k_select_write(SelArgs a, const int *__restrict__ tile_first,
-                                                           const int *__restrict__ new_off, const int *__restrict__ inv_perm,
-                                                           long long n_perm, int batch_column, float *__restrict__ out,
-                                                           long long out_capacity, int *__restrict__ flag) {
+// The write pass over one tile, up to where a kept row goes: recomputes the decisions and calls
+//   place(b, src, v, isnear, rank, nrank)
+// for every kept row, with its frame, its row in a.pts, its first four floats (three without VEC4), its flat rank among the
+// kept rows and, under NEAR, whether it is near and its flat rank among the kept near rows.
+template <bool NEAR, bool VEC4, typename Place>
+__device__ __forceinline__ void walk_tile(const SelArgs &a, const Carved &w, Place place) {
     __shared__ Staged s;
-    __shared__ int s_noff[kMaxFrames + 1];
-    __shared__ int s_w[kWaves];
+    __shared__ int s_w[NEAR ? 2 : 1][kWaves];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int tile_base = blockIdx.x * kTile;
-    for (int i = threadIdx.x; i <= a.B; i += kThreads) s_noff[i] = new_off[i];
-    stage(a, s, tile_base);
-    const int lo = s.off[0], hi = s.off[a.B];
-    unsigned long long bal[kItems];
-    int frame[kItems];
-    bool keep[kItems];
-    float4 v[kItems];
-    int total = 0;
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-        const int row = tile_base + (wid * kItems + k) * 64 + lane;
-        keep[k] = false;
-        frame[k] = 0;
-        v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row >= lo && row < hi) {
-            if (VEC4) {
-                v[k] = *reinterpret_cast<const float4 *>(a.pts + (size_t)row * 4);       // one 16-byte access per lane
-            } else {
-                const float *p = a.pts + (size_t)row * a.F;
-                v[k].x = p[0]; v[k].y = p[1]; v[k].z = p[2];
-            }
-            frame[k] = frame_of(s.off, a.B, row);
-            keep[k] = decide(a, s, frame[k], v[k].x, v[k].y, v[k].z);
-        }
-        bal[k] = __ballot(keep[k]);
-        total += __popcll(bal[k]);
-    }
-    if (lane == 0) s_w[wid] = total;
-    __syncthreads();
-    long long pos = tile_first[blockIdx.x];
-    for (int w = 0; w < wid; ++w) pos += s_w[w];
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int W = a.F + (batch_column ? 1 : 0);
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-        const long long rank = pos + __popcll(bal[k] & below);
-        pos += __popcll(bal[k]);
-        if (!keep[k]) continue;
-        const int b = frame[k];
-        long long d = rank;
-        if (inv_perm) {
-            const int first = s_noff[b], m = s_noff[b + 1] - first;
-            if (rank >= n_perm) { *flag = 1; continue; }
-            const int q = inv_perm[rank];
-            if (q < 0 || q >= m) { *flag = 1; continue; }               // never a row of another frame, never out of bounds
-            d = (long long)first + q;
-        }
-        if (d < 0 || d >= out_capacity) { *flag = 1; continue; }
-        store_row<VEC4>(out + (size_t)d * W, batch_column, b, v[k],
-                        a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F, a.F);
-    }
-}
-
-struct Carved {
-    int *tile_count, *tile_first, *partial;
-    size_t bytes;
-};
-
-Carved carve(void *ws, int tiles, int B) {
-    hvpr_carver c(ws);
-    Carved r;
-    r.tile_count = c.take<int>((size_t)tiles + 1);
-    r.tile_first = c.take<int>((size_t)tiles + 1);
-    r.partial = c.take<int>((size_t)B + 1);
-    r.bytes = c.off;
-    return r;
-}
-
-int check_args(const float *points, long long rows, int F, const int32_t *off, int B, int mask, const float *calib,
-               const float *range_xy, void *workspace, size_t workspace_bytes, SelArgs *a) {
-    if (rows < 0 || F < 3 || B < 1 || mask < 0 || mask > 3 || !off || !workspace) return HVPR_ERR_INVALID_ARG;
-    if ((rows > 0 && !points) || ((mask & 1) && !calib) || ((mask & 2) && !range_xy)) return HVPR_ERR_INVALID_ARG;
-    if (B > kMaxFrames || F > 64 || rows > 0x7fffffffLL - kTile) return HVPR_ERR_UNSUPPORTED;
-    if (workspace_bytes < hvpr_ragged_select_workspace_bytes(rows, B)) return HVPR_ERR_WORKSPACE;
-    a->pts = points; a->rows = (int)rows; a->F = F; a->off = off; a->B = B; a->mask = mask;
-    a->tiles = hvpr_cdiv(rows, kTile);
-    a->calib = calib;
-    a->x0 = (mask & 2) ? range_xy[0] : 0.f; a->y0 = (mask & 2) ? range_xy[1] : 0.f;
-    a->x1 = (mask & 2) ? range_xy[2] : 0.f; a->y1 = (mask & 2) ? range_xy[3] : 0.f;
-    return HVPR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ sample_points, a whole batch
-// DataProcessor.sample_points (data_processor.py:77-108) behind the range mask.  Its draws depend on a frame only through the
-// count n of kept rows and the count c of kept rows that are near (||xyz|| < 40, hvpr_pred_near): the host draws over ordinals
-// from those two counts and hands back, for every kept row, the output rows it goes to.  So the count pass takes a second
-// ballot (kept AND near) next to the first and the scan yields near_off next to new_off; the write pass recomputes both
-// decisions, derives the row's ordinal from the two ranks and scatters it through the destination table.
-
-struct TwoCounts {                              // begins with the layout of carve(): the select write pass can read it too
-    int *count[2], *first[2], *partial[2];      // 0: kept rows, 1: kept and near rows
-    size_t bytes;
-};
-
-TwoCounts carve_two(void *ws, int tiles, int B) {
-    hvpr_carver c(ws);
-    TwoCounts r;
-    for (int j = 0; j < 2; ++j) {
-        r.count[j] = c.take<int>((size_t)tiles + 1);
-        r.first[j] = c.take<int>((size_t)tiles + 1);
-        r.partial[j] = c.take<int>((size_t)B + 1);
-    }
-    r.bytes = c.off;
-    return r;
-}
-
-__global__ void __launch_bounds__(kThreads) k_sample_count(SelArgs a, float near, int *__restrict__ tile_count,
-                                                           int *__restrict__ partial, int *__restrict__ tile_near,
-                                                           int *__restrict__ partial_near) {
-    __shared__ Staged s;
-    __shared__ unsigned long long s_bal[kGroups], s_nbal[kGroups];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int tile_base = blockIdx.x * kTile;
-    stage(a, s, tile_base);
-    const int lo = s.off[0], hi = s.off[a.B];
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-        const int row = tile_base + (wid * kItems + k) * 64 + lane;
-        bool f = false, g = false;
-        if (row >= lo && row < hi) {
-            const float *p = a.pts + (size_t)row * a.F;
-            const float x = p[0], y = p[1], z = p[2];
-            f = decide(a, s, frame_of(s.off, a.B, row), x, y, z);
-            g = f && hvpr_pred_near(x, y, z, near);
-        }
-        const unsigned long long bal = __ballot(f), nbal = __ballot(g);
-        if (lane == 0) { s_bal[wid * kItems + k] = bal; s_nbal[wid * kItems + k] = nbal; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0, n = 0;
-#pragma unroll
-        for (int g = 0; g < kGroups; ++g) { c += __popcll(s_bal[g]); n += __popcll(s_nbal[g]); }
-        tile_count[blockIdx.x] = c;
-        tile_near[blockIdx.x] = n;
-    }
-    for (int b = threadIdx.x; b <= a.B; b += kThreads) {
-        const int o = s.off[b];
-        if (min(o / kTile, a.tiles - 1) != (int)blockIdx.x) continue;
-        const int local = o - tile_base, g_end = local >> 6;           // 0 .. kTile
-        int c = 0, n = 0;
-        for (int g = 0; g < g_end; ++g) { c += __popcll(s_bal[g]); n += __popcll(s_nbal[g]); }
-        if (g_end < kGroups) {
-            const unsigned long long m = (1ull << (local & 63)) - 1ull;
-            c += __popcll(s_bal[g_end] & m);
-            n += __popcll(s_nbal[g_end] & m);
-        }
-        partial[b] = c;
-        partial_near[b] = n;
-    }
-}
-
-// scan_counts for both counts in turn, one workgroup
-__global__ void __launch_bounds__(kThreads) k_sample_scan(const int *__restrict__ off, int B, int rows, int tiles, TwoCounts w,
-                                                          int *__restrict__ new_off, int *__restrict__ near_off) {
-    __shared__ int s_w[kWaves];
-    scan_counts(off, B, rows, tiles, w.count[0], w.first[0], w.partial[0], new_off, s_w);
-    __syncthreads();
-    scan_counts(off, B, rows, tiles, w.count[1], w.first[1], w.partial[1], near_off, s_w);
-}
-
-struct SampleArgs {
-    const int *new_off, *near_off, *mode, *dest;
-    const int *tile_first, *tile_near_first;
-    long long n_dest, out_capacity;
-    float near;
-    int P, batch_column;
-};
-
-template <bool VEC4>
-__global__ void __launch_bounds__(kThreads) k_sample_write(SelArgs a, SampleArgs q, float *__restrict__ out, int *__restrict__ flag) {
-    __shared__ Staged s;
-    __shared__ int s_noff[kMaxFrames + 1], s_near[kMaxFrames + 1];
-    __shared__ int s_w[kWaves], s_wn[kWaves];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int tile_base = blockIdx.x * kTile;
-    for (int i = threadIdx.x; i <= a.B; i += kThreads) { s_noff[i] = q.new_off[i]; s_near[i] = q.near_off[i]; }
     stage(a, s, tile_base);
     const int lo = s.off[0], hi = s.off[a.B];
     unsigned long long bal[kItems], nbal[kItems];
@@ -387,33 +224,81 @@ __global__ void __launch_bounds__(kThreads) k_sample_write(SelArgs a, SampleArgs
             }
             frame[k] = frame_of(s.off, a.B, row);
             keep[k] = decide(a, s, frame[k], v[k].x, v[k].y, v[k].z);
-            isnear[k] = keep[k] && hvpr_pred_near(v[k].x, v[k].y, v[k].z, q.near);
+            if constexpr (NEAR) isnear[k] = keep[k] && hvpr_pred_near(v[k].x, v[k].y, v[k].z, a.near);
         }
         bal[k] = __ballot(keep[k]);
-        nbal[k] = __ballot(isnear[k]);
         total += __popcll(bal[k]);
-        ntotal += __popcll(nbal[k]);
+        if constexpr (NEAR) {
+            nbal[k] = __ballot(isnear[k]);
+            ntotal += __popcll(nbal[k]);
+        }
     }
-    if (lane == 0) { s_w[wid] = total; s_wn[wid] = ntotal; }
+    if (lane == 0) {
+        s_w[0][wid] = total;
+        if constexpr (NEAR) s_w[1][wid] = ntotal;
+    }
     __syncthreads();
-    long long pos = q.tile_first[blockIdx.x], npos = q.tile_near_first[blockIdx.x];
-    for (int w = 0; w < wid; ++w) { pos += s_w[w]; npos += s_wn[w]; }
+    long long pos = w.first[0][blockIdx.x], npos = 0;
+    if constexpr (NEAR) npos = w.first[1][blockIdx.x];
+    for (int i = 0; i < wid; ++i) {
+        pos += s_w[0][i];
+        if constexpr (NEAR) npos += s_w[1][i];
+    }
     const unsigned long long below = (1ull << lane) - 1ull;
-    const int W = a.F + (q.batch_column ? 1 : 0);
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
-        const long long rank = pos + __popcll(bal[k] & below), nrank = npos + __popcll(nbal[k] & below);
+        const long long rank = pos + __popcll(bal[k] & below);
         pos += __popcll(bal[k]);
-        npos += __popcll(nbal[k]);
-        if (!keep[k]) continue;
-        const int b = frame[k];
+        long long nrank = 0;
+        if constexpr (NEAR) {
+            nrank = npos + __popcll(nbal[k] & below);
+            npos += __popcll(nbal[k]);
+        }
+        if (keep[k]) place(frame[k], a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F, v[k], isnear[k], rank, nrank);
+    }
+}
+
+template <bool VEC4>
+__global__ void __launch_bounds__(kThreads) k_select_write(SelArgs a, Carved w, const int *__restrict__ new_off,
+                                                           const int *__restrict__ inv_perm, long long n_perm, int batch_column,
+                                                           float *__restrict__ out, long long out_capacity, int *__restrict__ flag) {
+    __shared__ int s_noff[kMaxFrames + 1];
+    for (int i = threadIdx.x; i <= a.B; i += kThreads) s_noff[i] = new_off[i];                // walk_tile's barriers follow
+    const int W = a.F + (batch_column ? 1 : 0);
+    walk_tile<false, VEC4>(a, w, [&](int b, const float *src, const float4 &v, bool, long long rank, long long) {
+        long long d = rank;
+        if (inv_perm) {
+            const int first = s_noff[b], m = s_noff[b + 1] - first;
+            if (rank >= n_perm) { *flag = 1; return; }
+            const int q = inv_perm[rank];
+            if (q < 0 || q >= m) { *flag = 1; return; }                 // never a row of another frame, never out of bounds
+            d = (long long)first + q;
+        }
+        if (d < 0 || d >= out_capacity) { *flag = 1; return; }
+        store_row<VEC4>(out + (size_t)d * W, batch_column, b, v, src, a.F);
+    });
+}
+
+struct SampleArgs {
+    const int *new_off, *near_off, *mode, *dest;
+    long long n_dest, out_capacity;
+    int P, batch_column;
+};
+
+template <bool VEC4>
+__global__ void __launch_bounds__(kThreads) k_sample_write(SelArgs a, Carved w, SampleArgs q, float *__restrict__ out,
+                                                           int *__restrict__ flag) {
+    __shared__ int s_noff[kMaxFrames + 1], s_near[kMaxFrames + 1];
+    for (int i = threadIdx.x; i <= a.B; i += kThreads) { s_noff[i] = q.new_off[i]; s_near[i] = q.near_off[i]; }
+    const int W = a.F + (q.batch_column ? 1 : 0);
+    walk_tile<true, VEC4>(a, w, [&](int b, const float *src, const float4 &v, bool isnear, long long rank, long long nrank) {
         const long long first = s_noff[b], n_b = s_noff[b + 1] - first;
         const long long r = rank - first, an = nrank - s_near[b], c_b = s_near[b + 1] - s_near[b];
         const int mode = q.mode[b];
-        long long src = r;                                               // mode 0: the in-frame rank
-        if (mode == 1) src = isnear[k] ? an : c_b + (r - an);           // mode 1: near ordinals first, then the far ones
-        const long long t = first + src;
-        if ((mode != 0 && mode != 1) || src < 0 || src >= n_b || t < 0 || t >= q.n_dest) { *flag = 1; continue; }
+        long long ord = r;                                               // mode 0: the in-frame rank
+        if (mode == 1) ord = isnear ? an : c_b + (r - an);              // mode 1: near ordinals first, then the far ones
+        const long long t = first + ord;
+        if ((mode != 0 && mode != 1) || ord < 0 || ord >= n_b || t < 0 || t >= q.n_dest) { *flag = 1; return; }
         const int2 d2 = *reinterpret_cast<const int2 *>(q.dest + 2 * t);
         const int dd[2] = {d2.x, d2.y};
 #pragma unroll
@@ -423,43 +308,100 @@ __global__ void __launch_bounds__(kThreads) k_sample_write(SelArgs a, SampleArgs
             if (d < -1 || d >= q.P) { *flag = 1; continue; }
             const long long at = (long long)b * q.P + d;
             if (at >= q.out_capacity) { *flag = 1; continue; }           // never outside `out`
-            store_row<VEC4>(out + (size_t)at * W, q.batch_column, b, v[k],
-                            a.pts + (size_t)(tile_base + (wid * kItems + k) * 64 + lane) * a.F, a.F);
+            store_row<VEC4>(out + (size_t)at * W, q.batch_column, b, v, src, a.F);
         }
-    }
+    });
 }
 
-int check_sample_args(const float *points, long long rows, int F, const int32_t *off, int B, int mask, const float *calib,
-                      const float *range_xy, float near, void *workspace, size_t workspace_bytes, SelArgs *a) {
-    // check_args' own size test is for the smaller layout of the select calls: the size is tested below
-    const int st = check_args(points, rows, F, off, B, mask, calib, range_xy, workspace, (size_t)-1, a);
-    if (st != HVPR_OK) return st;
+// what all four entry points check; `need` is the workspace size of the caller's layout, `near` 0 where there is none
+int check_args(const float *points, long long rows, int F, const int32_t *off, int B, int mask, const float *calib,
+               const float *range_xy, float near, void *workspace, size_t workspace_bytes, size_t need, SelArgs *a) {
+    if (rows < 0 || F < 3 || B < 1 || mask < 0 || mask > 3 || !off || !workspace) return HVPR_ERR_INVALID_ARG;
+    if ((rows > 0 && !points) || ((mask & 1) && !calib) || ((mask & 2) && !range_xy)) return HVPR_ERR_INVALID_ARG;
+    if (B > kMaxFrames || F > 64 || rows > 0x7fffffffLL - kTile) return HVPR_ERR_UNSUPPORTED;
     if (!(near >= 0.f)) return HVPR_ERR_INVALID_ARG;
-    if (workspace_bytes < hvpr_ragged_sample_workspace_bytes(rows, B)) return HVPR_ERR_WORKSPACE;
+    if (workspace_bytes < need) return HVPR_ERR_WORKSPACE;
+    a->pts = points; a->rows = (int)rows; a->F = F; a->off = off; a->B = B; a->mask = mask;
+    a->tiles = hvpr_cdiv(rows, kTile);
+    a->calib = calib;
+    a->x0 = (mask & 2) ? range_xy[0] : 0.f; a->y0 = (mask & 2) ? range_xy[1] : 0.f;
+    a->x1 = (mask & 2) ? range_xy[2] : 0.f; a->y1 = (mask & 2) ? range_xy[3] : 0.f;
+    a->near = near;
     return HVPR_OK;
+}
+
+size_t workspace_bytes_of(long long rows, int B, int sets) {
+    if (rows < 0 || B < 1) return 0;
+    return carve(nullptr, hvpr_cdiv(rows, kTile), B, sets).bytes;
+}
+
+void launch_count(const SelArgs &a, const Carved &w, int sets, int32_t *new_off, int32_t *near_off, hipStream_t s) {
+    if (a.tiles > 0) {
+        if (sets == 2) hipLaunchKernelGGL(k_count<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, w);
+        else hipLaunchKernelGGL(k_count<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, w);
+    }
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(kThreads), 0, s, a.off, a.B, a.rows, a.tiles, w, sets, new_off, near_off);
+}
+
+// one 16-byte access per row, where the rows allow it
+bool rows_vec4(const float *points, int F, int batch_column, const float *out) {
+    return F == 4 && ((uintptr_t)points & 15) == 0 && (batch_column || ((uintptr_t)out & 15) == 0);
 }
 
 }  // namespace
 
-extern "C" size_t hvpr_ragged_sample_workspace_bytes(long long rows, int n_frames) {
-    if (rows < 0 || n_frames < 1) return 0;
-    return carve_two(nullptr, hvpr_cdiv(rows, kTile), n_frames).bytes;
+extern "C" int hvpr_ragged_select_tile_rows(void) { return kTile; }
+
+extern "C" size_t hvpr_ragged_select_workspace_bytes(long long rows, int n_frames) { return workspace_bytes_of(rows, n_frames, 1); }
+
+extern "C" size_t hvpr_ragged_sample_workspace_bytes(long long rows, int n_frames) { return workspace_bytes_of(rows, n_frames, 2); }
+
+extern "C" int hvpr_ragged_select_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, int32_t *new_off, void *workspace,
+                                            size_t workspace_bytes, hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, 0.f, workspace, workspace_bytes,
+                              workspace_bytes_of(rows, n_frames, 1), &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off) return HVPR_ERR_INVALID_ARG;
+    launch_count(a, carve(workspace, a.tiles, n_frames, 1), 1, new_off, nullptr, (hipStream_t)stream);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
 }
 
 extern "C" int hvpr_ragged_sample_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
                                             int mask, const float *calib, const float *range_xy, float near, int32_t *new_off,
                                             int32_t *near_off, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
     SelArgs a;
-    const int st = check_sample_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace,
-                                     workspace_bytes, &a);
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace, workspace_bytes,
+                              workspace_bytes_of(rows, n_frames, 2), &a);
     if (st != HVPR_OK) return st;
     if (!new_off || !near_off) return HVPR_ERR_INVALID_ARG;
-    const TwoCounts w = carve_two(workspace, a.tiles, n_frames);
+    launch_count(a, carve(workspace, a.tiles, n_frames, 2), 2, new_off, near_off, (hipStream_t)stream);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_ragged_select_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
+                                            int mask, const float *calib, const float *range_xy, const int32_t *new_off,
+                                            const int32_t *inv_perm, long long n_perm, int batch_column, float *out,
+                                            long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
+                                            hvpr_stream_t stream) {
+    SelArgs a;
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, 0.f, workspace, workspace_bytes,
+                              workspace_bytes_of(rows, n_frames, 1), &a);
+    if (st != HVPR_OK) return st;
+    if (!new_off || !flag || out_capacity < 0 || n_perm < 0 || (out_capacity > 0 && !out)) return HVPR_ERR_INVALID_ARG;
+    if (out_capacity > 0x7fffffffLL) return HVPR_ERR_UNSUPPORTED;
+    if (a.tiles == 0) return HVPR_OK;
+    const Carved w = carve(workspace, a.tiles, n_frames, 1);
     hipStream_t s = (hipStream_t)stream;
-    if (a.tiles > 0)
-        hipLaunchKernelGGL(k_sample_count, dim3(a.tiles), dim3(kThreads), 0, s, a, near, w.count[0], w.partial[0], w.count[1],
-                           w.partial[1]);
-    hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kThreads), 0, s, off, n_frames, a.rows, a.tiles, w, new_off, near_off);
+    if (rows_vec4(points, point_floats, batch_column, out))
+        hipLaunchKernelGGL(k_select_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, w, new_off, inv_perm, n_perm,
+                           batch_column ? 1 : 0, out, out_capacity, flag);
+    else
+        hipLaunchKernelGGL(k_select_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, w, new_off, inv_perm, n_perm,
+                           batch_column ? 1 : 0, out, out_capacity, flag);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }
@@ -471,71 +413,22 @@ extern "C" int hvpr_ragged_sample_write_f32(const float *points, long long rows,
                                             long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
                                             hvpr_stream_t stream) {
     SelArgs a;
-    const int st = check_sample_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace,
-                                     workspace_bytes, &a);
+    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, near, workspace, workspace_bytes,
+                              workspace_bytes_of(rows, n_frames, 2), &a);
     if (st != HVPR_OK) return st;
     if (!new_off || !near_off || !mode || !flag || out_capacity < 0 || n_dest < 0 || num_points < 0) return HVPR_ERR_INVALID_ARG;
     if ((out_capacity > 0 && !out) || (n_dest > 0 && !dest) || ((uintptr_t)dest & 7) != 0) return HVPR_ERR_INVALID_ARG;
     if (out_capacity > 0x7fffffffLL || n_dest > 0x3fffffffLL) return HVPR_ERR_UNSUPPORTED;
     if (a.tiles == 0) return HVPR_OK;
-    const TwoCounts w = carve_two(workspace, a.tiles, n_frames);
+    const Carved w = carve(workspace, a.tiles, n_frames, 2);
     SampleArgs q;
     q.new_off = new_off; q.near_off = near_off; q.mode = mode; q.dest = dest;
-    q.tile_first = w.first[0]; q.tile_near_first = w.first[1];
-    q.n_dest = n_dest; q.out_capacity = out_capacity; q.near = near; q.P = num_points; q.batch_column = batch_column ? 1 : 0;
+    q.n_dest = n_dest; q.out_capacity = out_capacity; q.P = num_points; q.batch_column = batch_column ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec4 = point_floats == 4 && ((uintptr_t)points & 15) == 0 && (batch_column || ((uintptr_t)out & 15) == 0);
-    if (vec4)
-        hipLaunchKernelGGL(k_sample_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, q, out, flag);
+    if (rows_vec4(points, point_floats, batch_column, out))
+        hipLaunchKernelGGL(k_sample_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, w, q, out, flag);
     else
-        hipLaunchKernelGGL(k_sample_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, q, out, flag);
-    HVPR_CHECK_LAUNCH();
-    return HVPR_OK;
-}
-
-extern "C" int hvpr_ragged_select_tile_rows(void) { return kTile; }
-
-extern "C" size_t hvpr_ragged_select_workspace_bytes(long long rows, int n_frames) {
-    if (rows < 0 || n_frames < 1) return 0;
-    return carve(nullptr, hvpr_cdiv(rows, kTile), n_frames).bytes;
-}
-
-extern "C" int hvpr_ragged_select_count_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
-                                            int mask, const float *calib, const float *range_xy, int32_t *new_off, void *workspace,
-                                            size_t workspace_bytes, hvpr_stream_t stream) {
-    SelArgs a;
-    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, workspace, workspace_bytes, &a);
-    if (st != HVPR_OK) return st;
-    if (!new_off) return HVPR_ERR_INVALID_ARG;
-    const Carved w = carve(workspace, a.tiles, n_frames);
-    hipStream_t s = (hipStream_t)stream;
-    if (a.tiles > 0) hipLaunchKernelGGL(k_select_count, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_count, w.partial);
-    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kThreads), 0, s, off, n_frames, a.rows, a.tiles, w.tile_count, w.tile_first,
-                       w.partial, new_off);
-    HVPR_CHECK_LAUNCH();
-    return HVPR_OK;
-}
-
-extern "C" int hvpr_ragged_select_write_f32(const float *points, long long rows, int point_floats, const int32_t *off, int n_frames,
-                                            int mask, const float *calib, const float *range_xy, const int32_t *new_off,
-                                            const int32_t *inv_perm, long long n_perm, int batch_column, float *out,
-                                            long long out_capacity, int32_t *flag, void *workspace, size_t workspace_bytes,
-                                            hvpr_stream_t stream) {
-    SelArgs a;
-    const int st = check_args(points, rows, point_floats, off, n_frames, mask, calib, range_xy, workspace, workspace_bytes, &a);
-    if (st != HVPR_OK) return st;
-    if (!new_off || !flag || out_capacity < 0 || n_perm < 0 || (out_capacity > 0 && !out)) return HVPR_ERR_INVALID_ARG;
-    if (out_capacity > 0x7fffffffLL) return HVPR_ERR_UNSUPPORTED;
-    if (a.tiles == 0) return HVPR_OK;
-    const Carved w = carve(workspace, a.tiles, n_frames);
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec4 = point_floats == 4 && ((uintptr_t)points & 15) == 0 && (batch_column || ((uintptr_t)out & 15) == 0);
-    if (vec4)
-        hipLaunchKernelGGL(k_select_write<true>, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_first, new_off, inv_perm, n_perm,
-                           batch_column ? 1 : 0, out, out_capacity, flag);
-    else
-        hipLaunchKernelGGL(k_select_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, w.tile_first, new_off, inv_perm, n_perm,
-                           batch_column ? 1 : 0, out, out_capacity, flag);
+        hipLaunchKernelGGL(k_sample_write<false>, dim3(a.tiles), dim3(kThreads), 0, s, a, w, q, out, flag);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }

@@ -43,6 +43,28 @@ static inline int hvpr_ensure_dyn_lds(const void *fn, int bytes, unsigned long l
 
 __device__ __forceinline__ int hvpr_lane() { return threadIdx.x & 63; }
 
+// One workgroup (a multiple of 64 threads): dst[i] = base + get(0) + ... + get(i - 1) for i in [0, n); with `total`, dst[n] = base
+// + the sum of all.  A contiguous piece per thread, the pieces' sums scanned over the wave by shuffles and over the waves
+// through `wave_sum`, the caller's LDS array of one int per wave.  Ends with a barrier: the workgroup may read dst and use
+// `wave_sum` again.
+template <typename Get>
+__device__ __forceinline__ void hvpr_block_scan(Get get, int n, int base, int32_t *dst, bool total, int *wave_sum) {
+    const int T = blockDim.x, t = threadIdx.x, ln = t & 63, wv = t >> 6, per = (n + T - 1) / T;
+    const int lo = min(n, t * per), hi = min(n, lo + per);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += get(i);
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (ln >= o) inc += u; }
+    if (ln == 63) wave_sum[wv] = inc;
+    __syncthreads();
+    int run = base + inc - s;
+    for (int w = 0; w < wv; ++w) run += wave_sum[w];
+    for (int i = lo; i < hi; ++i) { const int v = get(i); dst[i] = run; run += v; }
+    if (total && t == T - 1) dst[n] = run;                             // the last piece ends at n
+    __syncthreads();
+}
+
 // All-lanes reductions over the 64-lane wave or within its 32-lane halves, without the LDS crossbar: two quad permutes, the two
 // row mirrors (after the quad steps every lane of a quad holds the same value, so mirroring combines exactly the groups an
 // xor butterfly would), then v_permlane16_swap / v_permlane32_swap (gfx950) across the 16-lane rows.  Same reduction tree as

@@ -2,10 +2,8 @@
 // KittiDataset.create_groundtruth_database (pcdet/datasets/kitti/kitti_dataset.py:205-238).  Per annotated box the points of
 // its frame that lie inside it (points_in_boxes_cpu, :217), moved into the box's own frame (:226), end to end in one arena.
 //
-// The inside test is the one of csrc_cpu/gt_sampling.cpp:95-107, the same fp32 operations in the same order (k_points_count of
-// augment.hip holds the same expression; it is restated here so that file's code stays as it is).  The move is numpy's: a
-// float32 column minus a float64 centre is computed in double and rounded once (:226 subtracts float64 boxes from a float32
-// array), so the centres come as doubles.
+// The inside test is box_cut.h's, shared with augment.hip.  The move is numpy's: a float32 column minus a float64 centre is
+// computed in double and rounded once (:226 subtracts float64 boxes from a float32 array), so the centres come as doubles.
 //
 // Three passes, no atomics, stable, bit-reproducible: a count pass (per box and block of kBlk scene points how many points are
 // inside, then per box the sum), a scan (obj_off over the boxes, then each box's blocks), a write pass.  The count and write
@@ -13,6 +11,7 @@
 // 200 keep the machine equally busy.  Between the two entry points the host reads obj_count and sizes the arena.
 //
 // Built with -ffp-contract=off: the fp32 operation order below is the CPU native's.
+#include "box_cut.h"
 #include "common.h"
 
 #include <algorithm>
@@ -24,31 +23,17 @@ constexpr int kBlk = 256;            // scene points per workgroup of the count 
 constexpr int kWaves = kBlk / 64;
 constexpr int kMaxFrames = 65535;    // gridDim.y
 
-struct Cut { float x, y, z, hx, hy, hz, cs, sn; };
-
-__device__ __forceinline__ void load_cuts(const float *__restrict__ boxes, int b0, int nb, Cut *cut) {
-    for (int k = threadIdx.x; k < nb; k += blockDim.x) {
-        const float *b = boxes + (size_t)(b0 + k) * 7;
-        Cut c;
-        c.x = b[0]; c.y = b[1]; c.z = b[2];
-        c.hx = b[3] / 2.0f; c.hy = b[4] / 2.0f; c.hz = b[5] / 2.0f;
-        c.cs = cosf(-b[6]); c.sn = sinf(-b[6]);
-        cut[k] = c;
-    }
-}
-
-__device__ __forceinline__ bool inside(const Cut &c, float x, float y, float z) {
-    if (!(fabsf(z - c.z) <= c.hz)) return false;
-    const float sx = x - c.x, sy = y - c.y;
-    const float lx = sx * c.cs - sy * c.sn, ly = sx * c.sn + sy * c.cs;
-    return fabsf(lx) < c.hx && fabsf(ly) < c.hy;
+// The boxes as they are: no extra width.  size + 0.0f is the size for every float except that -0 becomes +0, and a half width
+// of either zero rejects every point under `<` and decides `<=` alike, so every inside decision is that of size / 2.0f.
+__device__ __forceinline__ void load_cuts(const float *__restrict__ boxes, int b0, int nb, hvpr_cut *cut) {
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) cut[k] = hvpr_make_cut(boxes + (size_t)(b0 + k) * 7, 0.0f, 0.0f, 0.0f);
 }
 
 // wave_n[w * kFrameBoxes + k] = how many points of wave w of this workgroup lie in box k of the frame
-__device__ __forceinline__ void wave_counts(const Cut *cut, int nb, bool live, float x, float y, float z, int *wave_n) {
+__device__ __forceinline__ void wave_counts(const hvpr_cut *cut, int nb, bool live, float x, float y, float z, int *wave_n) {
     const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int k = 0; k < nb; ++k) {
-        const unsigned long long m = __ballot(live && inside(cut[k], x, y, z));
+        const unsigned long long m = __ballot(live && hvpr_cut_inside(cut[k], x, y, z));
         if (ln == 0) wave_n[wv * kFrameBoxes + k] = __popcll(m);
     }
 }
@@ -58,7 +43,7 @@ __device__ __forceinline__ void wave_counts(const Cut *cut, int nb, bool live, f
 __global__ void __launch_bounds__(kBlk) k_count(const float *__restrict__ pts, int F, const int32_t *__restrict__ pt_off,
                                                 const float *__restrict__ boxes, const int32_t *__restrict__ box_off,
                                                 int32_t *__restrict__ blk_cnt) {
-    __shared__ Cut cut[kFrameBoxes];
+    __shared__ hvpr_cut cut[kFrameBoxes];
     __shared__ int wave_n[kWaves * kFrameBoxes];
     const int f = blockIdx.y;
     const int b0 = box_off[f], nb = min(box_off[f + 1] - b0, kFrameBoxes);
@@ -94,38 +79,18 @@ __global__ void __launch_bounds__(64) k_obj_count(const int32_t *__restrict__ bl
     if (threadIdx.x == 0) obj_count[blockIdx.x] = s;
 }
 
-// dst[i] = base + the sum of src[0..i) for i in [0, n); with `total`, dst[n] = base + the sum of all.  One workgroup, a
-// contiguous piece per thread.
-__device__ __forceinline__ void block_scan(const int32_t *__restrict__ src, int n, int base, int32_t *__restrict__ dst, bool total,
-                                           int *part) {
-    const int T = blockDim.x, t = threadIdx.x, per = (n + T - 1) / T;
-    const int lo = min(n, t * per), hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += src[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int run = base;
-        for (int i = 0; i < T; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        if (total) dst[n] = run;
-    }
-    __syncthreads();
-    int run = part[t];
-    for (int i = lo; i < hi; ++i) { const int v = src[i]; dst[i] = run; run += v; }
-}
-
 // pass 2a: obj_off [n_obj + 1]
 __global__ void __launch_bounds__(256) k_scan_obj(const int32_t *__restrict__ obj_count, int n_obj, int32_t *__restrict__ obj_off) {
-    __shared__ int part[256];
-    block_scan(obj_count, n_obj, 0, obj_off, true, part);
+    __shared__ int wave_sum[256 / 64];
+    hvpr_block_scan([&](int i) { return obj_count[i]; }, n_obj, 0, obj_off, true, wave_sum);
 }
 
 // pass 2b: blk_pre[k * max_blk + b] = the arena row of the first point of block b in box k; a workgroup per box
 __global__ void __launch_bounds__(64) k_scan_blk(const int32_t *__restrict__ blk_cnt, int max_blk, const int32_t *__restrict__ obj_off,
                                                  int32_t *__restrict__ blk_pre) {
-    __shared__ int part[64];
+    __shared__ int wave_sum[1];
     const size_t o = (size_t)blockIdx.x * max_blk;
-    block_scan(blk_cnt + o, max_blk, obj_off[blockIdx.x], blk_pre + o, false, part);
+    hvpr_block_scan([&](int i) { return blk_cnt[o + i]; }, max_blk, obj_off[blockIdx.x], blk_pre + o, false, wave_sum);
 }
 
 // pass 3: every (point, box) pair that is inside writes one arena row.  The test is made again, on the same values by the same
@@ -134,7 +99,7 @@ __global__ void __launch_bounds__(kBlk) k_write(const float *__restrict__ pts, i
                                                 const float *__restrict__ boxes, const int32_t *__restrict__ box_off,
                                                 const double *__restrict__ centres, const int32_t *__restrict__ blk_pre,
                                                 long long capacity, float *__restrict__ arena) {
-    __shared__ Cut cut[kFrameBoxes];
+    __shared__ hvpr_cut cut[kFrameBoxes];
     __shared__ int wave_n[kWaves * kFrameBoxes];
     const int f = blockIdx.y;
     const int b0 = box_off[f], nb = min(box_off[f + 1] - b0, kFrameBoxes);
@@ -151,7 +116,7 @@ __global__ void __launch_bounds__(kBlk) k_write(const float *__restrict__ pts, i
     __syncthreads();
     const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int k = 0; k < nb; ++k) {
-        const bool in = live && inside(cut[k], x, y, z);
+        const bool in = live && hvpr_cut_inside(cut[k], x, y, z);
         const unsigned long long m = __ballot(in);
         if (!in) continue;
         int before = 0;

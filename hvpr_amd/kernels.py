@@ -990,8 +990,7 @@ def augment_points(plan_host, plan_dev, words, valid, points, bank_points, bank_
         out = torch.empty((n + int(h[c5: c5 + C].sum()), F), dtype=torch.float32, device=points.device)
     if out_off is None:
         out_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
-    ws_bytes = lib().hvpr_augment_points_workspace_bytes(B, max_frame, C, n)
-    ws = torch.empty((max(int(ws_bytes), 256),), dtype=torch.uint8, device=points.device)
+    ws = _workspace(None, lib().hvpr_augment_points_workspace_bytes(B, max_frame, C, n), points.device)
     check(lib().hvpr_augment_points_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words),
                                         _ptr(valid, torch.int32, "valid"), _ptr(points, torch.float32, "points"), n, F,
                                         _ptr(bank_points, torch.float32, "bank points"), bank_points.shape[0],
@@ -1024,10 +1023,7 @@ def _gt_database_workspace(pt_off_host, n_obj, device, workspace):
     import numpy as np
     off = pt_off_host.numpy()
     max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
-    need = int(lib().hvpr_gt_database_workspace_bytes(off.shape[0] - 1, max_frame, int(n_obj)))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=device)
-    return workspace
+    return _workspace(workspace, lib().hvpr_gt_database_workspace_bytes(off.shape[0] - 1, max_frame, int(n_obj)), device)
 
 
 def gt_database_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off, obj_count=None, workspace=None):
@@ -1073,27 +1069,46 @@ def ragged_select_tile_rows():
     return int(lib().hvpr_ragged_select_tile_rows())
 
 
-def _range_xy(range_xy):
+def _workspace(workspace, need, device):
+    """`workspace` where it holds `need` bytes, else a new uint8 one of at least 256."""
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(int(need), 256),), dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _ragged_head(points, off, mask, calib, range_xy):
+    """(rows, F, B, head, range): `head` is the arguments every hvpr_ragged_* call begins with; `range` owns the host floats
+    `head` points to and has to outlive the call."""
     import numpy as np
-    return None if range_xy is None else np.ascontiguousarray(range_xy, np.float32).reshape(4)
+    rows, F = points.shape
+    B = off.numel() - 1
+    r = None if range_xy is None else np.ascontiguousarray(range_xy, np.float32).reshape(4)
+    head = (_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B, int(mask),
+            _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data)
+    return rows, F, B, head, r
+
+
+def _offsets(t, B, device):
+    return torch.empty((B + 1,), dtype=torch.int32, device=device) if t is None else t
+
+
+def _out_and_flag(out, flag, rows, width, device):
+    if out is None:
+        out = torch.empty((rows, width), dtype=torch.float32, device=device)
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=device)
+    return out, flag
 
 
 def ragged_select_count(points, off, mask, calib=None, range_xy=None, new_off=None, workspace=None):
     """(new_off (B+1,) int32, workspace).  points (rows, F) float32 and off (B+1,) int32 on the device, `calib` (B, 26) float32
     on the device (eval_loop.pack_calib) for mask bit 1, `range_xy` four host floats (x0, y0, x1, y1) for mask bit 2.  Rows at or
     past off[B] are ignored.  Nothing is read: the workspace goes to ragged_select_write of the same input."""
-    rows, F = points.shape
-    B = off.numel() - 1
-    r = _range_xy(range_xy)
-    if new_off is None:
-        new_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
-    need = int(lib().hvpr_ragged_select_workspace_bytes(rows, B))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=points.device)
-    check(lib().hvpr_ragged_select_count_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
-                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
-                                             _ptr(new_off, torch.int32, "new_off"), workspace.data_ptr(), workspace.numel(),
-                                             _stream()), "hvpr_ragged_select_count_f32")
+    rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
+    new_off = _offsets(new_off, B, points.device)
+    workspace = _workspace(workspace, lib().hvpr_ragged_select_workspace_bytes(rows, B), points.device)
+    check(lib().hvpr_ragged_select_count_f32(*head, _ptr(new_off, torch.int32, "new_off"), workspace.data_ptr(),
+                                             workspace.numel(), _stream()), "hvpr_ragged_select_count_f32")
     return new_off, workspace
 
 
@@ -1102,16 +1117,9 @@ def ragged_select_write(points, off, mask, new_off, workspace, calib=None, range
     """(out, flag).  `out` (capacity, F + batch_column) float32: the kept rows, stable, each at its flat rank or, with the flat
     int32 `inv_perm`, at new_off[b] + inv_perm[rank]; `flag` (1,) int32 is set when a row had to be dropped (an inv_perm entry
     outside its frame, an output too small).  Without `out` the output is sized by the input rows: no read is needed."""
-    rows, F = points.shape
-    B = off.numel() - 1
-    r = _range_xy(range_xy)
-    if out is None:
-        out = torch.empty((rows, F + (1 if batch_column else 0)), dtype=torch.float32, device=points.device)
-    if flag is None:
-        flag = torch.zeros((1,), dtype=torch.int32, device=points.device)
-    check(lib().hvpr_ragged_select_write_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
-                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
-                                             _ptr(new_off, torch.int32, "new_off"), _ptr(inv_perm, torch.int32, "inv_perm"),
+    rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
+    out, flag = _out_and_flag(out, flag, rows, F + (1 if batch_column else 0), points.device)
+    check(lib().hvpr_ragged_select_write_f32(*head, _ptr(new_off, torch.int32, "new_off"), _ptr(inv_perm, torch.int32, "inv_perm"),
                                              0 if inv_perm is None else inv_perm.numel(), int(bool(batch_column)),
                                              _ptr(out, torch.float32, "out"), out.shape[0], _ptr(flag, torch.int32, "flag"),
                                              workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_ragged_select_write_f32")
@@ -1121,19 +1129,10 @@ def ragged_select_write(points, off, mask, new_off, workspace, calib=None, range
 def ragged_sample_count(points, off, mask, calib=None, range_xy=None, near=40.0, new_off=None, near_off=None, workspace=None):
     """(new_off, near_off, workspace): ragged_select_count with the second count sample_points needs.  near_off[b] = kept rows in
     front of off[b] with ||xyz|| < near.  Nothing is read: the workspace goes to ragged_sample_write of the same input."""
-    rows, F = points.shape
-    B = off.numel() - 1
-    r = _range_xy(range_xy)
-    if new_off is None:
-        new_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
-    if near_off is None:
-        near_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
-    need = int(lib().hvpr_ragged_sample_workspace_bytes(rows, B))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=points.device)
-    check(lib().hvpr_ragged_sample_count_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
-                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
-                                             float(near), _ptr(new_off, torch.int32, "new_off"),
+    rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
+    new_off, near_off = _offsets(new_off, B, points.device), _offsets(near_off, B, points.device)
+    workspace = _workspace(workspace, lib().hvpr_ragged_sample_workspace_bytes(rows, B), points.device)
+    check(lib().hvpr_ragged_sample_count_f32(*head, float(near), _ptr(new_off, torch.int32, "new_off"),
                                              _ptr(near_off, torch.int32, "near_off"), workspace.data_ptr(), workspace.numel(),
                                              _stream()), "hvpr_ragged_sample_count_f32")
     return new_off, near_off, workspace
@@ -1145,18 +1144,11 @@ def ragged_sample_write(points, off, mask, new_off, near_off, mode, dest, num_po
     two destinations d >= 0 in `dest` (total kept, 2) int32, indexed by new_off[b] + the row's source ordinal: its in-frame rank
     where `mode` (B,) int32 is 0, near ordinals first and far ones behind them where it is 1.  `flag` (1,) int32 is set when a
     store had to be dropped (a destination outside [-1, num_points), a table or an output too small)."""
-    rows, F = points.shape
-    B = off.numel() - 1
-    r = _range_xy(range_xy)
-    if out is None:
-        out = torch.empty((B * int(num_points), F + (1 if batch_column else 0)), dtype=torch.float32, device=points.device)
-    if flag is None:
-        flag = torch.zeros((1,), dtype=torch.int32, device=points.device)
+    rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
+    out, flag = _out_and_flag(out, flag, B * int(num_points), F + (1 if batch_column else 0), points.device)
     if mode.numel() != B or dest.dim() != 2 or dest.shape[1] != 2:
         raise ValueError("hvpr_amd: mode must be (B,) and dest (n, 2)")
-    check(lib().hvpr_ragged_sample_write_f32(_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B,
-                                             int(mask), _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data,
-                                             float(near), _ptr(new_off, torch.int32, "new_off"),
+    check(lib().hvpr_ragged_sample_write_f32(*head, float(near), _ptr(new_off, torch.int32, "new_off"),
                                              _ptr(near_off, torch.int32, "near_off"), _ptr(mode, torch.int32, "mode"),
                                              _ptr(dest, torch.int32, "dest"), dest.shape[0], int(num_points),
                                              int(bool(batch_column)), _ptr(out, torch.float32, "out"), out.shape[0],
