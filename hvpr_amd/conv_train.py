@@ -343,13 +343,18 @@ def conv_fwd_raw(x, weight, stride=1, adjoint=False, stats=False):
     return (z, None) if stats else z
 
 
+def _wino_wgrad_fits(H, W, cin, cout):
+    """The Winograd-domain weight-gradient kernel addresses inside an image with 32 bits (hvpr_conv2d_wino_wgrad_nhwc_f32 refuses an
+    image of 2 GB and more): those go to the direct kernel."""
+    return H * W * max(cin, cout) * 4 < 2 ** 31
+
+
 def conv_wgrad(x, dz, taps, stride, cout, cin):
     N, H, W, _ = x.shape
     OH, OW = dz.shape[1], dz.shape[2]
     k = 3 if taps == 9 else 1
     dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
-    # (the Winograd-domain kernel addresses inside an image with 32 bits: images of 2 GB and more go to the direct kernel)
-    if taps == 9 and stride == 1 and kernels.conv_algo() == "winograd" and H * W * max(cin, cout) * 4 < 2 ** 31:
+    if taps == 9 and stride == 1 and kernels.conv_algo() == "winograd" and _wino_wgrad_fits(H, W, cin, cout):
         nbytes = lib().hvpr_conv2d_wino_wgrad_workspace_bytes(N, H, W, cin, cout)
         ws = _workspace(nbytes, x.device)
         check(lib().hvpr_conv2d_wino_wgrad_nhwc_f32(kernels._ptr(x, torch.float32, "x"), N, H, W, cin, kernels._ptr(dz, torch.float32, "dz"),
