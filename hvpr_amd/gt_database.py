@@ -102,7 +102,7 @@ def _points_of(p):
 def count_points_in_boxes(points_list, boxes_list, device="cuda:0", frames_per_call=32):
     """Per frame i an (n_i,) int32 array: how many of points_list[i] (N_i, F) lie inside each of boxes_list[i] (n_i, 7+).  The
     box test of the database, without the database; NOT get_infos' num_points_in_gt (kitti_dataset.py:171-184), which is a hull
-    test over the points in the camera's view."""
+    test over the points in the camera's view: that count is hvpr_amd.kitti_dataset's (InfoCounter, KittiDataset.get_infos)."""
     if len(points_list) != len(boxes_list):
         raise ValueError("count_points_in_boxes: one box array per frame")
     out, stage, ws = [], [None], None

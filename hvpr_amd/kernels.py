@@ -1063,6 +1063,41 @@ def gt_database_extract(points, pt_off_host, pt_off, boxes, box_off_host, box_of
     return obj_off
 
 
+# ------------------------------------------------------------------------------------------------ f8: get_infos' counts
+def kitti_infos_block_points():
+    """Scene points per workgroup of the count pass (the database's block)."""
+    return int(lib().hvpr_kitti_infos_block_points())
+
+
+def kitti_infos_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off, calib_host, calib, obj_count=None, fov_count=None,
+                      want_fov=False, workspace=None):
+    """(obj_count (n_obj,) int32, fov_count (B,) int32 or None, workspace): per box the points of its frame in the camera's view
+    and inside it, per frame (with `want_fov` or a `fov_count` tensor) the points in view.  The chunk as gt_database_count takes
+    it; `calib_host` is the (B, 26) float32 host tensor (eval_loop.pack_calib) the device copy `calib` was made from.  The library
+    checks the host copies before it launches anything."""
+    import numpy as np
+    n, F = points.shape
+    n_obj, B = int(boxes.shape[0]), pt_off_host.numel() - 1
+    if calib_host.dtype != torch.float32 or calib_host.numel() != 26 * B or not calib_host.is_contiguous() or calib_host.is_cuda:
+        raise ValueError("kitti_infos_count: calib_host must be a contiguous (B, 26) float32 host tensor")
+    if calib.numel() != 26 * B:
+        raise ValueError("kitti_infos_count: calib must be (B, 26)")
+    if obj_count is None:
+        obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=points.device)[:n_obj]
+    if fov_count is None and want_fov:
+        fov_count = torch.empty((B,), dtype=torch.int32, device=points.device)
+    off = pt_off_host.numpy()
+    max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
+    workspace = _workspace(workspace, lib().hvpr_kitti_infos_workspace_bytes(B, max_frame, n_obj), points.device)
+    check(lib().hvpr_kitti_infos_count_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
+                                           _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
+                                           box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"), n_obj,
+                                           calib_host.data_ptr(), _ptr(calib, torch.float32, "calib"),
+                                           _ptr(obj_count, torch.int32, "obj_count"), _ptr(fov_count, torch.int32, "fov_count"),
+                                           workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_kitti_infos_count_f32")
+    return obj_count, fov_count, workspace
+
+
 # ------------------------------------------------------------------------------------------------ f7: ragged select / collate
 def ragged_select_tile_rows():
     """Rows per workgroup of the count and write passes."""

@@ -866,6 +866,32 @@ int hvpr_ragged_sample_write_f32(const float *points, long long rows, int point_
                                  int num_points, int batch_column, float *out, long long out_capacity, int32_t *flag,
                                  void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * f8  get_infos' num_points_in_gt, a chunk of frames per call: the loop of KittiDataset.get_infos (kitti_dataset.py:171-184).
+ *     The chunk is f6's: `points` [n_points, point_floats] f32 (3 <= point_floats <= 8) with `pt_off`, `boxes` [n_obj, 7] f32
+ *     with `box_off`, both offset arrays [n_frames + 1] i32 given twice (`_host` read and checked here, the other read by the
+ *     kernels), a frame of at most 256 boxes, a chunk of at most 65535 frames, 32-bit rows.  The calibration table is f7's:
+ *     `calib` [n_frames, 26] f32 (eval_loop.pack_calib: V2C^T R0^T 4x3, P2 3x4, image height, image width), also given twice;
+ *     the host copy is checked for image height and width > 0.  Every check is made on the host: a refused call returns
+ *     HVPR_ERR_INVALID_ARG / HVPR_ERR_UNSUPPORTED / HVPR_ERR_WORKSPACE and launches nothing.  The call only enqueues.
+ *     hvpr_kitti_infos_count_f32    obj_count[k] = points of box k's frame that are in that frame's camera view AND inside box
+ *                           k.  The view test is the shared expression of hvpr_point_flags_f32 mode 0 and the ragged select
+ *                           (the same decisions, bit for bit); the box test is f6's (the hull of a cuboid's corners is the
+ *                           cuboid; on a face `<=` / `<` decide here and Qhull's tolerance in the reference: unpinned; a box
+ *                           with a zero size counts 0).  `fov_count` [n_frames] i32, or NULL to skip it: the frame's points in
+ *                           view.  With n_obj == 0 and fov_count NULL nothing is launched.  No atomics, bit-reproducible.
+ *     hvpr_kitti_infos_workspace_bytes  for frames of at most max_frame_points points and n_obj boxes in all (per box and per
+ *                           frame one partial count per block); 0 for a chunk without frames.  Needs no GPU.
+ *     hvpr_kitti_infos_block_points scene points per workgroup: the block of hvpr_gt_database_block_points, the same number.
+ * ------------------------------------------------------------------------------------------- */
+int hvpr_kitti_infos_block_points(void);
+size_t hvpr_kitti_infos_workspace_bytes(int n_frames, int max_frame_points, int n_obj);
+int hvpr_kitti_infos_count_f32(const float *points, long long n_points, int point_floats, const int32_t *pt_off_host,
+                               const int32_t *pt_off, int n_frames, const float *boxes, const int32_t *box_off_host,
+                               const int32_t *box_off, int n_obj, const float *calib_host, const float *calib,
+                               int32_t *obj_count, int32_t *fov_count, void *workspace, size_t workspace_bytes,
+                               hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
