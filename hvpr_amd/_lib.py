@@ -107,6 +107,12 @@ SIGNATURES = {
     "hvpr_conv2d_wino_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "hvpr_conv2d_wino_stats_rows": (_I, [_I, _I, _I]),
     "hvpr_conv2d_wino_items": (_I, [_I, _I, _I, _I, _I]),
+    "hvpr_conv2d_wino_tab_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "hvpr_conv2d_wino_tab_build": (_I, [_I, _I, _I, _I, _I, _P, _P]),
+    "hvpr_conv2d_wino_nhwc_tab_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "hvpr_conv2d_tab_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "hvpr_conv2d_tab_build": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "hvpr_conv2d_nhwc_tab_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "hvpr_conv2d_s2_dgrad_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "hvpr_bn_train_affine_f32": (_I, [_P, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "hvpr_bn_finalize_partials_f32": (_I, [_P, _I, _I, _c.c_longlong, _F, _P, _P, _P, _P]),

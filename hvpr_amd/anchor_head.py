@@ -259,7 +259,7 @@ class AnchorHeadSingle(AnchorHeadTemplate):
         f2d = data_dict["spatial_features_2d"]
         x = f2d.permute(0, 2, 3, 1).contiguous()
         P = self._fold.get(x.device, lambda: self._build_packed(x.device))
-        head = kernels.conv2d_nhwc(x, P["pc"])                                   # (B, H, W, na*(nc+7+bins))
+        head = kernels.conv2d_nhwc(x, P["pc"], use_table=True)                                   # (B, H, W, na*(nc+7+bins))
         na, nc, nb = self.num_anchors_per_location, self.num_class, self.num_dir_bins
         self.forward_ret_dict["cls_preds"] = head[..., : na * nc]                 # NHWC views, as the reference keeps
         self.forward_ret_dict["box_preds"] = head[..., na * nc: na * (nc + 7)]

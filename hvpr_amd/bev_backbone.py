@@ -130,22 +130,22 @@ class _Fork:
 def _trunk(lv, x, out=None):
     """The level's trunk convolutions, the last one into `out` when given."""
     for pc in lv.trunk[:-1]:
-        x = kernels.conv2d_nhwc(x, pc)
-    return kernels.conv2d_nhwc(x, lv.trunk[-1], out=out)
+        x = kernels.conv2d_nhwc(x, pc, use_table=True)
+    return kernels.conv2d_nhwc(x, lv.trunk[-1], out=out, use_table=True)
 
 
 def _branch(lv, x, y, out, fork, y_out=None):
     """The level's attentive branch on x = its trunk output and y = the scale stream: scale conv (into `y_out` when given), gate, SFM
     steps, deconv into the level's slice of `out`.  Returns the level's scale output, the next level's y."""
     with fork.branch(lv.index, x, out):
-        y = kernels.conv2d_nhwc(y, lv.scale, out=y_out)
+        y = kernels.conv2d_nhwc(y, lv.scale, out=y_out, use_table=True)
         fork.y_ready(lv.index, y)
         gate = kernels.spatial_gate(y, *lv.gate)
         for pc in lv.sfm_steps:
-            x = kernels.conv2d_nhwc(x, pc, gate=gate, resid=x)
+            x = kernels.conv2d_nhwc(x, pc, gate=gate, resid=x, use_table=True)
             fork.held.append(x)
         fork.held.append(gate)
-        kernels.conv2d_nhwc(x, lv.deconv, out=out, out_coff=lv.coff)
+        kernels.conv2d_nhwc(x, lv.deconv, out=out, out_coff=lv.coff, use_table=True)
     return y
 
 

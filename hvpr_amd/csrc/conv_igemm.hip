@@ -60,7 +60,22 @@ struct ConvArgs {
     int up;               // 1, or the ConvTranspose stride s (kernel == stride): column = (ky*s+kx)*cout_real + co
     int cout_real;        // channels per sub-pixel when up > 1 (== cout_gemm when up == 1)
     int tiles_x, tiles_y, n_ct;
+    const unsigned long long *tab;   // one entry per walk step (k_conv_tab) or null: the walk is decoded in the kernel
 };
+
+// Per-item work outside the K loop, each a compile-time switch of the forward instantiations (UP2 keeps the plain code), as in
+// conv_wino.hip:  OPT_TAB  the items come from a table (the instantiation a launch with a table runs);  OPT_PEEL  chunk 0 is peeled and its first MFMA per
+// accumulator block takes C = 0, no clear.
+enum { OPT_TAB = 1, OPT_PEEL = 2 };
+#ifndef HVPR_ITEM_OPT
+#define HVPR_ITEM_OPT (OPT_TAB | OPT_PEEL)      // the kept set
+#endif
+
+// Table entry of a walk step:  lo = tx [0..15] | ty [16..30] | hole [31]    hi = ct [0..11] | n [12..31]
+constexpr int TAB_MAX_TX = 1 << 16, TAB_MAX_TY = 1 << 15, TAB_MAX_CT = 1 << 12, TAB_MAX_N = 1 << 20;
+__device__ __forceinline__ unsigned long long tab_load(const unsigned long long *tab, int step) {      // uniform address: a scalar load
+    return *((const __attribute__((address_space(4))) unsigned long long *)(size_t)tab + step);
+}
 
 #ifdef HVPR_EXP_TIMING
 // kernel experiments: cycle stamps of the phases of every chunk of the SECOND tile of a few workgroups (all four waves), read
@@ -77,9 +92,11 @@ __device__ long long g_conv_dbg[8 * 4 * 64 * 4];
 // (conv_train.py ran that one on the Winograd kernel: 4.7 ms per layer at batch 16 for 173 GFLOP of useful work).  A 16 x 16 output
 // tile = 8 x 8 positions (a, b) x 4 classes; MFMA block mb of a wave IS class (mb >> 1, mb & 1) for the wave's 4 x 8 positions, so which
 // taps a block multiplies is known at compile time and every wave does the same 9 (tap, class) products per chunk.
-template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false>
+template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, int OPT = 0>
 __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     static_assert(!UP2 || (TAPS == 9 && S == 1 && TH == 16 && TW == 16), "UP2: 16 x 16 output tiles of a 3x3 stride-2 layer's data gradient");
+    static_assert(!UP2 || OPT == 0, "the item switches belong to the forward instantiations");
+    constexpr bool TAB = (OPT & OPT_TAB) != 0, PEEL = (OPT & OPT_PEEL) != 0;
     constexpr int BM = TH * TW;
     constexpr int WM = BM / 2, WN = BN / 2;        // per-wave tile
     constexpr int MB = WM / 32, NB = WN / 32;
@@ -162,14 +179,25 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     int dbg_tile = 0;
     const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;
 #endif
+    unsigned long long e_next = 0ull;                          // the next step's entry, in flight while this item multiplies
+    if (TAB && (int)blockIdx.x < total_walk) e_next = tab_load(a.tab, blockIdx.x);
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
-    const int xcd = it & 7, j = it >> 3;
-    const int ct = j % a.n_ct;
-    int pt = (j / a.n_ct) * 8 + xcd;
-    if (pt >= n_pt) continue;
-    const int tx = pt % a.tiles_x; pt /= a.tiles_x;
-    const int ty = pt % a.tiles_y;
-    const int n = pt / a.tiles_y;
+    int ct, tx, ty, n;
+    if constexpr (TAB) {
+        const unsigned lo = (unsigned)e_next, hi = (unsigned)(e_next >> 32);
+        if (it + (int)gridDim.x < total_walk) e_next = tab_load(a.tab, it + (int)gridDim.x);
+        if (lo >> 31) continue;
+        tx = (int)(lo & 0xffffu); ty = (int)(lo >> 16 & 0x7fffu); ct = (int)(hi & 0xfffu); n = (int)(hi >> 12);
+        if (n >= a.N || ct >= a.n_ct) continue;                // a table of another shape cannot send an access out of bounds
+    } else {
+        const int xcd = it & 7, j = it >> 3;
+        ct = j % a.n_ct;
+        int pt = (j / a.n_ct) * 8 + xcd;
+        if (pt >= n_pt) continue;
+        tx = pt % a.tiles_x; pt /= a.tiles_x;
+        ty = pt % a.tiles_y;
+        n = pt / a.tiles_y;
+    }
     const int oy0 = ty * TH, ox0 = tx * TW;
     const int iy0 = UP2 ? oy0 / 2 : oy0 * S - (HALO / 2), ix0 = UP2 ? ox0 / 2 : ox0 * S - (HALO / 2);
     const int co0 = ct * BN;
@@ -215,18 +243,22 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     }
     if (tid < BN / 4) s_bias[tid] = *(const float4 *)(a.bias + co0 + tid * 4);   // (visible by the chunk barriers; the previous tile's
     f32x16 acc[MB][NB];                                                           //  readers are behind its closing barrier)
+    if (!PEEL) {
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
+        for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
+            for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+    }
 
     const int n_chunks = a.Cin / KSTAGE;
     // one chunk: wait for it, let the next one stream into the other stage, multiply.  `buf` is a compile-time constant in
     // both call sites (the loop is unrolled by two) so that every LDS address is an immediate offset.
-    auto chunk_step = [&](int c, auto buf_tag) {
+    // FIRST: the peeled chunk 0 of an item (OPT_PEEL only)
+    auto chunk_step = [&](int c, auto buf_tag, auto first_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
+        constexpr bool FIRST = decltype(first_tag)::value;
         // chunk c has landed: this wave's DMA is waited for by hand, the barrier covers the other waves' and also
         // says that every wave is done reading the other stage
 #ifdef HVPR_EXP_TIMING
@@ -275,7 +307,9 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     if (UP2 && !up2_uses(mb, tap)) continue;
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].x, av[cur][mb].x, acc[mb][nb], 0, 0, 0);
+                    // tap 0 of chunk 0: 0 + a b is what the cleared block gave, the accumulators are born here
+                    if (PEEL && FIRST && tap == 0) acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].x, av[cur][mb].x, f32x16{}, 0, 0, 0);
+                    else acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].x, av[cur][mb].x, acc[mb][nb], 0, 0, 0);
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].y, av[cur][mb].y, acc[mb][nb], 0, 0, 0);
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].z, av[cur][mb].z, acc[mb][nb], 0, 0, 0);
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][nb].w, av[cur][mb].w, acc[mb][nb], 0, 0, 0);
@@ -289,7 +323,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
             }
         }
 #ifdef HVPR_EXP_TIMING
-        if (dbg_slot >= 0 && dbg_tile == 1 && lane == 0 && c < 64) {
+        if (dbg_slot >= 0 && dbg_tile == 1 && c < 64) {      // a uniform branch: every lane stores the same words
             asm volatile("" ::"v"(acc[0][0][0]));
             long long *d = g_conv_dbg + (((size_t)dbg_slot * 4 + wid) * 64 + c) * 4;
             d[0] = q0; d[1] = q1; d[2] = q2; d[3] = __builtin_readcyclecounter();
@@ -297,11 +331,20 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
 #endif
     };
     stage(0, 0);
-    for (int c = 0; c + 1 < n_chunks; c += 2) {        // straight-line body: no accumulator shuffling at a join
-        chunk_step(c, std::integral_constant<int, 0>{});
-        chunk_step(c + 1, std::integral_constant<int, 1>{});
+    if constexpr (PEEL) {
+        chunk_step(0, std::integral_constant<int, 0>{}, std::true_type{});        // chunk c multiplies stage c & 1, as below
+        for (int c = 1; c + 1 < n_chunks; c += 2) {
+            chunk_step(c, std::integral_constant<int, 1>{}, std::false_type{});
+            chunk_step(c + 1, std::integral_constant<int, 0>{}, std::false_type{});
+        }
+        if (!(n_chunks & 1)) chunk_step(n_chunks - 1, std::integral_constant<int, 1>{}, std::false_type{});
+    } else {
+        for (int c = 0; c + 1 < n_chunks; c += 2) {        // straight-line body: no accumulator shuffling at a join
+            chunk_step(c, std::integral_constant<int, 0>{}, std::false_type{});
+            chunk_step(c + 1, std::integral_constant<int, 1>{}, std::false_type{});
+        }
+        if (n_chunks & 1) chunk_step(n_chunks - 1, std::integral_constant<int, 0>{}, std::false_type{});
     }
-    if (n_chunks & 1) chunk_step(n_chunks - 1, std::integral_constant<int, 0>{});
 
     // ---- epilogue: bias (+ReLU) (+gate * y + residual), NHWC store.  The weights are the MFMA "A" operand, so a lane
     // holds ONE pixel (column lane&31 of the block) and 16 channels: rows (r&3) + 8*(r>>2) + 4*(lane>>5), i.e. four runs of
@@ -343,7 +386,36 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     }
 }
 
-template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false>
+// the table of OPT_TAB: entry `it` is what the kernel's own arithmetic decodes step `it` to, one thread per step
+__global__ void k_conv_tab(int N, int tiles_x, int tiles_y, int n_ct, int total_walk, unsigned long long *__restrict__ tab) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= total_walk) return;
+    const int xcd = it & 7, j = it >> 3;
+    const int ct = j % n_ct;
+    int pt = (j / n_ct) * 8 + xcd;
+    if (pt >= tiles_x * tiles_y * N) {
+        tab[it] = 1ull << 31;
+        return;
+    }
+    const int tx = pt % tiles_x; pt /= tiles_x;
+    const int ty = pt % tiles_y;
+    const int n = pt / tiles_y;
+    tab[it] = (unsigned long long)((unsigned)tx | (unsigned)ty << 16) | (unsigned long long)((unsigned)ct | (unsigned)n << 12) << 32;
+}
+
+// tile grid of a forward layer under tile_cfg -> walk steps (0: no table for it)
+static int conv_tab_grid(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg, int &tiles_x, int &tiles_y, int &n_ct) {
+    if (N < 1 || H < 1 || W < 1 || cout_pad < 1 || (taps != 9 && taps != 1) || (stride != 1 && stride != 2) || tile_cfg < 0 || tile_cfg > 2) return 0;
+    const int OH = taps == 9 ? (H + 2 - 3) / stride + 1 : H, OW = taps == 9 ? (W + 2 - 3) / stride + 1 : W;
+    const int tw = tile_cfg == 1 ? 8 : 16, bn = tile_cfg == 0 ? 128 : 64;
+    if (OH < 1 || OW < 1 || cout_pad % bn != 0) return 0;
+    tiles_x = (OW + tw - 1) / tw; tiles_y = (OH + 7) / 8; n_ct = cout_pad / bn;
+    if (tiles_x > TAB_MAX_TX || tiles_y > TAB_MAX_TY || n_ct > TAB_MAX_CT || N > TAB_MAX_N) return 0;
+    const long long steps = ((long long)N * tiles_x * tiles_y + 7) / 8 * 8 * n_ct;
+    return steps < (1ll << 28) ? (int)steps : 0;
+}
+
+template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, int OPT = 0>
 int launch(ConvArgs a, hipStream_t s) {
     a.tiles_x = (a.OW + TW - 1) / TW;
     a.tiles_y = (a.OH + TH - 1) / TH;
@@ -354,13 +426,13 @@ int launch(ConvArgs a, hipStream_t s) {
         int per_cu = 0, dev = 0, cus = 256;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv<TH, TW, BN, S, TAPS, UP2>, 256, 0) != hipSuccess || per_cu < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv<TH, TW, BN, S, TAPS, UP2, OPT>, 256, 0) != hipSuccess || per_cu < 1)
             per_cu = 1;
         resident = per_cu * cus;
     }
     long long blocks = tiles < resident ? (tiles + 7) / 8 * 8 : resident;   // a multiple of 8: workgroup id % 8 = its XCD
     if (blocks > resident && resident >= 8) blocks = resident / 8 * 8;
-    hipLaunchKernelGGL((k_conv<TH, TW, BN, S, TAPS, UP2>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_conv<TH, TW, BN, S, TAPS, UP2, OPT>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     return 0;
 }
 
@@ -387,16 +459,33 @@ extern "C" int hvpr_conv2d_s2_dgrad_nhwc_f32(const float *dz, int N, int H, int 
     a.OH = OH; a.OW = OW;
     a.cout_gemm = cout; a.cout_pad = cout_pad; a.cout_real = cout;
     a.out_cstride = out_cstride; a.out_coff = out_coff; a.resid_cstride = 0;
-    a.relu = 0; a.up = 1;
+    a.relu = 0; a.up = 1; a.tab = nullptr;
     launch<16, 16, 64, 1, 9, true>(a, (hipStream_t)stream);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }
 
-extern "C" int hvpr_conv2d_nhwc_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed,
-                                    const float *bias, int taps, int stride, int cout, int cout_pad, int up,
-                                    int relu, const float *gate, const float *resid, int resid_cstride, float *out,
-                                    int out_cstride, int out_coff, int tile_cfg, hvpr_stream_t stream) {
+// The walk table of a forward layer: bytes for a shape (0: no table for it), and the fill.
+extern "C" size_t hvpr_conv2d_tab_bytes(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg) {
+    int tiles_x, tiles_y, n_ct;
+    return (size_t)conv_tab_grid(N, H, W, taps, stride, cout_pad, tile_cfg, tiles_x, tiles_y, n_ct) * sizeof(unsigned long long);
+}
+
+extern "C" int hvpr_conv2d_tab_build(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg, void *table, hvpr_stream_t stream) {
+    if (!table) return HVPR_ERR_INVALID_ARG;
+    int tiles_x, tiles_y, n_ct;
+    const int steps = conv_tab_grid(N, H, W, taps, stride, cout_pad, tile_cfg, tiles_x, tiles_y, n_ct);
+    if (steps == 0) return HVPR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_conv_tab, dim3(hvpr_cdiv(steps, 256)), dim3(256), 0, (hipStream_t)stream, N, tiles_x, tiles_y, n_ct, steps,
+                       (unsigned long long *)table);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+static int conv_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_packed,
+                     const float *bias, int taps, int stride, int cout, int cout_pad, int up,
+                     int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                     int out_cstride, int out_coff, int tile_cfg, const void *table, hvpr_stream_t stream) {
     if (!in || !w_packed || !bias || !out || N < 1 || H < 1 || W < 1 || Cin < 8 || cout < 1) return HVPR_ERR_INVALID_ARG;
     if ((gate == nullptr) != (resid == nullptr)) return HVPR_ERR_INVALID_ARG;
     if (Cin % KC != 0 || (taps != 9 && taps != 1) || (stride != 1 && stride != 2) || up < 1) return HVPR_ERR_UNSUPPORTED;
@@ -415,21 +504,44 @@ extern "C" int hvpr_conv2d_nhwc_f32(const float *in, int N, int H, int W, int Ci
     a.cout_pad = cout_pad; a.cout_real = cout;
     a.out_cstride = out_cstride; a.out_coff = out_coff; a.resid_cstride = resid_cstride;
     a.relu = relu; a.up = up;
+    a.tab = (HVPR_ITEM_OPT & OPT_TAB) ? (const unsigned long long *)table : nullptr;
     if (cout_pad < a.cout_gemm) return HVPR_ERR_INVALID_ARG;
+    if (table && hvpr_conv2d_tab_bytes(N, H, W, taps, stride, cout_pad, tile_cfg) == 0) return HVPR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     // tile_cfg: 0 = 128 px x 128 ch, 1 = 64 px x 64 ch, 2 = 128 px x 64 ch
     const int bn = tile_cfg == 0 ? 128 : 64;
     if (cout_pad % bn != 0) return HVPR_ERR_INVALID_ARG;
-#define HV_CASE(TH, TW, BN)                                                        \
-    if (taps == 9 && stride == 1) launch<TH, TW, BN, 1, 9>(a, s);                   \
-    else if (taps == 9 && stride == 2) launch<TH, TW, BN, 2, 9>(a, s);              \
-    else if (wide1x1) launch<TH, TW, BN, 1, 4>(a, s);                                \
-    else launch<TH, TW, BN, 1, 1>(a, s);
-    if (tile_cfg == 0) { HV_CASE(8, 16, 128) }
-    else if (tile_cfg == 1) { HV_CASE(8, 8, 64) }
-    else if (tile_cfg == 2) { HV_CASE(8, 16, 64) }
+    constexpr int OPT0 = HVPR_ITEM_OPT & ~OPT_TAB;
+#define HV_CASE(TH, TW, BN, OPT)                                                    \
+    if (taps == 9 && stride == 1) launch<TH, TW, BN, 1, 9, false, OPT>(a, s);       \
+    else if (taps == 9 && stride == 2) launch<TH, TW, BN, 2, 9, false, OPT>(a, s);  \
+    else if (wide1x1) launch<TH, TW, BN, 1, 4, false, OPT>(a, s);                   \
+    else launch<TH, TW, BN, 1, 1, false, OPT>(a, s);
+#define HV_TILE(TH, TW, BN)                                                         \
+    if (a.tab) { HV_CASE(TH, TW, BN, OPT0 | OPT_TAB) } else { HV_CASE(TH, TW, BN, OPT0) }
+    if (tile_cfg == 0) { HV_TILE(8, 16, 128) }
+    else if (tile_cfg == 1) { HV_TILE(8, 8, 64) }
+    else if (tile_cfg == 2) { HV_TILE(8, 16, 64) }
     else return HVPR_ERR_INVALID_ARG;
+#undef HV_TILE
 #undef HV_CASE
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
+}
+
+extern "C" int hvpr_conv2d_nhwc_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed,
+                                    const float *bias, int taps, int stride, int cout, int cout_pad, int up,
+                                    int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                                    int out_cstride, int out_coff, int tile_cfg, hvpr_stream_t stream) {
+    return conv_nhwc(in, N, H, W, Cin, w_packed, bias, taps, stride, cout, cout_pad, up, relu, gate, resid, resid_cstride, out, out_cstride,
+                     out_coff, tile_cfg, nullptr, stream);
+}
+
+// as hvpr_conv2d_nhwc_f32 with the walk table of this shape (hvpr_conv2d_tab_build); null: the in-kernel decode
+extern "C" int hvpr_conv2d_nhwc_tab_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed,
+                                        const float *bias, int taps, int stride, int cout, int cout_pad, int up,
+                                        int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                                        int out_cstride, int out_coff, int tile_cfg, const void *table, hvpr_stream_t stream) {
+    return conv_nhwc(in, N, H, W, Cin, w_packed, bias, taps, stride, cout, cout_pad, up, relu, gate, resid, resid_cstride, out, out_cstride,
+                     out_coff, tile_cfg, table, stream);
 }

@@ -60,7 +60,27 @@ struct WinoArgs {
     WinoWalk walk;        // tile grid and edge pairing of this shape (wino_walk.h)
     int n_ct;
     float *stats;         // optional [pixel tiles][2][cout]: per-tile sum / sum of squares of the raw output (train-mode BatchNorm)
+    const WinoTabEntry *tab;   // OPT_TAB: one entry per walk step (k_wino_tab), else unused
 };
+
+// Per-item work outside the K loop that the eval-forward kernel (NG 1, NB 2, no statistics) can shed, each a compile-time switch
+// whose off state is the code every other instantiation runs:
+//   OPT_TAB   the item of a walk step comes from a table built once per shape instead of ~10 runtime integer divisions
+//   OPT_PEEL  chunk 0 is peeled and its first MFMA per accumulator block takes C = 0: no 128-register clear per item
+// (-DHVPR_ITEM_OPT=<bits> builds a library with another set, for measuring; a third switch, wave priority 1 outside the K loop, won
+// alone and lost beside these two and was removed: profiles/NOTES_r17.md §3)
+enum { OPT_TAB = 1, OPT_PEEL = 2 };
+#ifndef HVPR_ITEM_OPT
+#define HVPR_ITEM_OPT (OPT_TAB | OPT_PEEL)      // the kept set
+#endif
+
+// a table entry through the constant address space: the address is uniform, so this is one scalar 8-byte load
+__device__ __forceinline__ WinoTabEntry tab_load(const WinoTabEntry *tab, int step) {
+    const unsigned long long w = *((const __attribute__((address_space(4))) unsigned long long *)(size_t)tab + step);
+    WinoTabEntry e;
+    e.lo = (unsigned)w; e.hi = (unsigned)(w >> 32);
+    return e;
+}
 
 __device__ __forceinline__ float4 f4_fma(float s, float4 a, float4 b) {      // s * a + b, s = +-1: an exact add / subtract
     return make_float4(fmaf(s, a.x, b.x), fmaf(s, a.y, b.y), fmaf(s, a.z, b.z), fmaf(s, a.w, b.w));
@@ -68,8 +88,16 @@ __device__ __forceinline__ float4 f4_fma(float s, float4 a, float4 b) {      // 
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 
-template <int NG, bool STATS, int NB>
+#ifdef HVPR_EXP_TIMING
+// kernel experiments: cycle stamps of the first three items of a few workgroups (wave 0), read back by hvpr_exp_wino_dbg:
+// [block slot 0..7][item 0..2][4] = item entry, exit of the first chunk's barrier, end of the K loop, end of the item
+__device__ long long g_wino_dbg[8 * 3 * 4];
+#endif
+
+template <int NG, bool STATS, int NB, int OPT = 0>
 __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2, NB == 2 ? 2 : 3))) k_wino(WinoArgs a) {
+    static_assert(OPT == 0 || (NG == 1 && NB == 2 && !STATS), "the item switches belong to the eval-forward kernel");
+    constexpr bool TAB = (OPT & OPT_TAB) != 0, PEEL = (OPT & OPT_PEEL) != 0;
     constexpr int NT = 256 * NG;
     constexpr int TH = 8 * NG, PH = TH + 2;
     constexpr int PPAD = (PH * ROWP + 63) / 64 * 64;          // float4 per channel-half plane
@@ -121,11 +149,28 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     const int n_pt = a.walk.per_image * a.N;
     const int total_walk = ((n_pt + 7) / 8) * 8 * a.n_ct;
     const int n_chunks = a.Cin / KC;
+#ifdef HVPR_EXP_TIMING
+    int dbg_item = 0;
+    const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;
+    long long q_in = 0, q_first = 0, q_k = 0;
+#endif
+    WinoTabEntry e_next = {0u, 0u};                            // the next step's entry, in flight while this item multiplies
+    if (TAB && (int)blockIdx.x < total_walk) e_next = tab_load(a.tab, blockIdx.x);
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
-    int ct;
-    int pt = wino_walk_step(it, a.n_ct, ct);
-    if (pt >= n_pt) continue;
+#ifdef HVPR_EXP_TIMING
+    q_in = __builtin_readcyclecounter();
+#endif
+    int ct, pt = 0;
     int tx, ty, n, mode = WINO_SINGLE;
+    if constexpr (TAB) {
+        const WinoTabEntry e = e_next;
+        if (it + (int)gridDim.x < total_walk) e_next = tab_load(a.tab, it + (int)gridDim.x);
+        if (wino_tab_hole(e)) continue;
+        tx = wino_tab_tx(e); ty = wino_tab_ty(e); mode = wino_tab_mode(e); ct = wino_tab_ct(e); n = wino_tab_n(e);
+        if (n >= a.N || ct >= a.n_ct) continue;                // a table of another shape cannot send an access out of bounds
+    } else {
+    pt = wino_walk_step(it, a.n_ct, ct);
+    if (pt >= n_pt) continue;
     if constexpr (PAIR) {
         const WinoItem w = wino_walk_item(a.walk, pt);
         tx = w.tx; ty = w.ty; n = w.n; mode = w.mode;
@@ -133,6 +178,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         tx = pt % a.walk.tiles_x; pt /= a.walk.tiles_x;
         ty = pt % a.walk.tiles_y;
         n = pt / a.walk.tiles_y;
+    }
     }
     // tile B of a pair: its patch sits 10 columns right of / 6 rows below A's in LDS, its pixels TH rows below / TW columns right of A's
     const bool pr = PAIR && mode == WINO_PAIR_RIGHT, pb = PAIR && mode == WINO_PAIR_BOTTOM;
@@ -188,17 +234,24 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     static_assert(BIAS_SLOT + BNT / 4 <= PPAD, "room for the bias row behind the patch");
     if (tid < BNT / 4) s_patch[BIAS_SLOT + tid] = *(const float4 *)(a.bias + co0 + tid * 4);
     f32x16 acc[4][NB];
+    if (!PEEL) {
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+        for (int b = 0; b < 4; ++b)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
+            for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[b][nb][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[b][nb][r] = 0.f;
+    }
 
-    auto chunk_step = [&](int c, auto buf_tag) {
+    // FIRST: the peeled chunk 0 of an item (OPT_PEEL only)
+    auto chunk_step = [&](int c, auto buf_tag, auto first_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
+        constexpr bool FIRST = decltype(first_tag)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
+#ifdef HVPR_EXP_TIMING
+        if (c == 0) q_first = __builtin_readcyclecounter();
+#endif
         const float4 *sp = s_patch + BUF * PATCH_PAD;
         const float4 *sw = s_w + BUF * W_V4T;
         float4 d0[4], d1[4], u[4][NB];
@@ -227,7 +280,9 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].x, v[b].x, acc[b][nb], 0, 0, 0);
+                // 0 + u v is what the cleared block gave: the accumulators are born here
+                if constexpr (PEEL && FIRST) acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].x, v[b].x, f32x16{}, 0, 0, 0);
+                else acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].x, v[b].x, acc[b][nb], 0, 0, 0);
                 acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].y, v[b].y, acc[b][nb], 0, 0, 0);
                 acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].z, v[b].z, acc[b][nb], 0, 0, 0);
                 acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][nb].w, v[b].w, acc[b][nb], 0, 0, 0);
@@ -249,12 +304,26 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         }
     };
     stage(0, 0);
-    for (int c = 0; c + 1 < n_chunks; c += 2) {
-        chunk_step(c, std::integral_constant<int, 0>{});
-        chunk_step(c + 1, std::integral_constant<int, 1>{});
+    if constexpr (PEEL) {
+        // chunk c multiplies stage c & 1, as below
+        chunk_step(0, std::integral_constant<int, 0>{}, std::true_type{});
+        for (int c = 1; c + 1 < n_chunks; c += 2) {
+            chunk_step(c, std::integral_constant<int, 1>{}, std::false_type{});
+            chunk_step(c + 1, std::integral_constant<int, 0>{}, std::false_type{});
+        }
+        if (!(n_chunks & 1)) chunk_step(n_chunks - 1, std::integral_constant<int, 1>{}, std::false_type{});
+    } else {
+        for (int c = 0; c + 1 < n_chunks; c += 2) {
+            chunk_step(c, std::integral_constant<int, 0>{}, std::false_type{});
+            chunk_step(c + 1, std::integral_constant<int, 1>{}, std::false_type{});
+        }
+        if (n_chunks & 1) chunk_step(n_chunks - 1, std::integral_constant<int, 0>{}, std::false_type{});
     }
-    if (n_chunks & 1) chunk_step(n_chunks - 1, std::integral_constant<int, 0>{});
 
+#ifdef HVPR_EXP_TIMING
+    asm volatile("" ::"v"(acc[3][NB - 1][15]));
+    q_k = __builtin_readcyclecounter();
+#endif
     // ---- output transform + epilogue.  A lane holds block l31 and 16 channels per accumulator block (rows (r&3) + 8*(r>>2) +
     // 4*half: four runs of four).  Exchange area (float4): [grp][a][q][channel half of the pass][run][lane]. ----
     const int p = wa >> 1, q = wa & 1;
@@ -344,6 +413,13 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         }
     }
     __syncthreads();   // the next tile refills the LDS stages
+#ifdef HVPR_EXP_TIMING
+    if (dbg_slot >= 0 && dbg_item < 3 && tid == 0) {
+        long long *d = g_wino_dbg + (dbg_slot * 3 + dbg_item) * 4;
+        d[0] = q_in; d[1] = q_first; d[2] = q_k; d[3] = __builtin_readcyclecounter();
+    }
+    ++dbg_item;
+#endif
     }
 }
 
@@ -381,7 +457,14 @@ __global__ void k_wino_pack(const float *__restrict__ w, const float *__restrict
     }
 }
 
-template <int NG, bool STATS, int NB>
+// the table of OPT_TAB: entry `it` is what step `it` of the walk decodes to (wino_walk.h as it stands), one thread per step
+__global__ void k_wino_tab(WinoWalk walk, int N, int n_ct, int total_walk, WinoTabEntry *__restrict__ tab) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= total_walk) return;
+    tab[it] = wino_tab_entry(walk, N, n_ct, it);
+}
+
+template <int NG, bool STATS, int NB, int OPT = 0>
 int launch(WinoArgs a, hipStream_t s) {
     constexpr int NT = 256 * NG, TH = 8 * NG, PH = TH + 2;
     constexpr int PPAD = (PH * ROWP + 63) / 64 * 64;
@@ -390,23 +473,33 @@ int launch(WinoArgs a, hipStream_t s) {
     a.walk = wino_walk_make(a.H, a.W, TH, NG == 1 && NB == 2 && !STATS);
     a.n_ct = a.cout_pad / (32 * NB);
     static unsigned long long lds_set = 0ull;
-    if (hvpr_ensure_dyn_lds((const void *)k_wino<NG, STATS, NB>, lds, &lds_set) != 0) return -1;
+    if (hvpr_ensure_dyn_lds((const void *)k_wino<NG, STATS, NB, OPT>, lds, &lds_set) != 0) return -1;
     const long long tiles = (long long)a.N * a.walk.per_image * a.n_ct;
     static int resident = 0;
     if (resident == 0) {
         int per_cu = 0, dev = 0, cus = 256;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wino<NG, STATS, NB>, NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wino<NG, STATS, NB, OPT>, NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
         resident = per_cu * cus;
     }
     long long blocks = tiles < resident ? (tiles + 7) / 8 * 8 : resident;
     if (blocks > resident && resident >= 8) blocks = resident / 8 * 8;
-    hipLaunchKernelGGL((k_wino<NG, STATS, NB>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL((k_wino<NG, STATS, NB, OPT>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
     return 0;
 }
 
 }  // namespace
+
+#ifdef HVPR_EXP_TIMING
+extern "C" int hvpr_exp_wino_dbg(long long *host_out, int n_words, int clear) {
+    if (clear) {
+        const long long zeros[8 * 3 * 4] = {0};
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_wino_dbg), zeros, sizeof(zeros)) == hipSuccess ? 0 : -1;
+    }
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wino_dbg), sizeof(long long) * n_words) == hipSuccess ? 0 : -1;
+}
+#endif
 
 extern "C" int hvpr_conv2d_wino_stats_rows(int N, int H, int W) {     // rows of bn_partials: the 8 x 16 pixel tiles
     if (N < 1 || H < 1 || W < 1) return 0;
@@ -437,9 +530,29 @@ extern "C" int hvpr_conv2d_wino_pack_f32(const float *weight, const float *scale
     return HVPR_OK;
 }
 
-extern "C" int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias,
-                                         int cout, int relu, const float *gate, const float *resid, int resid_cstride, float *out,
-                                         int out_cstride, int out_coff, int px_groups, float *bn_partials, hvpr_stream_t stream) {
+// The walk table of the eval-forward kernel (px_groups 1, no statistics): bytes for a shape (0: no table for it), and the fill.
+extern "C" size_t hvpr_conv2d_wino_tab_bytes(int N, int H, int W, int cout, int px_groups) {
+    if (N < 1 || H < 1 || W < 1 || cout < 1 || px_groups != 1 || N > WINO_TAB_MAX_N) return 0;
+    const WinoWalk w = wino_walk_make(H, W, 8, 1);
+    const int n_ct = (cout + BN - 1) / BN;
+    if (w.tiles_x > WINO_TAB_MAX_TILES || w.tiles_y > WINO_TAB_MAX_TILES || n_ct > WINO_TAB_MAX_CT) return 0;
+    const long long steps = ((long long)N * w.per_image + 7) / 8 * 8 * n_ct;
+    return steps < (1ll << 28) ? (size_t)steps * sizeof(WinoTabEntry) : 0;
+}
+
+extern "C" int hvpr_conv2d_wino_tab_build(int N, int H, int W, int cout, int px_groups, void *table, hvpr_stream_t stream) {
+    if (!table) return HVPR_ERR_INVALID_ARG;
+    if (hvpr_conv2d_wino_tab_bytes(N, H, W, cout, px_groups) == 0) return HVPR_ERR_UNSUPPORTED;
+    const WinoWalk w = wino_walk_make(H, W, 8, 1);
+    const int n_ct = (cout + BN - 1) / BN, steps = wino_walk_steps(w, N, n_ct);
+    hipLaunchKernelGGL(k_wino_tab, dim3(hvpr_cdiv(steps, 256)), dim3(256), 0, (hipStream_t)stream, w, N, n_ct, steps, (WinoTabEntry *)table);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+static int wino_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias,
+                     int cout, int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                     int out_cstride, int out_coff, int px_groups, float *bn_partials, const void *table, hvpr_stream_t stream) {
     if (!in || !w_packed || !bias || !out || N < 1 || H < 1 || W < 1 || Cin < 8 || cout < 1) return HVPR_ERR_INVALID_ARG;
     if ((gate == nullptr) != (resid == nullptr)) return HVPR_ERR_INVALID_ARG;
     if (Cin % KC != 0) return HVPR_ERR_UNSUPPORTED;
@@ -452,13 +565,33 @@ extern "C" int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, i
     a.out_cstride = out_cstride; a.out_coff = out_coff; a.resid_cstride = resid_cstride;
     a.relu = relu;
     a.stats = bn_partials;
+    a.tab = (HVPR_ITEM_OPT & OPT_TAB) ? (const WinoTabEntry *)table : nullptr;
+    if (table && (px_groups != 1 || bn_partials || hvpr_conv2d_wino_tab_bytes(N, H, W, cout, px_groups) == 0)) return HVPR_ERR_UNSUPPORTED;
     if (bn_partials && (px_groups != 1 || relu || gate)) return HVPR_ERR_UNSUPPORTED;      // statistics of the RAW output, 8 x 16 tiles
     int rc;
-    if (px_groups == 1) rc = bn_partials ? launch<1, true, 2>(a, (hipStream_t)stream) : launch<1, false, 2>(a, (hipStream_t)stream);
+    constexpr int OPT0 = HVPR_ITEM_OPT & ~OPT_TAB;
+    if (px_groups == 1 && bn_partials) rc = launch<1, true, 2>(a, (hipStream_t)stream);
+    else if (px_groups == 1) rc = a.tab ? launch<1, false, 2, OPT0 | OPT_TAB>(a, (hipStream_t)stream) : launch<1, false, 2, OPT0>(a, (hipStream_t)stream);
     else if (px_groups == 2) rc = launch<2, false, 2>(a, (hipStream_t)stream);
     else if (px_groups == 4) rc = launch<1, false, 1>(a, (hipStream_t)stream);      // 8 x 16 px x 32 channels: twice the tiles
     else return HVPR_ERR_INVALID_ARG;
     if (rc != 0) return HVPR_ERR_LAUNCH;
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
+}
+
+extern "C" int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias,
+                                         int cout, int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                                         int out_cstride, int out_coff, int px_groups, float *bn_partials, hvpr_stream_t stream) {
+    return wino_nhwc(in, N, H, W, Cin, w_packed, bias, cout, relu, gate, resid, resid_cstride, out, out_cstride, out_coff, px_groups,
+                     bn_partials, nullptr, stream);
+}
+
+// as hvpr_conv2d_wino_nhwc_f32 with the walk table of this (N, H, W, cout) (hvpr_conv2d_wino_tab_build); null: the in-kernel decode
+extern "C" int hvpr_conv2d_wino_nhwc_tab_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias,
+                                             int cout, int relu, const float *gate, const float *resid, int resid_cstride, float *out,
+                                             int out_cstride, int out_coff, int px_groups, float *bn_partials, const void *table,
+                                             hvpr_stream_t stream) {
+    return wino_nhwc(in, N, H, W, Cin, w_packed, bias, cout, relu, gate, resid, resid_cstride, out, out_cstride, out_coff, px_groups,
+                     bn_partials, table, stream);
 }

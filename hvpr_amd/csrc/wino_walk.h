@@ -75,3 +75,33 @@ HVPR_WALK_HD WinoItem wino_walk_item(const WinoWalk &w, int pt) {
     }
     return it;
 }
+
+// The walk as a TABLE, one 8-byte entry per step, built once per (N, H, W, cout) so that a workgroup reads its item instead of
+// dividing for it:   lo = tx [0..11] | ty [12..23] | mode [24..25] | hole [31]      hi = ct [0..11] | n [12..31]
+// A hole is a step of the last round that has no item.
+struct WinoTabEntry {
+    unsigned lo, hi;
+};
+enum { WINO_TAB_MAX_TILES = 4096, WINO_TAB_MAX_CT = 4096, WINO_TAB_MAX_N = 1 << 20 };
+
+HVPR_WALK_HD int wino_walk_steps(const WinoWalk &w, int N, int n_ct) { return (N * w.per_image + 7) / 8 * 8 * n_ct; }
+
+HVPR_WALK_HD WinoTabEntry wino_tab_entry(const WinoWalk &w, int N, int n_ct, int it) {
+    WinoTabEntry e;
+    int ct;
+    const int pt = wino_walk_step(it, n_ct, ct);
+    if (pt >= N * w.per_image) {
+        e.lo = 1u << 31; e.hi = 0u;
+        return e;
+    }
+    const WinoItem i = wino_walk_item(w, pt);
+    e.lo = (unsigned)i.tx | (unsigned)i.ty << 12 | (unsigned)i.mode << 24;
+    e.hi = (unsigned)ct | (unsigned)i.n << 12;
+    return e;
+}
+HVPR_WALK_HD bool wino_tab_hole(WinoTabEntry e) { return (e.lo >> 31) != 0u; }
+HVPR_WALK_HD int wino_tab_tx(WinoTabEntry e) { return (int)(e.lo & 4095u); }
+HVPR_WALK_HD int wino_tab_ty(WinoTabEntry e) { return (int)(e.lo >> 12 & 4095u); }
+HVPR_WALK_HD int wino_tab_mode(WinoTabEntry e) { return (int)(e.lo >> 24 & 3u); }
+HVPR_WALK_HD int wino_tab_ct(WinoTabEntry e) { return (int)(e.hi & 4095u); }
+HVPR_WALK_HD int wino_tab_n(WinoTabEntry e) { return (int)(e.hi >> 12); }

@@ -500,11 +500,12 @@ def canvas_buffers(batch, nx, ny, device):
 class PackedConv:
     """Weights of one conv layer in the kernel's layout [taps, Cin/8, 2, cout_pad, 4] with BatchNorm folded."""
 
-    __slots__ = ("w", "bias", "taps", "stride", "cout", "cout_pad", "up", "cin", "relu", "tile_cfg")
+    __slots__ = ("w", "bias", "taps", "stride", "cout", "cout_pad", "up", "cin", "relu", "tile_cfg", "tabs")
 
     def __init__(self, w, bias, taps, stride, cout, cout_pad, up, cin, relu, tile_cfg):
         self.w, self.bias, self.taps, self.stride = w, bias, taps, stride
         self.cout, self.cout_pad, self.up, self.cin, self.relu, self.tile_cfg = cout, cout_pad, up, cin, relu, tile_cfg
+        self.tabs = {}        # walk tables by (N, H, W): _walk_table
 
 
 def _tile_channels(tile_cfg):
@@ -537,11 +538,37 @@ _zero_bias = {}
 class PackedConvWino:
     """Stride-1 3x3 conv weights in the Winograd kernel's stage image (hvpr_conv2d_wino_pack_f32) with BatchNorm folded."""
 
-    __slots__ = ("w", "bias", "cout", "cout_pad", "cin", "relu", "px_groups")
+    __slots__ = ("w", "bias", "cout", "cout_pad", "cin", "relu", "px_groups", "tabs")
     taps, stride, up = 9, 1, 1
 
     def __init__(self, w, bias, cout, cout_pad, cin, relu, px_groups):
         self.w, self.bias, self.cout, self.cout_pad, self.cin, self.relu, self.px_groups = w, bias, cout, cout_pad, cin, relu, px_groups
+        self.tabs = {}        # walk tables by (N, H, W): _walk_table
+
+
+def _walk_table(pc, N, H, W, device):
+    """Address of the packed layer's walk table for (N, H, W) — the items of the persistent kernel's walk, read instead of divided
+    for — or 0 (the in-kernel decode).  The table is a tensor on the packed-layer object, built by the first eager call with the
+    shape, so it lives as long as the packed weights a captured graph bakes in; a call inside a capture that finds none passes 0
+    and neither allocates nor launches the builder."""
+    key = (N, H, W)
+    t = pc.tabs.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            return 0
+        if isinstance(pc, PackedConvWino):
+            shape = (N, H, W, pc.cout, pc.px_groups)
+            size, build = lib().hvpr_conv2d_wino_tab_bytes, lib().hvpr_conv2d_wino_tab_build
+        else:
+            shape = (N, H, W, pc.taps, pc.stride, pc.cout_pad, pc.tile_cfg)
+            size, build = lib().hvpr_conv2d_tab_bytes, lib().hvpr_conv2d_tab_build
+        nbytes = size(*shape)
+        t = torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+        if nbytes:
+            check(build(*shape, t.data_ptr(), _stream()), "walk table build")
+            torch.cuda.current_stream().synchronize()      # once per layer and shape: later calls may come on any stream
+        pc.tabs[key] = t
+    return t.data_ptr() if t.numel() else 0
 
 
 def pack_conv_wino(weight, scale=None, shift=None, relu=True, px_groups=1, adjoint=False):
@@ -568,19 +595,23 @@ def pack_conv_wino(weight, scale=None, shift=None, relu=True, px_groups=1, adjoi
     return PackedConvWino(wp, b, cout, cout_pad, cin, relu, px_groups)
 
 
-def conv2d_wino_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None, bn_partials=None):
+def conv2d_wino_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None, bn_partials=None, use_table=False):
     """x (N,H,W,Cin) contiguous f32 -> (N,H,W,C): 3x3 / stride 1 / pad 1 by Winograd F(2x2,3x3); arguments as conv2d_nhwc.
+    use_table: read the walk's items from the layer's table (_walk_table) where the kernel takes one — for layers that are packed
+    once and called many times (eval); False: the in-kernel decode.
     bn_partials: (hvpr_conv2d_wino_stats_rows(N,H,W), 2, C) f32 to receive the per-tile sums of the raw output (training)."""
     N, H, W, cin = x.shape
     assert cin == pc.cin
     if out is None:
         out = torch.empty((N, H, W, pc.cout), dtype=torch.float32, device=x.device)
     assert out.shape[:3] == (N, H, W) and out.is_contiguous()
-    check(lib().hvpr_conv2d_wino_nhwc_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(), pc.bias.data_ptr(),
-                                          pc.cout, 1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
-                                          _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
-                                          out.data_ptr(), out.shape[-1], int(out_coff), pc.px_groups,
-                                          _ptr(bn_partials, torch.float32, "bn_partials"), _stream()), "hvpr_conv2d_wino_nhwc_f32")
+    tab = _walk_table(pc, N, H, W, x.device) if use_table and bn_partials is None and pc.px_groups == 1 else 0
+    check(lib().hvpr_conv2d_wino_nhwc_tab_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(), pc.bias.data_ptr(),
+                                              pc.cout, 1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
+                                              _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
+                                              out.data_ptr(), out.shape[-1], int(out_coff), pc.px_groups,
+                                              _ptr(bn_partials, torch.float32, "bn_partials"), tab, _stream()),
+          "hvpr_conv2d_wino_nhwc_tab_f32")
     return out
 
 
@@ -618,7 +649,7 @@ def pack_conv_auto(weight, scale=None, shift=None, stride=1, relu=True, tile_cfg
     return pack_conv(weight, scale, shift, stride=stride, relu=relu, tile_cfg=tile_cfg)
 
 
-def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None):
+def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None, use_table=False):
     """x (N,H,W,Cin) contiguous f32 -> (N,OH*up,OW*up,C) ; optional fused y = gate*y + resid (SFM step).  The packed type selects the
     kernel.  A PackedConvBf3 takes split-bf16 activations (split_bf16) and returns them, or fp32 when pc.out_split is off or it is
     a deconvolution; split-bf16 activations handed to an fp32 layer are recombined first."""
@@ -631,7 +662,7 @@ def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None):
     if x.dtype == torch.bfloat16:
         x = unsplit_bf16(x)
     if isinstance(pc, PackedConvWino):
-        return conv2d_wino_nhwc(x, pc, out=out, out_coff=out_coff, gate=gate, resid=resid)
+        return conv2d_wino_nhwc(x, pc, out=out, out_coff=out_coff, gate=gate, resid=resid, use_table=use_table)
     N, H, W, cin = x.shape
     assert cin == pc.cin
     if pc.taps == 9:
@@ -641,12 +672,13 @@ def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None):
     if out is None:
         out = torch.empty((N, OH * pc.up, OW * pc.up, pc.cout), dtype=torch.float32, device=x.device)
     assert out.shape[:3] == (N, OH * pc.up, OW * pc.up) and out.is_contiguous()
-    check(lib().hvpr_conv2d_nhwc_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(),
-                                     pc.bias.data_ptr(), pc.taps, pc.stride, pc.cout, pc.cout_pad, pc.up,
-                                     1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
-                                     _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
-                                     out.data_ptr(), out.shape[-1], int(out_coff), pc.tile_cfg, _stream()),
-          "hvpr_conv2d_nhwc_f32")
+    tab = _walk_table(pc, N, H, W, x.device) if use_table else 0
+    check(lib().hvpr_conv2d_nhwc_tab_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(),
+                                         pc.bias.data_ptr(), pc.taps, pc.stride, pc.cout, pc.cout_pad, pc.up,
+                                         1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
+                                         _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
+                                         out.data_ptr(), out.shape[-1], int(out_coff), pc.tile_cfg, tab, _stream()),
+          "hvpr_conv2d_nhwc_tab_f32")
     return out
 
 

@@ -234,6 +234,17 @@ int hvpr_conv2d_nhwc_f32(const float *in, int N, int H, int W, int Cin, const fl
                          int taps, int stride, int cout, int cout_pad, int up, int relu, const float *gate,
                          const float *resid, int resid_cstride, float *out, int out_cstride, int out_coff,
                          int tile_cfg, hvpr_stream_t stream);
+/* Walk table (optional).  A workgroup of the persistent kernel otherwise derives every item (image, pixel tile, channel tile) of its
+ * walk by integer divisions; a table holds them, one 8-byte entry per walk step, built once per (N, H, W, taps, stride, cout_pad,
+ * tile_cfg) into caller-owned device memory of hvpr_conv2d_tab_bytes bytes (0: no table for these arguments) by
+ * hvpr_conv2d_tab_build.  hvpr_conv2d_nhwc_tab_f32 is hvpr_conv2d_nhwc_f32 with `table` = the table of exactly this shape, or NULL
+ * for the in-kernel decode; the result is bit-identical either way.  The table must stay valid until the launch has run. */
+size_t hvpr_conv2d_tab_bytes(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg);
+int hvpr_conv2d_tab_build(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg, void *table, hvpr_stream_t stream);
+int hvpr_conv2d_nhwc_tab_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias,
+                             int taps, int stride, int cout, int cout_pad, int up, int relu, const float *gate,
+                             const float *resid, int resid_cstride, float *out, int out_cstride, int out_coff,
+                             int tile_cfg, const void *table, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a5  SpatialAttention gate.  Replaces ChannelPool + ConvLayer(2->1, 3x3, bias) + BatchNorm + sigmoid of
@@ -664,6 +675,15 @@ int hvpr_conv2d_wino_nhwc_f32(const float *in, int N, int H, int W, int Cin, con
  * (count = N * H * W; sums finished in double, fixed order: deterministic). */
 int hvpr_conv2d_wino_stats_rows(int N, int H, int W);
 int hvpr_conv2d_wino_items(int N, int H, int W, int cout, int px_groups);
+/* Walk table of the px_groups == 1 launch without bn_partials, as for hvpr_conv2d_nhwc_tab_f32: hvpr_conv2d_wino_tab_bytes bytes (0
+ * for every other px_groups: no table) filled once per (N, H, W, cout) by hvpr_conv2d_wino_tab_build, one 8-byte entry per walk step
+ * (hvpr_conv2d_wino_items rounded up to whole rounds of 8 pixel items: csrc/wino_walk.h); hvpr_conv2d_wino_nhwc_tab_f32 is
+ * hvpr_conv2d_wino_nhwc_f32 with `table` = that table or NULL (the in-kernel decode), bit-identical either way. */
+size_t hvpr_conv2d_wino_tab_bytes(int N, int H, int W, int cout, int px_groups);
+int hvpr_conv2d_wino_tab_build(int N, int H, int W, int cout, int px_groups, void *table, hvpr_stream_t stream);
+int hvpr_conv2d_wino_nhwc_tab_f32(const float *in, int N, int H, int W, int Cin, const float *w_packed, const float *bias, int cout,
+                                  int relu, const float *gate, const float *resid, int resid_cstride, float *out, int out_cstride,
+                                  int out_coff, int px_groups, float *bn_partials, const void *table, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a5 optional precision modes: 3x3 convolutions on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulation)

@@ -21,6 +21,7 @@ for (H, W, C) in [(248, 296, 128), (124, 148, 256), (62, 74, 512)]:
                      ("direct_128x64", lambda: kernels.conv2d_nhwc(x, kernels_pd[2])),
                      ("direct_128x128", lambda: kernels.conv2d_nhwc(x, kernels_pd[0])),
                      ("wino_g1", lambda: kernels.conv2d_wino_nhwc(x, pw[1])),
+                     ("wino_g1_table", lambda: kernels.conv2d_wino_nhwc(x, pw[1], use_table=True)),
                      ("wino_g2", lambda: kernels.conv2d_wino_nhwc(x, pw[2])),
                      ("wino_c32", lambda: kernels.conv2d_wino_nhwc(x, pw[4]))]:
         for _ in range(3):
