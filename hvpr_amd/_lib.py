@@ -55,6 +55,7 @@ SIGNATURES = {
     "hvpr_nms_bev_batched_workspace_bytes": (_Z, [_I, _I]),
     "hvpr_nms_bev_batched_f32": (_I, [_P, _I, _c.c_longlong, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]),
     "hvpr_gather_predictions_batched_f32": (_I, [_P, _I, _c.c_longlong, _I, _P, _P, _c.c_longlong, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "hvpr_gather_predictions_multiclass_f32": (_I, [_P, _I, _c.c_longlong, _P, _c.c_longlong, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "hvpr_furthest_point_sample_f32": (_I, [_P, _I, _I, _I, _P, _P]),
     "hvpr_ball_query_f32": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P]),
     "hvpr_three_nn_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),

@@ -232,6 +232,13 @@ class AugmentPlanner:
     def num_groups(self):
         return len(self.groups)
 
+    def reset(self):
+        """The sampler's per-class state as the constructor leaves it (database_sampler.py:31-40): what a freshly forked worker
+        of the reference starts an epoch with."""
+        for cname, grp in self.groups.items():
+            n = len(self.bank.class_ids[cname])
+            grp.update(sample_num=self.sample_class_num[cname], pointer=n, indices=np.arange(n))
+
     def _sample_with_fixed_number(self, class_name, grp, rng):
         """database_sampler.py:79-96, returning indices into the class list."""
         sample_num, pointer, indices = int(grp["sample_num"]), grp["pointer"], grp["indices"]

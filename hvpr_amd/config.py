@@ -59,6 +59,47 @@ def cfg_from_yaml_file(cfg_file, config=None):
     return _merge(config, new, os.path.dirname(os.path.dirname(os.path.abspath(cfg_file))))
 
 
+def _literal(text):
+    import ast
+    try:
+        return ast.literal_eval(text)
+    except (ValueError, SyntaxError):
+        return text
+
+
+def cfg_from_list(cfg_list, config):
+    """`--set KEY VALUE ...` (pcdet/config.py:24-48): KEY is a dotted path that must exist; VALUE is read as a Python literal (a bare
+    word stays a string) and must have the type of the value it replaces.  A value for a list may be written `a,b,c`; its items
+    take the type of the list's first item.  An int is taken for a float."""
+    if len(cfg_list) % 2 != 0:
+        raise ValueError("--set takes KEY VALUE pairs")
+    for key, text in zip(cfg_list[0::2], cfg_list[1::2]):
+        d = config
+        parts = key.split(".")
+        for p in parts[:-1]:
+            if not isinstance(d, dict) or p not in d:
+                raise KeyError(f"--set {key}: no such key")
+            d = d[p]
+        last = parts[-1]
+        if not isinstance(d, dict) or last not in d:
+            raise KeyError(f"--set {key}: no such key")
+        old = d[last]
+        new = _literal(text) if isinstance(text, str) else text
+        if isinstance(old, dict):
+            raise TypeError(f"--set {key}: a block cannot be replaced, set its keys")
+        if isinstance(old, list) and isinstance(new, str):
+            items = new.split(",")
+            new = [type(old[0])(_literal(x)) for x in items] if old else [_literal(x) for x in items]
+        if isinstance(new, tuple):
+            new = list(new)
+        if isinstance(old, float) and isinstance(new, int) and not isinstance(new, bool):
+            new = float(new)
+        if old is not None and type(new) is not type(old):
+            raise TypeError(f"--set {key}: {type(new).__name__} given for a {type(old).__name__}")
+        d[last] = new
+    return config
+
+
 CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfgs")
 
 

@@ -396,7 +396,69 @@ __global__ void __launch_bounds__(256) k_gather_predictions(const float *__restr
     }
 }
 
+// The same tail for the MULTI_CLASSES_NMS branch (detector3d_template.py:214-239): frame b = blockIdx.y owns the nc candidate lists
+// b * nc .. b * nc + nc - 1 of a batched NMS, and its rows are the kept candidates of class 0, then class 1, ..., each in keep order:
+// class k starts at the sum of min(keep_count, K) over the classes in front of it.  Every thread walks the frame's nc counts itself
+// (nc is 3 for KITTI: a handful of cached loads, no LDS and no barrier) until it meets the class its row falls into.  Rows past the
+// frame's total hold anchor 0 of class 0, what the padded rows of the class-agnostic records hold.
+__global__ void __launch_bounds__(256) k_gather_predictions_multiclass(const float *__restrict__ boxes, int box_stride,
+                                                                       long long table_stride, const float *__restrict__ scores,
+                                                                       long long score_stride, const int *__restrict__ keep,
+                                                                       const int *__restrict__ keep_count, int nc, int K,
+                                                                       float *__restrict__ out_boxes, float *__restrict__ out_scores,
+                                                                       long long *__restrict__ out_labels,
+                                                                       long long *__restrict__ out_selected, int *__restrict__ out_count) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int P = nc * K;
+    if (t >= P * 8) return;
+    const int b = blockIdx.y;
+    const int r = t >> 3, c = t & 7;
+    const int *kc = keep_count + (size_t)b * nc;
+    int k = 0, base = 0;
+    for (; k < nc; ++k) {
+        const int n = min(max(kc[k], 0), K);
+        if (r < base + n) break;
+        base += n;
+    }
+    if (t == 0) {                         // row 0 stops at the first class that keeps something: walk on for the total
+        int total = base;
+        for (int j = k; j < nc; ++j) total += min(max(kc[j], 0), K);
+        out_count[b] = total;
+    }
+    const bool live = k < nc;
+    const int cls = live ? k : 0;
+    const int src = live ? keep[((size_t)b * nc + k) * K + (r - base)] : 0;
+    const size_t o = (size_t)b * P + r;
+    if (c < 7) out_boxes[o * 7 + c] = boxes[(long long)b * table_stride + (size_t)src * box_stride + c];
+    else {
+        out_scores[o] = scores[((long long)b * nc + cls) * score_stride + src];
+        out_labels[o] = (long long)(cls + 1);
+        out_selected[o] = (long long)src;
+    }
+}
+
 }  // namespace
+
+extern "C" int hvpr_gather_predictions_multiclass_f32(const float *boxes, int box_stride, long long table_stride, const float *scores,
+                                                      long long score_stride, const int32_t *keep, const int32_t *keep_count,
+                                                      int n_frames, int n_class, int max_keep, float *out_boxes, float *out_scores,
+                                                      int64_t *out_labels, int64_t *out_selected, int32_t *out_count,
+                                                      hvpr_stream_t stream) {
+    if (n_frames < 0 || n_class < 0 || max_keep < 0 || box_stride < 7) return HVPR_ERR_INVALID_ARG;
+    if (n_frames == 0) return HVPR_OK;
+    if (!out_count) return HVPR_ERR_INVALID_ARG;
+    if (n_class == 0 || max_keep == 0) {
+        if (hipMemsetAsync(out_count, 0, (size_t)n_frames * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return HVPR_ERR_LAUNCH;
+        return HVPR_OK;
+    }
+    if (!boxes || !scores || !keep || !keep_count || !out_boxes || !out_scores || !out_labels || !out_selected) return HVPR_ERR_INVALID_ARG;
+    if (n_frames > 65535 || (long long)n_class * max_keep * 8 > 0x7fffffffll) return HVPR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_gather_predictions_multiclass, dim3(hvpr_cdiv(n_class * max_keep * 8, 256), n_frames), dim3(256), 0,
+                       (hipStream_t)stream, boxes, box_stride, table_stride, scores, score_stride, keep, keep_count, n_class, max_keep,
+                       out_boxes, out_scores, (long long *)out_labels, (long long *)out_selected, out_count);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
 
 extern "C" int hvpr_gather_predictions_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
                                                    const float *scores, const int32_t *labels, long long score_stride,

@@ -36,11 +36,11 @@ def class_agnostic_nms(box_scores, box_preds, nms_config, score_thresh=None):
     return selected, box_scores[selected]
 
 
-def _nms_of_score_rows(scores, boxes, nms_config, score_thresh, ws, segments_per_table):
+def _nms_of_score_rows(scores, boxes, nms_config, score_thresh, ws, segments_per_table, counts_on_device=False):
     """Score filter, top NMS_PRE_MAXSIZE and rotated NMS of every row of scores (S, A) — a candidate list each, row s ranking the
     box table boxes[s // segments_per_table] of boxes (T, A, >= 7) — in one score_topk and one batched NMS call per
     kernels.MAX_NMS_SEGMENTS lists.  Both f32 and contiguous.  Returns keep (S, NMS_POST_MAXSIZE) i32 and the S counts as a host list
-    (ONE read)."""
+    (ONE read), or with counts_on_device as the (S,) i32 device tensor (no read)."""
     pre = min(int(nms_config.NMS_PRE_MAXSIZE), scores.shape[1])
     order, _, counts = kernels.score_topk(scores, score_thresh, pre, ws, want_scores=False)
     keeps, kcs = [], []
@@ -50,7 +50,8 @@ def _nms_of_score_rows(scores, boxes, nms_config, score_thresh, ws, segments_per
         keeps.append(keep)
         kcs.append(kc)
     one = len(keeps) == 1
-    return (keeps[0] if one else torch.cat(keeps)), (kcs[0] if one else torch.cat(kcs)).tolist()
+    kc = kcs[0] if one else torch.cat(kcs)
+    return (keeps[0] if one else torch.cat(keeps)), (kc if counts_on_device else kc.tolist())
 
 
 def multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh=None):
@@ -182,11 +183,12 @@ class Detector3DTemplate(nn.Module):
         sync=True  -> the reference's return: pred_dicts[i] = {pred_boxes (n,7), pred_scores (n,), pred_labels (n,)}.
         sync=False -> no host read-back: every tensor is padded to NMS_POST_MAXSIZE rows and pred_count (device i32)
                       says how many are live (rows past it are copies of anchor 0 and must be ignored).
+        MULTI_CLASSES_NMS: the same two forms; the sync=False records are padded to num_class * NMS_POST_MAXSIZE rows.
         """
         cfg = self.model_cfg.POST_PROCESSING
         ncfg = cfg.NMS_CONFIG
         if ncfg.MULTI_CLASSES_NMS:
-            return self._post_processing_multi_class(batch_dict)
+            return self._post_processing_multi_class(batch_dict) if sync else self._post_processing_multi_class_device(batch_dict)
         B = batch_dict["batch_size"]
         boxes_all = batch_dict["batch_box_preds"]
         assert boxes_all.dim() == 3 and boxes_all.shape[0] == B
@@ -269,6 +271,28 @@ class Detector3DTemplate(nn.Module):
             recall_dict = self.generate_recall_record(rec["pred_boxes"], recall_dict, b, batch_dict, cfg.RECALL_THRESH_LIST)
             pred_dicts.append(rec)
         return pred_dicts, recall_dict, batch_dict
+
+    def _post_processing_multi_class_device(self, batch_dict):
+        """The MULTI_CLASSES_NMS branch with nothing read back: the same score_topk and batched NMS calls as the host form, the
+        counts left on the device, and ONE gather (hvpr_gather_predictions_multiclass_f32) that lays each frame's classes end to
+        end.  Records as the class-agnostic sync=False ones: padded to num_class * NMS_POST_MAXSIZE rows, the first pred_count of
+        them equal to the sync=True record; recall is the caller's (eval_loop.DeviceEvalEpilogue), so recall_dict is empty."""
+        cfg = self.model_cfg.POST_PROCESSING
+        ncfg = cfg.NMS_CONFIG
+        B = batch_dict["batch_size"]
+        cls = batch_dict["batch_cls_preds"]
+        cls = (cls if batch_dict["cls_preds_normalized"] else torch.sigmoid(cls)).float()
+        A, nc = cls.shape[1], cls.shape[2]
+        if A == 0 or nc == 0:
+            raise ValueError("post_processing(sync=False) with MULTI_CLASSES_NMS needs at least one anchor and one class")
+        boxes = batch_dict["batch_box_preds"].float().contiguous()
+        rows = cls.permute(0, 2, 1).reshape(B * nc, A).contiguous()              # class-major: row b * nc + k
+        ws = self._post_workspace(B * nc, A, min(int(ncfg.NMS_PRE_MAXSIZE), A), cls.device, kernels.nms_call_segments(B, nc))
+        keep, kc = _nms_of_score_rows(rows, boxes, ncfg, cfg.SCORE_THRESH, ws, nc, counts_on_device=True)
+        pb, ps, pl, sel, cnt = kernels.gather_predictions_multiclass(boxes, rows, keep, kc, nc)
+        pred_dicts = [{"pred_boxes": pb[b], "pred_labels": pl[b], "pred_scores": ps[b], "selected": sel[b], "pred_count": cnt[b:b + 1]}
+                      for b in range(B)]
+        return pred_dicts, {}, batch_dict
 
     @staticmethod
     def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
@@ -770,21 +794,30 @@ def load_data_to_gpu(batch_dict):
         batch_dict[k] = torch.from_numpy(v).float().cuda()
 
 
+class _PointFeatureEncoder:
+    def __init__(self, n):
+        self.num_point_features = n
+
+
+def set_model_attributes(dataset, dataset_cfg):
+    """The attributes of DatasetTemplate the model constructors read (dataset.py:17-40), from a DATA_CONFIG block: range,
+    voxel / grid size, point feature count.  Shared by SyntheticDataset and kitti_dataset.KittiDataset."""
+    from .voxel_generator import grid_size_of
+    dataset.point_cloud_range = np.array(dataset_cfg["POINT_CLOUD_RANGE"], dtype=np.float32)
+    dataset.point_feature_encoder = _PointFeatureEncoder(len(dataset_cfg["POINT_FEATURE_ENCODING"]["used_feature_list"]))
+    vc = [p for p in dataset_cfg["DATA_PROCESSOR"] if p["NAME"] == "transform_points_to_voxels"][0]
+    dataset.voxel_size = vc["VOXEL_SIZE"]
+    dataset.grid_size = grid_size_of(dataset.point_cloud_range, dataset.voxel_size)
+
+
 class SyntheticDataset:
     """The slice of DatasetTemplate the model constructors read (dataset.py:17-40): class names, range, voxel/grid size,
     point feature count.  Used by tests and bench.py, which have no KITTI files."""
 
-    class _Encoder:
-        def __init__(self, n):
-            self.num_point_features = n
+    _Encoder = _PointFeatureEncoder
 
     def __init__(self, cfg, training=False):
-        from .voxel_generator import grid_size_of
         self.dataset_cfg = cfg.DATA_CONFIG
         self.class_names = list(cfg.CLASS_NAMES)
         self.training = training
-        self.point_cloud_range = np.array(self.dataset_cfg.POINT_CLOUD_RANGE, dtype=np.float32)
-        self.point_feature_encoder = self._Encoder(len(self.dataset_cfg.POINT_FEATURE_ENCODING.used_feature_list))
-        vc = [p for p in self.dataset_cfg.DATA_PROCESSOR if p.NAME == "transform_points_to_voxels"][0]
-        self.voxel_size = vc.VOXEL_SIZE
-        self.grid_size = grid_size_of(self.point_cloud_range, self.voxel_size)
+        set_model_attributes(self, self.dataset_cfg)

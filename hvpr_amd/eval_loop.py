@@ -63,7 +63,8 @@ class DeviceEvalEpilogue:
     """Owns the split-wide detection tables (the layout of kitti_eval_device.AnnoTables) and the running recall counters.
 
     class_names: the detector's, label l names class_names[l - 1]; recall_thresh_list: POST_PROCESSING.RECALL_THRESH_LIST (at most
-    8); max_frames: frames of the split; post_max: NMS_POST_MAXSIZE, the rows a frame can have (<= 4096, the evaluator's limit).
+    8); max_frames: frames of the split; post_max: the rows a frame can have (<= 4096, the evaluator's limit): NMS_POST_MAXSIZE,
+    times the number of classes on the MULTI_CLASSES_NMS branch (`post_max_of`).
     The tables hold max_frames * post_max rows unless `capacity` says otherwise; a split that outgrows them raises at the next
     read (nothing is written past them)."""
 
@@ -96,8 +97,8 @@ class DeviceEvalEpilogue:
         if B == 0:
             return
         if any("pred_count" not in r for r in pred_dicts):
-            raise ValueError("add_batch takes the sync=False records of the class-agnostic branch; the MULTI_CLASSES_NMS branch "
-                             "synchronises by construction (one read of all its counts) and is outside the device epilogue")
+            raise ValueError("add_batch takes the sync=False records of post_processing (class-agnostic or MULTI_CLASSES_NMS branch): "
+                             "padded tensors with a device pred_count; sync=True records belong to the host path")
         if self.n_frames + B > self.max_frames:
             raise ValueError(f"more than max_frames = {self.max_frames} frames")
         P = int(pred_dicts[0]["pred_boxes"].shape[0])
@@ -207,6 +208,15 @@ def write_kitti_txt(annos, output_dir):
                          loc[i][0], loc[i][1], loc[i][2], a["rotation_y"][i], a["score"][i]), file=f)
 
 
+def post_max_of(cfg, class_names=None):
+    """Rows per frame of the sync=False records of cfg's post-processing: NMS_POST_MAXSIZE, per class with MULTI_CLASSES_NMS."""
+    ncfg = cfg.MODEL.POST_PROCESSING.NMS_CONFIG
+    post = int(ncfg.NMS_POST_MAXSIZE)
+    if ncfg.get("MULTI_CLASSES_NMS", False):
+        post *= len(class_names if class_names is not None else cfg.CLASS_NAMES)
+    return post
+
+
 def eval_one_epoch_device(cfg, model, batches, gt_annos, epoch_id=None, logger=None, save_to_file=False, result_dir=None,
                           log_every=0, class_names=None, epilogue=None):
     """The reference's eval_one_epoch (tools/eval_utils/eval_utils.py:22-127) over DeviceEvalEpilogue: the model is called with
@@ -218,8 +228,8 @@ def eval_one_epoch_device(cfg, model, batches, gt_annos, epoch_id=None, logger=N
     pp = cfg.MODEL.POST_PROCESSING
     thresholds = list(pp.RECALL_THRESH_LIST)
     class_names = list(class_names if class_names is not None else cfg.CLASS_NAMES)
-    ep = epilogue if epilogue is not None else DeviceEvalEpilogue(class_names, thresholds, len(gt_annos),
-                                                                  int(pp.NMS_CONFIG.NMS_POST_MAXSIZE))
+    # sized on the host before anything is launched: more than the evaluator's rows per frame raises here
+    ep = epilogue if epilogue is not None else DeviceEvalEpilogue(class_names, thresholds, len(gt_annos), post_max_of(cfg, class_names))
     info = logger.info if logger is not None else (lambda s: None)
     info("*************** EPOCH %s EVALUATION *****************" % epoch_id)
     model.eval()

@@ -862,6 +862,30 @@ def gather_predictions_batched(boxes, scores, labels, keep, segments_per_table=1
     return ob, os_, ol, osel
 
 
+def gather_predictions_multiclass(boxes, scores, keep, keep_count, num_class):
+    """The MULTI_CLASSES_NMS records of a batch in one launch, nothing read back: boxes (B, A, >=7), scores (B * nc, A) class-major,
+    keep (B * nc, K) i32 and keep_count (B * nc,) i32 as the batched NMS leaves them -> pred_boxes (B, nc * K, 7), pred_scores,
+    pred_labels i64 (class + 1), selected i64 (B, nc * K) and pred_count (B,) i32.  A frame's rows are its classes' kept candidates
+    in class order; the rows past pred_count hold anchor 0 of class 0."""
+    nc = int(num_class)
+    S, K = keep.shape
+    if boxes.dim() != 3 or nc < 1 or boxes.shape[0] * nc != S or tuple(scores.shape) != (S, boxes.shape[1]) \
+            or tuple(keep_count.shape) != (S,):
+        raise ValueError("gather_predictions_multiclass: shapes do not match")
+    B, dev = boxes.shape[0], boxes.device
+    ob = torch.empty((B, nc * K, 7), dtype=torch.float32, device=dev)
+    os_ = torch.empty((B, nc * K), dtype=torch.float32, device=dev)
+    ol = torch.empty((B, nc * K), dtype=torch.int64, device=dev)
+    osel = torch.empty((B, nc * K), dtype=torch.int64, device=dev)
+    oc = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().hvpr_gather_predictions_multiclass_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
+                                                       _ptr(scores, torch.float32, "scores"), scores.shape[1],
+                                                       _ptr(keep, torch.int32, "keep"), _ptr(keep_count, torch.int32, "keep_count"),
+                                                       B, nc, K, ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), osel.data_ptr(),
+                                                       oc.data_ptr(), _stream()), "hvpr_gather_predictions_multiclass_f32")
+    return ob, os_, ol, osel, oc
+
+
 def boxes_pairwise(a, b, mode):
     """mode 0: BEV overlap area, 1: BEV IoU, 2: 3D IoU.  a (N,7), b (M,7) -> (N,M)."""
     a = a[:, :7].contiguous()

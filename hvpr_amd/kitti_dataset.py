@@ -256,6 +256,9 @@ class KittiDataset:
         self.set_split(_get(dataset_cfg, "DATA_SPLIT", DEFAULT_SPLIT)[self.mode])
         self.kitti_infos = []
         self.include_kitti_data(self.mode)
+        if all(k in dataset_cfg for k in ("POINT_CLOUD_RANGE", "POINT_FEATURE_ENCODING", "DATA_PROCESSOR")):
+            from .detector import set_model_attributes       # what build_network(cfg.MODEL, n, dataset=self) reads
+            set_model_attributes(self, dataset_cfg)
 
     def include_kitti_data(self, mode):
         for info_path in _get(self.dataset_cfg, "INFO_PATH", DEFAULT_INFO_PATH)[mode]:
@@ -333,7 +336,10 @@ class KittiDataset:
         info = self.kitti_infos[index]
         sample_idx = info["point_cloud"]["lidar_idx"]
         calib = self.get_calib(sample_idx)
-        out = {"points": torch.from_numpy(self.get_lidar(sample_idx)).to(self.device), "frame_id": sample_idx, "calib": calib,
+        points = torch.from_numpy(self.get_lidar(sample_idx))
+        if self.device.type == "cuda":                       # through pinned memory: the upload does not synchronise the host
+            points = points.pin_memory()
+        out = {"points": points.to(self.device, non_blocking=True), "frame_id": sample_idx, "calib": calib,
                "image_shape": info["image"]["image_shape"]}
         if "annos" in info:
             annos = info["annos"]

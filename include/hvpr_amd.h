@@ -321,6 +321,14 @@ int hvpr_boxes_pairwise_f32(const float *boxes_a, int n, const float *boxes_b, i
  *     (S, n) serves every call with at most S segments and n_max <= n.
  *     hvpr_gather_predictions_batched_f32: out_*[s, r] = *[keep[s, r]] for r < max_keep; boxes are addressed like the NMS's
  *     (table_stride, segments_per_table); scores and labels are one row per segment, score_stride elements apart.
+ *     hvpr_gather_predictions_multiclass_f32: the records of the MULTI_CLASSES_NMS branch without a host read.  keep
+ *     [n_frames * n_class, max_keep] and keep_count [n_frames * n_class] are the batched NMS's over the class-major score rows
+ *     [n_frames * n_class, score_stride] (row b * n_class + k: class k of frame b, ranking box table b).  Frame b's rows are the
+ *     kept candidates of class 0, then class 1, ..., each in keep order; class k starts at the sum of min(keep_count, max_keep)
+ *     over the classes in front of it (computed in the kernel); label = k + 1, score = class k's of the anchor.  out_boxes
+ *     [n_frames, n_class * max_keep, 7], out_scores / out_labels / out_selected [n_frames, n_class * max_keep], out_count
+ *     [n_frames] = the frame's total; every row past it holds anchor 0 of class 0 (label 1, selected 0).  One launch;
+ *     n_frames == 0: nothing is done; n_class == 0 or max_keep == 0: the counts are zeroed.  n_frames <= 65535.
  * ------------------------------------------------------------------------------------------- */
 size_t hvpr_nms_bev_batched_workspace_bytes(int n_segments, int n_max);
 int hvpr_nms_bev_batched_f32(const float *boxes, int box_stride, long long table_stride, int segments_per_table,
@@ -331,6 +339,10 @@ int hvpr_gather_predictions_batched_f32(const float *boxes, int box_stride, long
                                         const float *scores, const int32_t *labels, long long score_stride,
                                         const int32_t *keep, int n_segments, int max_keep, float *out_boxes,
                                         float *out_scores, int64_t *out_labels, int64_t *out_selected, hvpr_stream_t stream);
+int hvpr_gather_predictions_multiclass_f32(const float *boxes, int box_stride, long long table_stride, const float *scores,
+                                           long long score_stride, const int32_t *keep, const int32_t *keep_count, int n_frames,
+                                           int n_class, int max_keep, float *out_boxes, float *out_scores, int64_t *out_labels,
+                                           int64_t *out_selected, int32_t *out_count, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3  KITTI AP on the device (hvpr_amd/kitti_eval_device.py; the host evaluator hvpr_amd/kitti_eval.py is the yardstick).
