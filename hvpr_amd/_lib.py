@@ -141,6 +141,9 @@ SIGNATURES = {
     "hvpr_kitti_infos_block_points": (_I, []),
     "hvpr_kitti_infos_workspace_bytes": (_Z, [_I, _I, _I]),
     "hvpr_kitti_infos_count_f32": (_I, [_P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "hvpr_render_bev_workspace_bytes": (_Z, [_I, _I, _I]),
+    "hvpr_render_bev_u8": (_I, [_P, _c.c_longlong, _I, _I, _P, _I, _P, _F, _P, _I, _I, _P, _P, _F, _P, _I, _P, _I, _I, _P, _P, _F, _P, _I,
+                                _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -19,7 +19,7 @@ PER_FILE = {"iou3d_nms.hip": ["-ffp-contract=off"], "voxelize.hip": ["-ffp-contr
             "preprocess.hip": ["-ffp-contract=off"], "assign_loss.hip": ["-ffp-contract=off"], "kitti_ap.hip": ["-ffp-contract=off"],
             "augment.hip": ["-ffp-contract=off"], "eval_tail.hip": ["-ffp-contract=off"],
             "gt_database.hip": ["-ffp-contract=off"], "collate.hip": ["-ffp-contract=off"],
-            "kitti_infos.hip": ["-ffp-contract=off"]}
+            "kitti_infos.hip": ["-ffp-contract=off"], "bev_render.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

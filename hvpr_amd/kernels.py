@@ -1246,3 +1246,67 @@ def ragged_sample_write(points, off, mask, new_off, near_off, mode, dest, num_po
                                              _ptr(flag, torch.int32, "flag"), workspace.data_ptr(), workspace.numel(), _stream()),
           "hvpr_ragged_sample_write_f32")
     return out, flag
+
+
+# ------------------------------------------------------------------------------------------------ v1: the BEV picture
+def bev_grid(point_cloud_range, pixel):
+    """(H, W) of the picture: round((hi - lo) / pixel) in float32, y cells by x cells (tools/vis.py:90-91)."""
+    import numpy as np
+    r = np.ascontiguousarray(point_cloud_range, np.float32).reshape(6)
+    g = np.round((r[3:5] - r[:2]) / np.float32(pixel)).astype(np.int64)
+    return int(g[1]), int(g[0])
+
+
+def render_bev(points, frame_offsets, point_cloud_range, pixel, palette, tables=(), xyz_col=0, thickness=2, heading_sign=-1,
+               image=None, counts=None, want_counts=False, workspace=None):
+    """(image (B, H, W, 3) uint8, counts (B, H, W) int32 or None, workspace): the height picture of the ragged `points`
+    (n, stride) float32 with `frame_offsets` (B + 1,) int32 on the device, and on it the outlines of up to two box tables.  A
+    table is a dict: `boxes` (B, P, >= 7) float32, optionally `count` (B,) int32, `scores` (B, P) float32 with `thresh`, `labels`
+    (B, P) int64, and `ink` (a row's ink is ink + label; ink alone without labels).  `palette` (n_ink, 3) uint8 on the device,
+    ink 0 unused.  heading_sign -1 draws a lidar heading as it is, +1 mirrored as the reference does.  Only enqueues."""
+    import numpy as np
+    tables = list(tables)
+    if len(tables) > 2:
+        raise ValueError("render_bev: two box tables at the most")
+    if points.dim() != 2 or frame_offsets.dim() != 1 or frame_offsets.numel() < 2:
+        raise ValueError("render_bev: points must be (n, stride) and frame_offsets (B + 1,)")
+    n, stride = points.shape
+    B = frame_offsets.numel() - 1
+    rng = np.ascontiguousarray(point_cloud_range, np.float32).reshape(6)
+    H, W = bev_grid(rng, pixel)
+    need = lib().hvpr_render_bev_workspace_bytes(B, H, W)
+    if need == 0:
+        raise ValueError(f"render_bev: a picture of {B} x {H} x {W} pixels is not supported")
+    dev = points.device
+    if palette.dim() != 2 or palette.shape[1] != 3:
+        raise ValueError("render_bev: palette must be (n_ink, 3)")
+    if image is None:
+        image = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    elif tuple(image.shape) != (B, H, W, 3):
+        raise ValueError(f"render_bev: image must be {(B, H, W, 3)}")
+    if counts is None and want_counts:
+        counts = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    elif counts is not None and tuple(counts.shape) != (B, H, W):
+        raise ValueError(f"render_bev: counts must be {(B, H, W)}")
+    args = []
+    for t in tables + [None] * (2 - len(tables)):
+        if t is None:
+            args += [None, 0, 7, None, None, 0.0, None, 0]
+            continue
+        boxes = t["boxes"]
+        if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] < 7:
+            raise ValueError("render_bev: boxes must be (B, P, >= 7)")
+        P = boxes.shape[1]
+        for key, shape in (("count", (B,)), ("scores", (B, P)), ("labels", (B, P))):
+            if t.get(key) is not None and tuple(t[key].shape) != shape:
+                raise ValueError(f"render_bev: {key} must be {shape}")
+        args += [_ptr(boxes, torch.float32, "boxes") if P else None, P, boxes.shape[2], _ptr(t.get("count"), torch.int32, "count"),
+                 _ptr(t.get("scores"), torch.float32, "scores"), float(t.get("thresh", 0.0)),
+                 _ptr(t.get("labels"), torch.int64, "labels"), int(t.get("ink", 1))]
+    workspace = _workspace(workspace, need, dev)
+    check(lib().hvpr_render_bev_u8(_ptr(points, torch.float32, "points") if n else None, n, stride, int(xyz_col),
+                                   _ptr(frame_offsets, torch.int32, "frame_offsets"), B, rng.ctypes.data, float(pixel), *args,
+                                   _ptr(palette, torch.uint8, "palette"), palette.shape[0], int(thickness), int(heading_sign),
+                                   _ptr(image, torch.uint8, "image"), _ptr(counts, torch.int32, "counts"), workspace.data_ptr(),
+                                   workspace.numel(), _stream()), "hvpr_render_bev_u8")
+    return image, counts, workspace

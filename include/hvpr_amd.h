@@ -924,6 +924,55 @@ int hvpr_kitti_infos_count_f32(const float *points, long long n_points, int poin
                                int32_t *obj_count, int32_t *fov_count, void *workspace, size_t workspace_bytes,
                                hvpr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * v1  The bird's-eye-view picture of a batch: tools/vis.py kitti_vis (:279-286) -- point_to_vis_bev (:109-121) over points_to_bev /
+ *     _points_to_bevmap_reverse_kernel (:9-106) with ONE height slice, then draw_box_in_bev (:223-249) -- for every frame of a
+ *     batch in one call, from the forms the batch loader and post_processing(sync=False) leave on the device.
+ *     points        [n_points, point_stride] f32, xyz at columns xyz_col..xyz_col+2 (the loader's batch column costs no copy);
+ *                   frame_offsets [batch + 1] i32 on the device: frame b owns rows offsets[b] .. offsets[b + 1] - 1; a row no
+ *                   frame owns and a point with a non-finite coordinate are dropped.
+ *     range, pixel  range[6] f32 on the HOST (x, y, z low, then high), read during the call; the grid is W = round((hi_x - lo_x) /
+ *                   pixel), H = round((hi_y - lo_y) / pixel) in float32 with ties to even, as points_to_bev forms it; the one
+ *                   height slice is range[5] - range[2] (float32) high.
+ *     height pass   a point belongs to cell floor((p - lo) / size) per axis in float32 (a true division) and is dropped when that
+ *                   is < 0 or >= the grid, z included; a cell's value is the maximum over its points of (z - z_lo) / (z_hi - z_lo)
+ *                   formed in double and rounded to float32, from 0; `counts` [batch, H, W] i32 (or NULL) is bev_map[-1], the
+ *                   points per cell.  Integer atomics only (max on the bits of a float >= 0, add): bit-reproducible.
+ *                   UNPINNED: the reference's loop ends at the max_voxels-th (80 000) newly opened cell in point order; this op has
+ *                   no such cap.
+ *     box tables    two, each optional (boxes NULL): boxes [batch, rows, box_stride] f32 with x, y, z, dx, dy, dz, heading in the
+ *                   first 7 floats of a row (box_stride >= 7); count [batch] i32 or NULL: only the first count[b] rows of frame b;
+ *                   scores [batch, rows] f32 or NULL: a row is drawn when score >= thresh; labels [batch, rows] i64 or NULL.  A
+ *                   row's ink is `ink` + its label (`ink` alone without labels); a row whose ink is < 1 or >= n_ink, or with a
+ *                   non-finite field, is not drawn.  palette [n_ink, 3] u8 on the device; ink 0 is "nothing drawn".
+ *     box pass      center_to_corner_box2d's corners in float32 (rotation_2d turns CLOCKWISE for a positive angle), plus the
+ *                   centre, minus range[:2], times (W, H) / (hi - lo)[:2] (both steps in float64, each rounded to float32, as
+ *                   numpy's in-place updates do), truncated toward zero and clamped to +-8191.  Per box the reference's THREE
+ *                   segments, corners 0-1, 2-3, 3-0 (bev_lines, :244-246; the edge 1-2 is left open there too).  heading_sign +1
+ *                   draws a lidar box (counter-clockwise heading) mirrored, as the reference does; -1 negates the angle first and
+ *                   is the correct drawing.
+ *                   UNPINNED: cv2.line's rasterisation.  The rule here: pixel p takes a segment's ink when 4 d^2 <= thickness^2, d
+ *                   the distance from p to the integer segment, evaluated exactly in int64 (at thickness 1 this contains every
+ *                   Bresenham pixel).  Where inks meet the larger index wins (integer atomic max), on every run.
+ *     image         [batch, H, W, 3] u8: the ink's palette row where ink was drawn, else uint8(v * 255) (float32 product) in all
+ *                   three channels.
+ *     Refusals, before any launch: HVPR_ERR_INVALID_ARG for a null frame_offsets / range / image / palette / workspace (or points
+ *     with n_points > 0), batch < 1, n_ink < 1, thickness < 1, heading_sign other than +-1, xyz_col outside the row, a
+ *     non-finite or empty range, pixel <= 0, a table with rows < 0 or box_stride < 7; HVPR_ERR_UNSUPPORTED for W or H > 8192,
+ *     thickness > 255, batch > 65535, batch * H * W or n_points >= 2^31, a table of more than 2^20 rows; HVPR_ERR_WORKSPACE.
+ *     Four launches at most, no host read, no allocation: capturable into a hipGraph.
+ *     hvpr_render_bev_workspace_bytes  for [batch, height, width] pixels (three 32-bit planes); 0 for a shape that is refused.
+ *                   Needs no GPU.
+ * ------------------------------------------------------------------------------------------- */
+size_t hvpr_render_bev_workspace_bytes(int batch, int height, int width);
+int hvpr_render_bev_u8(const float *points, long long n_points, int point_stride, int xyz_col, const int32_t *frame_offsets,
+                       int batch, const float *range, float pixel, const float *boxes0, int rows0, int box_stride0,
+                       const int32_t *count0, const float *scores0, float thresh0, const long long *labels0, int ink0,
+                       const float *boxes1, int rows1, int box_stride1, const int32_t *count1, const float *scores1,
+                       float thresh1, const long long *labels1, int ink1, const uint8_t *palette, int n_ink, int thickness,
+                       int heading_sign, uint8_t *image, int32_t *counts, void *workspace, size_t workspace_bytes,
+                       hvpr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
