@@ -82,6 +82,8 @@ SIGNATURES = {
     "hvpr_segment_sum_rows_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P, _P, _c.c_longlong, _P, _c.c_longlong, _P]),
     "hvpr_attend_rows_fwd_f32": (_I, [_P, _I, _P, _c.c_longlong, _P, _I, _I, _P, _P, _P]),
     "hvpr_fused_adam_truewd_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "hvpr_fused_adam_l2_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "hvpr_fused_sgd_f32": (_I, [_P, _P, _P, _c.c_longlong, _F, _F, _F, _P, _P]),
     "hvpr_assign_targets_workspace_bytes": (_Z, [_I, _I]),
     "hvpr_assign_targets_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _F, _I, _I, _I, _c.c_longlong, _P, _P, _P, _P, _P, _Z, _P]),
     "hvpr_rpn_losses_workspace_bytes": (_Z, [_I, _c.c_longlong]),

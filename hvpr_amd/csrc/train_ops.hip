@@ -11,6 +11,9 @@
 //                                      p *= 1 - wd * lr followed by the Adam step — OptimWrapper.step,
 //                                      tools/train_utils/optimization/fastai_optim.py:132-149, with the gradient-norm clip of
 //                                      tools/train_utils/train_utils.py:41 folded in as a device-side scale.
+//   hvpr_fused_adam_l2_f32             the same launch for build_optimizer's 'adam' (tools/train_utils/optimization/__init__.py:
+//                                      12-13): torch.optim.Adam with COUPLED decay, g' = g * scale + wd * p.
+//   hvpr_fused_sgd_f32                 its 'sgd' (:14-18): torch.optim.SGD, dampening 0, no Nesterov, over the same flat buffers.
 // The tensor layouts are the reference's (channel-major point features), so the wrappers drop into its modules.
 #include "common.h"
 
@@ -52,6 +55,8 @@ __global__ void __launch_bounds__(256) k_three_interpolate(const float *__restri
 
 // One thread = 4 consecutive parameters.  Same arithmetic as torch.optim.Adam (bias-corrected step size, eps added after the
 // bias-corrected square root) preceded by the decoupled decay.  grad_scale (device word, may be null): the clip coefficient.
+// kL2: torch.optim.Adam's coupled decay instead — `decay` then carries weight_decay itself, which joins the gradient.
+template <bool kL2>
 __global__ void __launch_bounds__(256) k_fused_adam(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                     float *__restrict__ v, long long n, float decay, float beta1, float beta2,
                                                     float eps, float step_size, float inv_sqrt_bc2,
@@ -61,7 +66,8 @@ __global__ void __launch_bounds__(256) k_fused_adam(float *__restrict__ p, const
     const float gs = grad_scale ? *grad_scale : 1.f;
     auto upd = [&](float &pp, float gg, float &mm, float &vv) {
         gg *= gs;
-        pp *= decay;
+        if (kL2) gg += decay * pp;
+        else pp *= decay;
         mm = mm + (gg - mm) * (1.f - beta1);                 // lerp form, as torch's foreach path
         vv = vv * beta2 + (1.f - beta2) * gg * gg;
         const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
@@ -74,6 +80,38 @@ __global__ void __launch_bounds__(256) k_fused_adam(float *__restrict__ p, const
         *(float4 *)(p + i4) = P; *(float4 *)(m + i4) = M; *(float4 *)(v + i4) = V;
     } else {
         for (long long i = i4; i < n; ++i) upd(p[i], g[i], m[i], v[i]);
+    }
+}
+
+// One thread = 4 consecutive parameters of torch.optim.SGD (dampening 0, no Nesterov).  buf == nullptr: momentum 0.  A zeroed
+// buffer gives torch's first step (buf = d) with no step counter: 0 * momentum + d == d.
+__global__ void __launch_bounds__(256) k_fused_sgd(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ buf,
+                                                   long long n, float lr, float momentum, float weight_decay,
+                                                   const float *__restrict__ grad_scale) {
+    const long long i4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= n) return;
+    const float gs = grad_scale ? *grad_scale : 1.f;
+    auto upd = [&](float &pp, float gg, float *bb) {
+        float d = gg * gs + weight_decay * pp;
+        if (bb) {
+            d = momentum * *bb + d;
+            *bb = d;
+        }
+        pp -= lr * d;
+    };
+    if (i4 + 4 <= n) {
+        float4 P = *(float4 *)(p + i4);
+        const float4 G = *(const float4 *)(g + i4);
+        if (buf) {
+            float4 B = *(float4 *)(buf + i4);
+            upd(P.x, G.x, &B.x); upd(P.y, G.y, &B.y); upd(P.z, G.z, &B.z); upd(P.w, G.w, &B.w);
+            *(float4 *)(buf + i4) = B;
+        } else {
+            upd(P.x, G.x, nullptr); upd(P.y, G.y, nullptr); upd(P.z, G.z, nullptr); upd(P.w, G.w, nullptr);
+        }
+        *(float4 *)(p + i4) = P;
+    } else {
+        for (long long i = i4; i < n; ++i) upd(p[i], g[i], buf ? buf + i : nullptr);
     }
 }
 
@@ -157,8 +195,36 @@ extern "C" int hvpr_fused_adam_truewd_f32(float *params, const float *grads, flo
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     const float decay = 1.f - weight_decay * lr;
-    hipLaunchKernelGGL(k_fused_adam, dim3(hvpr_cdiv((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
+    hipLaunchKernelGGL(k_fused_adam<false>, dim3(hvpr_cdiv((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
                        n, decay, beta1, beta2, eps, step_size, inv_sqrt_bc2, grad_scale_device);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_fused_adam_l2_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, long long n, float lr,
+                                      float beta1, float beta2, float eps, float weight_decay, int step,
+                                      const float *grad_scale_device, hvpr_stream_t stream) {
+    if (n < 0 || step < 1 || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return HVPR_ERR_INVALID_ARG;
+    if (n == 0) return HVPR_OK;
+    if (!params || !grads || !exp_avg || !exp_avg_sq) return HVPR_ERR_INVALID_ARG;
+    if (((size_t)params | (size_t)grads | (size_t)exp_avg | (size_t)exp_avg_sq) % 16 != 0) return HVPR_ERR_INVALID_ARG;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    hipLaunchKernelGGL(k_fused_adam<true>, dim3(hvpr_cdiv((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, n, weight_decay, beta1, beta2, eps, step_size, inv_sqrt_bc2, grad_scale_device);
+    HVPR_CHECK_LAUNCH();
+    return HVPR_OK;
+}
+
+extern "C" int hvpr_fused_sgd_f32(float *params, const float *grads, float *momentum_buf, long long n, float lr, float momentum,
+                                  float weight_decay, const float *grad_scale_device, hvpr_stream_t stream) {
+    if (n < 0 || !(momentum >= 0.f && momentum < 1.f)) return HVPR_ERR_INVALID_ARG;
+    if (n == 0) return HVPR_OK;
+    if (momentum == 0.f) momentum_buf = nullptr;          // no buffer is read or written at momentum 0
+    if (!params || !grads || (momentum != 0.f && !momentum_buf)) return HVPR_ERR_INVALID_ARG;
+    if (((size_t)params | (size_t)grads | (size_t)momentum_buf) % 16 != 0) return HVPR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_fused_sgd, dim3(hvpr_cdiv((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale_device);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }

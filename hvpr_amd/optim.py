@@ -4,7 +4,11 @@ Restates build_optimizer 'adam_onecycle' (tools/train_utils/optimization/__init_
 (fastai_optim.py:132-149: p *= 1 - wd*lr for every group, BatchNorm included, the optimiser's own weight_decay forced to 0),
 OneCycle (learning_schedules_fastai.py:60-77) with cosine annealing (:53-57), and the clipped step of train_one_epoch
 (tools/train_utils/train_utils.py:35-42).  Parameter updates use torch's foreach/fused kernels instead of the reference's
-per-tensor python loops."""
+per-tensor python loops.
+
+The other two branches of build_optimizer / build_scheduler (__init__.py:12-18, 40-61) are here as well: 'adam' and 'sgd' as
+torch.optim.Adam / SGD or, on the GPU, their flat forms FusedAdam / FusedSGD, with step decay (StepDecayLR, the reference's
+LambdaLR) and the cosine warm-up (CosineWarmupLR)."""
 import math
 
 import torch
@@ -110,20 +114,17 @@ class AdamOneCycle:
             self.lr, self.mom = extra["lr"], extra["mom"]
 
 
-class FusedAdamOneCycle:
-    """The same optimiser as AdamOneCycle on ONE flat fp32 buffer: every trainable parameter becomes a view into `flat_p`, its
-    gradient a view into `flat_g`, and a step is one launch of hvpr_fused_adam_truewd_f32 (decay + Adam + the gradient-norm
-    clip as a device-side scale) instead of hundreds of small kernels per tensor (the reference: per-tensor python loops,
-    fastai_optim.py:132-149).  state_dict() / load_state_dict() speak torch.optim.Adam's format in AdamOneCycle's parameter
-    order, so checkpoints move between the two."""
+class _FlatOptimizer:
+    """What the flat optimisers share: every parameter of `params` becomes a view into ONE fp32 buffer `flat_p`, its gradient a
+    view into `flat_g`; zero_grad / _collect_grads keep the gradient addresses fixed, clip_grad_norm leaves the coefficient on the
+    device, and step() is one launch (`_launch`, the subclass's kernel) over the whole buffer."""
 
-    def __init__(self, model, wd, lr=3e-3, beta2=0.99, eps=1e-8):
+    def _flatten(self, params):
         from . import kernels
-        rest, bn = split_bn_params(model)
-        self.params = rest + bn
-        self.n_rest = len(rest)
-        assert self.params and all(p.dtype == torch.float32 for p in self.params), "FusedAdamOneCycle: fp32 parameters"
-        assert len({p.device for p in self.params}) == 1, "FusedAdamOneCycle: one device"
+        name = type(self).__name__
+        self.params = list(params)
+        assert self.params and all(p.dtype == torch.float32 for p in self.params), name + ": fp32 parameters"
+        assert len({p.device for p in self.params}) == 1, name + ": one device"
         dev = self.params[0].device
         self.offsets, off = [], 0
         for p in self.params:
@@ -132,7 +133,6 @@ class FusedAdamOneCycle:
         self.numel = off
         self.flat_p = torch.zeros(off, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat_p), torch.zeros_like(self.flat_p)
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 view = self.flat_p[o:o + p.numel()].view_as(p)
@@ -142,7 +142,6 @@ class FusedAdamOneCycle:
         self._point_grads()
         from . import conv_train
         conv_train.weights_changed()        # every parameter has just moved into the flat buffer
-        self.wd, self._lr, self._mom, self.beta2, self.eps = wd, lr, 0.9, beta2, eps
         self.steps = 0
         self._scale = None
         self._kernels = kernels
@@ -151,13 +150,9 @@ class FusedAdamOneCycle:
         for p, g in zip(self.params, self._grad_views):
             p.grad = g
 
-    lr = property(lambda self: self._lr, lambda self, v: setattr(self, "_lr", float(v)))
-    mom = property(lambda self: self._mom, lambda self, v: setattr(self, "_mom", float(v)))
-
-    @property
-    def param_groups(self):
-        return [{"params": self.params[:self.n_rest], "lr": self._lr, "betas": (self._mom, self.beta2)},
-                {"params": self.params[self.n_rest:], "lr": self._lr, "betas": (self._mom, self.beta2)}]
+    def _views(self, flat):
+        """The per-parameter views of a flat state buffer, in `params` order."""
+        return [flat[o:o + p.numel()].view_as(p) for p, o in zip(self.params, self.offsets)]
 
     def zero_grad(self):
         """Gradients are zeroed, never set to None: autograd then accumulates in place into the flat views, and p.grad keeps its
@@ -205,19 +200,45 @@ class FusedAdamOneCycle:
         self._launch()
         self._scale = None
 
-    def _launch(self):
-        """ONE launch of hvpr_fused_adam_truewd_f32 over the flat buffers."""
+    def _call(self, name, *args):
+        """ONE launch of the step kernel `name` over the flat buffers: (params, grads, *args, grad scale, stream)."""
         from ._lib import check, lib
         if not self.flat_p.is_cuda:
-            raise RuntimeError("hvpr_amd: FusedAdamOneCycle steps on the GPU (the HIP path has no CPU fallback)")
-        check(lib().hvpr_fused_adam_truewd_f32(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(),
-                                               self.exp_avg_sq.data_ptr(), self.numel, self._lr, self._mom, self.beta2, self.eps,
-                                               self.wd, self.steps, None if self._scale is None else self._scale.data_ptr(),
-                                               self._kernels._stream()), "hvpr_fused_adam_truewd_f32")
+            raise RuntimeError("hvpr_amd: %s steps on the GPU (the HIP path has no CPU fallback)" % type(self).__name__)
+        check(getattr(lib(), name)(self.flat_p.data_ptr(), self.flat_g.data_ptr(), *args,
+                                   None if self._scale is None else self._scale.data_ptr(), self._kernels._stream()), name)
         # the kernel writes the parameters through a raw pointer: torch's version counters do not see it, so whatever is derived from
         # the weights and cached by version (conv_train's packed Winograd filters) is told here
         from . import conv_train
         conv_train.weights_changed()
+
+
+class FusedAdamOneCycle(_FlatOptimizer):
+    """The same optimiser as AdamOneCycle on ONE flat fp32 buffer: every trainable parameter becomes a view into `flat_p`, its
+    gradient a view into `flat_g`, and a step is one launch of hvpr_fused_adam_truewd_f32 (decay + Adam + the gradient-norm
+    clip as a device-side scale) instead of hundreds of small kernels per tensor (the reference: per-tensor python loops,
+    fastai_optim.py:132-149).  state_dict() / load_state_dict() speak torch.optim.Adam's format in AdamOneCycle's parameter
+    order, so checkpoints move between the two."""
+
+    def __init__(self, model, wd, lr=3e-3, beta2=0.99, eps=1e-8):
+        rest, bn = split_bn_params(model)
+        self.n_rest = len(rest)
+        self._flatten(rest + bn)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat_p), torch.zeros_like(self.flat_p)
+        self.wd, self._lr, self._mom, self.beta2, self.eps = wd, lr, 0.9, beta2, eps
+
+    lr = property(lambda self: self._lr, lambda self, v: setattr(self, "_lr", float(v)))
+    mom = property(lambda self: self._mom, lambda self, v: setattr(self, "_mom", float(v)))
+
+    @property
+    def param_groups(self):
+        return [{"params": self.params[:self.n_rest], "lr": self._lr, "betas": (self._mom, self.beta2)},
+                {"params": self.params[self.n_rest:], "lr": self._lr, "betas": (self._mom, self.beta2)}]
+
+    def _launch(self):
+        """ONE launch of hvpr_fused_adam_truewd_f32 over the flat buffers."""
+        self._call("hvpr_fused_adam_truewd_f32", self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel, self._lr, self._mom,
+                   self.beta2, self.eps, self.wd, self.steps)
 
     def state_dict(self):
         state = {}
@@ -247,19 +268,199 @@ class FusedAdamOneCycle:
             self.wd, self.beta2, self._lr, self._mom = float(extra["wd"]), float(extra["beta2"]), float(extra["lr"]), float(extra["mom"])
 
 
+class _FlatTorchOptimizer(_FlatOptimizer):
+    """The flat form of a plain torch optimiser over `model.parameters()` (tools/train_utils/optimization/__init__.py:12-18): ONE
+    parameter group in that order, no BatchNorm split.  State indices count EVERY parameter, as torch's do: one with
+    requires_grad=False keeps its index, is not in the flat buffer and has no state.  `param_groups` is one dict with torch's keys
+    (a schedule writes `lr` and `initial_lr` into it), `lr` reads and writes it — the loop's `float(optimizer.lr)`
+    (train_utils.py:28) works.  state_dict() / load_state_dict() speak the torch optimiser's own format, so checkpoints move
+    between this class, the per-tensor form and the reference; one step counter serves the whole buffer.
+
+    An ABSENT gradient is a ZERO gradient (FusedAdamOneCycle's convention): a trainable parameter that took no part in the
+    backward pass is still stepped — decay and momentum act on it — where torch skips it and gives it no state."""
+    _STATE = ()                          # (state-dict key, attribute holding the flat buffer)
+
+    def __init__(self, model, defaults):
+        every = list(model.parameters())
+        self.index = [i for i, p in enumerate(every) if p.requires_grad]          # state-dict index of each flat parameter
+        self._flatten([every[i] for i in self.index])
+        self.param_groups = [dict(defaults, params=every)]
+
+    @property
+    def lr(self):
+        return self.param_groups[0]["lr"]
+
+    @lr.setter
+    def lr(self, v):
+        self.param_groups[0]["lr"] = float(v)
+
+    def _has_state(self):
+        return self.steps > 0
+
+    def state_dict(self):
+        state = {}
+        if self._has_state():
+            bufs = [(k, self._views(getattr(self, a))) for k, a in self._STATE]
+            for j, i in enumerate(self.index):
+                state[i] = {"step": torch.tensor(float(self.steps))} if self._STEP else {}
+                state[i].update((k, v[j].clone()) for k, v in bufs)
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(self.param_groups[0]["params"])))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.param_groups[0]["params"]):
+            raise ValueError("%s: the state dict holds %d group(s) of %s parameters, this optimiser one of %d" % (
+                type(self).__name__, len(groups), [len(g["params"]) for g in groups], len(self.param_groups[0]["params"])))
+        slot = {i: j for j, i in enumerate(self.index)}
+        with torch.no_grad():
+            bufs = [(k, getattr(self, a), self._views(getattr(self, a))) for k, a in self._STATE]
+            for _, flat, _ in bufs:
+                flat.zero_()
+            steps = 0
+            for i, st in sd["state"].items():
+                j = slot.get(int(i))
+                if j is None:
+                    continue
+                for k, _, views in bufs:
+                    if st.get(k) is not None:
+                        views[j].copy_(st[k])
+                        steps = max(steps, 1)
+                if "step" in st:
+                    steps = max(steps, int(float(st["step"])))
+            self.steps = steps
+        self.param_groups[0].update({k: v for k, v in groups[0].items() if k != "params"})
+
+
+_TORCH_GROUP = {"maximize": False, "foreach": None, "differentiable": False, "fused": None}
+
+
+class FusedAdam(_FlatTorchOptimizer):
+    """torch.optim.Adam(model.parameters(), lr, weight_decay) — build_optimizer's 'adam', coupled (L2) decay — as one launch of
+    hvpr_fused_adam_l2_f32 per step.  State per index: {"step", "exp_avg", "exp_avg_sq"}."""
+    _STATE, _STEP = (("exp_avg", "exp_avg"), ("exp_avg_sq", "exp_avg_sq")), True
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(model, dict(_TORCH_GROUP, lr=float(lr), betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                     capturable=False, decoupled_weight_decay=False))
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat_p), torch.zeros_like(self.flat_p)
+
+    def _launch(self):
+        g = self.param_groups[0]
+        self._call("hvpr_fused_adam_l2_f32", self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel, g["lr"], g["betas"][0],
+                   g["betas"][1], g["eps"], g["weight_decay"], self.steps)
+
+
+class FusedSGD(_FlatTorchOptimizer):
+    """torch.optim.SGD(model.parameters(), lr, momentum, weight_decay) — build_optimizer's 'sgd', dampening 0, no Nesterov — as one
+    launch of hvpr_fused_sgd_f32 per step.  State per index: {"momentum_buffer"}; none at momentum 0.  The buffer starts zeroed,
+    which reproduces torch's first step (buf = d) with no step counter."""
+    _STEP = False
+
+    def __init__(self, model, lr=1e-3, momentum=0.0, weight_decay=0.0):
+        super().__init__(model, dict(_TORCH_GROUP, lr=float(lr), momentum=momentum, dampening=0, weight_decay=weight_decay,
+                                     nesterov=False))
+        self.momentum_buffer = torch.zeros_like(self.flat_p) if momentum != 0 else None
+        self._STATE = (("momentum_buffer", "momentum_buffer"),) if momentum != 0 else ()
+
+    def _has_state(self):
+        return self.steps > 0 and self.momentum_buffer is not None
+
+    def _launch(self):
+        g = self.param_groups[0]
+        if (g["momentum"] != 0) != (self.momentum_buffer is not None):
+            raise ValueError("FusedSGD: momentum changed between zero and non-zero after construction")
+        self._call("hvpr_fused_sgd_f32", None if self.momentum_buffer is None else self.momentum_buffer.data_ptr(), self.numel, g["lr"],
+                   g["momentum"], g["weight_decay"])
+
+
+class _IterationSchedule:
+    """A learning rate that is a pure function of the iteration: step(it) writes lr(it) into every parameter group, so a resumed
+    run gets what the uninterrupted one got.  Own classes, since torch's schedulers refuse an object that is not a
+    torch.optim.Optimizer; like them, the constructor records `initial_lr` in each group and takes one step (to last_epoch + 1)."""
+
+    def __init__(self, optimizer, last_epoch=-1):
+        self.optimizer = optimizer
+        for g in optimizer.param_groups:
+            if last_epoch == -1:
+                g.setdefault("initial_lr", g["lr"])
+            elif "initial_lr" not in g:
+                raise KeyError("param 'initial_lr' is not specified in param_groups when resuming an optimizer")
+        self.base_lrs = [g["initial_lr"] for g in optimizer.param_groups]
+        self.step(last_epoch + 1)
+
+    def step(self, it):
+        self.last_epoch = it
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = self.lr_at(it, base)
+
+
+class StepDecayLR(_IterationSchedule):
+    """LambdaLR(lr_lbmd) of build_scheduler (tools/train_utils/optimization/__init__.py:40-55), in its operation order:
+    lr(it) = LR * max(LR_DECAY multiplied once per passed decay step, LR_CLIP / LR)."""
+
+    def __init__(self, optimizer, decay_steps, lr_decay, lr_clip, lr, last_epoch=-1):
+        self.decay_steps, self.lr_decay, self.floor = list(decay_steps), lr_decay, lr_clip / lr
+        super().__init__(optimizer, last_epoch)
+
+    def factor(self, it):
+        cur_decay = 1
+        for decay_step in self.decay_steps:
+            if it >= decay_step:
+                cur_decay = cur_decay * self.lr_decay
+        return max(cur_decay, self.floor)
+
+    def lr_at(self, it, base_lr):
+        return base_lr * self.factor(it)
+
+
+class CosineWarmupLR(_IterationSchedule):
+    """learning_schedules_fastai.py:80-89: eta_min -> base lr over T_max iterations along half a cosine."""
+
+    def __init__(self, optimizer, T_max, eta_min=0, last_epoch=-1):
+        self.T_max, self.eta_min = T_max, eta_min
+        super().__init__(optimizer, last_epoch)
+
+    def lr_at(self, it, base_lr):
+        return self.eta_min + (base_lr - self.eta_min) * (1 - math.cos(math.pi * it / self.T_max)) / 2
+
+
 def build_optimizer(model, optim_cfg):
-    """adam_onecycle (tools/train_utils/optimization/__init__.py:19-32).  On the GPU the flat fused optimiser; FUSED: False in the
-    OPTIMIZATION config (or a CPU model) keeps the per-tensor torch.optim.Adam form."""
-    assert optim_cfg.OPTIMIZER == "adam_onecycle", "hvpr path: adam_onecycle (hvpr.yaml:158)"
+    """tools/train_utils/optimization/__init__.py:11-36: 'adam', 'sgd' and 'adam_onecycle'.  On the GPU the flat fused optimisers;
+    FUSED: False in the OPTIMIZATION config (or a CPU model) keeps the per-tensor torch.optim forms, built as the reference builds
+    them."""
     ps = [p for p in model.parameters() if p.requires_grad]
-    if optim_cfg.get("FUSED", True) and ps and all(p.is_cuda and p.dtype == torch.float32 for p in ps):
+    fused = optim_cfg.get("FUSED", True) and ps and all(p.is_cuda and p.dtype == torch.float32 for p in ps)
+    if optim_cfg.OPTIMIZER == "adam":
+        if fused:
+            return FusedAdam(model, lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
+        return torch.optim.Adam(model.parameters(), lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
+    if optim_cfg.OPTIMIZER == "sgd":
+        if fused:
+            return FusedSGD(model, lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY, momentum=optim_cfg.MOMENTUM)
+        return torch.optim.SGD(model.parameters(), lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY, momentum=optim_cfg.MOMENTUM)
+    if optim_cfg.OPTIMIZER != "adam_onecycle":
+        raise NotImplementedError("OPTIMIZATION.OPTIMIZER %r: adam, sgd or adam_onecycle" % (optim_cfg.OPTIMIZER,))
+    if fused:
         return FusedAdamOneCycle(model, wd=optim_cfg.WEIGHT_DECAY)
     return AdamOneCycle(model, wd=optim_cfg.WEIGHT_DECAY)
 
 
 def build_scheduler(optimizer, total_iters_each_epoch, total_epochs, last_epoch, optim_cfg):
+    """(lr_scheduler, lr_warmup_scheduler) of tools/train_utils/optimization/__init__.py:39-63; the second is None unless LR_WARMUP.
+    The reference's T_max, WARMUP_EPOCH * len(total_iters_each_epoch), raises TypeError on the int (:59); here it is
+    WARMUP_EPOCH * total_iters_each_epoch."""
     total = total_iters_each_epoch * total_epochs
-    return OneCycle(optimizer, total, optim_cfg.LR, list(optim_cfg.MOMS), optim_cfg.DIV_FACTOR, optim_cfg.PCT_START), None
+    if optim_cfg.OPTIMIZER == "adam_onecycle":
+        return OneCycle(optimizer, total, optim_cfg.LR, list(optim_cfg.MOMS), optim_cfg.DIV_FACTOR, optim_cfg.PCT_START), None
+    decay_steps = [x * total_iters_each_epoch for x in optim_cfg.DECAY_STEP_LIST]
+    lr_scheduler = StepDecayLR(optimizer, decay_steps, optim_cfg.LR_DECAY, optim_cfg.LR_CLIP, optim_cfg.LR, last_epoch=last_epoch)
+    lr_warmup_scheduler = None
+    if optim_cfg.LR_WARMUP:
+        lr_warmup_scheduler = CosineWarmupLR(optimizer, T_max=optim_cfg.WARMUP_EPOCH * total_iters_each_epoch,
+                                             eta_min=optim_cfg.LR / optim_cfg.DIV_FACTOR)
+    return lr_scheduler, lr_warmup_scheduler
 
 
 def checkpoint_state(model=None, optimizer=None, epoch=None, it=None):

@@ -89,15 +89,15 @@ def main(argv=None):
     net = model
     if dist_train:
         model = distributed.wrap_ddp(model, device)
-    lr_scheduler, _ = optim.build_scheduler(optimizer, total_iters_each_epoch=len(train_loader), total_epochs=epochs,
-                                            last_epoch=last_epoch, optim_cfg=cfg.OPTIMIZATION)
+    lr_scheduler, lr_warmup_scheduler = optim.build_scheduler(optimizer, total_iters_each_epoch=len(train_loader), total_epochs=epochs,
+                                                              last_epoch=last_epoch, optim_cfg=cfg.OPTIMIZATION)
 
     logger.info("**********************Start training %s(%s)**********************" % (cfg.TAG, args.extra_tag))
     train_loop.train_model(model, optimizer, train_loader, optim.model_fn_decorator(), lr_scheduler, cfg.OPTIMIZATION,
                            start_epoch=start_epoch, total_epochs=epochs, start_iter=int(it), rank=rank, ckpt_save_dir=ckpt_dir,
                            logger=logger, train_sampler=train_sampler, ckpt_save_interval=args.ckpt_save_interval,
                            max_ckpt_save_num=args.max_ckpt_save_num, log_interval=args.log_interval,
-                           scalars_path=output_dir / "scalars.jsonl")
+                           scalars_path=output_dir / "scalars.jsonl", lr_warmup_scheduler=lr_warmup_scheduler)
     logger.info("**********************End training %s(%s)**********************" % (cfg.TAG, args.extra_tag))
 
     results = None

@@ -97,9 +97,10 @@ def rotate_checkpoints(ckpt_save_dir, max_ckpt_save_num):
 
 def train_model(model, optimizer, train_loader, model_func, lr_scheduler, optim_cfg, start_epoch, total_epochs, start_iter, rank,
                 ckpt_save_dir, logger, train_sampler=None, ckpt_save_interval=1, max_ckpt_save_num=50,
-                merge_all_iters_to_one_epoch=False, log_interval=50, scalars_path=None):
+                merge_all_iters_to_one_epoch=False, log_interval=50, scalars_path=None, lr_warmup_scheduler=None):
     """Epochs start_epoch .. total_epochs - 1; a checkpoint `checkpoint_epoch_<e>.pth` every ckpt_save_interval epochs on rank 0.
-    Returns the iteration count."""
+    `lr_warmup_scheduler` (build_scheduler's second value) steps instead of `lr_scheduler` in the epochs before
+    optim_cfg.WARMUP_EPOCH (train_utils.py:82-85).  Returns the iteration count."""
     if merge_all_iters_to_one_epoch:
         raise NotImplementedError("merge_all_iters_to_one_epoch is not built")
     accumulated_iter = start_iter
@@ -107,7 +108,9 @@ def train_model(model, optimizer, train_loader, model_func, lr_scheduler, optim_
     for cur_epoch in range(start_epoch, total_epochs):
         if train_sampler is not None:
             train_sampler.set_epoch(cur_epoch)
-        accumulated_iter, items = train_one_epoch(model, optimizer, train_loader, model_func, lr_scheduler, accumulated_iter, optim_cfg,
+        warming_up = lr_warmup_scheduler is not None and cur_epoch < optim_cfg.WARMUP_EPOCH
+        cur_scheduler = lr_warmup_scheduler if warming_up else lr_scheduler
+        accumulated_iter, items = train_one_epoch(model, optimizer, train_loader, model_func, cur_scheduler, accumulated_iter, optim_cfg,
                                                   rank=rank, scalar_log=scalar_log, logger=logger)
         trained_epoch = cur_epoch + 1
         logger.info("**********************Epoch%d training finished**********************" % trained_epoch)

@@ -650,6 +650,18 @@ int hvpr_mse_loss_f32(const float *x, const float *target, long long rows, int c
 int hvpr_fused_adam_truewd_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, long long n, float lr,
                                float beta1, float beta2, float eps, float weight_decay, int step,
                                const float *grad_scale_device, hvpr_stream_t stream);
+/*     The other two optimisers of build_optimizer (tools/train_utils/optimization/__init__.py:12-18) over the same flat buffers,
+ *     with the same grad_scale_device and the same argument rules (n == 0: HVPR_OK without a launch; n < 0, a NULL or
+ *     misaligned required pointer, step < 1, a beta or momentum outside [0, 1): HVPR_ERR_INVALID_ARG).
+ *     hvpr_fused_adam_l2_f32: torch.optim.Adam with COUPLED decay — g' = g * scale + weight_decay * p, then the same Adam step on g'.
+ *     hvpr_fused_sgd_f32: torch.optim.SGD with dampening 0 and no Nesterov — d = g * scale + weight_decay * p; with momentum != 0
+ *     buf = momentum * buf + d, d = buf; p -= lr * d.  momentum_buf starts zeroed (0 * momentum + d == d is torch's first step, so
+ *     there is no step counter); momentum == 0 takes a NULL momentum_buf (one given is neither read nor written). */
+int hvpr_fused_adam_l2_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, long long n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, int step, const float *grad_scale_device,
+                           hvpr_stream_t stream);
+int hvpr_fused_sgd_f32(float *params, const float *grads, float *momentum_buf, long long n, float lr, float momentum,
+                       float weight_decay, const float *grad_scale_device, hvpr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------
