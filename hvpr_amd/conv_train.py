@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import kernels
-from ._lib import check, lib
+from ._lib import call, lib
 
 _ws_cache = {}
 
@@ -164,12 +164,10 @@ def bn_statistics(z, eps, partials=None):
     mean, var, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
     if partials is not None and partials.numel() > 0:
         assert partials.shape[-1] == C and partials.shape[1] == 2
-        check(lib().hvpr_bn_finalize_partials_f32(partials.data_ptr(), partials.shape[0], C, P, float(eps), mean.data_ptr(), var.data_ptr(),
-                                                  invstd.data_ptr(), kernels._stream()), "hvpr_bn_finalize_partials_f32")
+        call("hvpr_bn_finalize_partials_f32", partials, partials.shape[0], C, P, float(eps), mean, var, invstd, kernels._stream())
     else:
         ws = _workspace(lib().hvpr_bn_workspace_bytes(P, C), dev)
-        check(lib().hvpr_bn_stats_nhwc_f32(kernels._ptr(z, torch.float32, "z"), P, C, float(eps), mean.data_ptr(), var.data_ptr(),
-                                           invstd.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_bn_stats_nhwc_f32")
+        call("hvpr_bn_stats_nhwc_f32", z, P, C, float(eps), mean, var, invstd, ws, ws.numel(), kernels._stream())
     sg = _sync_group()
     if sg is None:
         return mean, var, invstd, P
@@ -196,10 +194,8 @@ def _affine(mean, var, invstd, gamma, beta, count, bn):
     running = _running_of(bn)
     rm, rv, nbt, m = running if running is not None else (None, None, None, 0.0)
     mu = m * count / max(count - 1, 1)
-    check(lib().hvpr_bn_train_affine_f32(mean.data_ptr(), var.data_ptr(), invstd.data_ptr(), mean.numel(), kernels._ptr(gamma.detach(), torch.float32, "gamma"),
-                                         kernels._ptr(beta.detach(), torch.float32, "beta"), float(m), float(mu), kernels._ptr(rm, torch.float32, "running_mean"),
-                                         kernels._ptr(rv, torch.float32, "running_var"), kernels._ptr(nbt, torch.int64, "num_batches_tracked"),
-                                         scale.data_ptr(), shift.data_ptr(), kernels._stream()), "hvpr_bn_train_affine_f32")
+    call("hvpr_bn_train_affine_f32", mean, var, invstd, mean.numel(), gamma.detach(), beta.detach(), float(m), float(mu), rm, rv, nbt,
+         scale, shift, kernels._stream())
     if running is None:
         _update_running(bn, mean, var, count)
     else:                   # the kernel wrote the buffers through raw pointers: let torch's version counters know (no launch)
@@ -225,10 +221,7 @@ def _bn_forward(z, gamma, beta, eps, partials, bn, relu, gate=None, resid=None, 
     mean, var, invstd, count = bn_statistics(z, eps, partials)
     scale, shift = _affine(mean, var, invstd, gamma, beta, count, bn)
     y = torch.empty_like(z) if out is None else out
-    check(lib().hvpr_bn_relu_fwd_nhwc_f32(z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(), 1 if relu else 0,
-                                          kernels._ptr(gate, torch.float32, "gate"), kernels._ptr(resid, torch.float32, "resid"),
-                                          kernels._ptr(y, torch.float32, "out"), y.shape[-1], out_coff, kernels._stream()),
-          "hvpr_bn_relu_fwd_nhwc_f32")
+    call("hvpr_bn_relu_fwd_nhwc_f32", z, P, C, scale, shift, 1 if relu else 0, gate, resid, y, y.shape[-1], out_coff, kernels._stream())
     return y, (scale, shift, mean, invstd), count
 
 
@@ -242,18 +235,15 @@ def _bn_backward(dy, dy_cstride, dy_coff, z, scale, shift, mean, invstd, relu, g
     dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
     dgate = torch.empty_like(gate) if gate is not None else None
     ws = _workspace(lib().hvpr_bn_workspace_bytes(P, C), z.device)
-    common = (kernels._ptr(dy, torch.float32, "dy"), dy_cstride, dy_coff, z.data_ptr(), P, C, scale.data_ptr(), shift.data_ptr(),
-              mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0, kernels._ptr(gate))
-    check(lib().hvpr_bn_relu_bwd_sums_nhwc_f32(*common, dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-          "hvpr_bn_relu_bwd_sums_nhwc_f32")
+    common = (dy, dy_cstride, dy_coff, z, P, C, scale, shift, mean, invstd, 1 if relu else 0, gate)
+    call("hvpr_bn_relu_bwd_sums_nhwc_f32", *common, dgamma, dbeta, ws, ws.numel(), kernels._stream())
     sg = _sync_group()
     if sg is not None and torch.is_tensor(count):
         dg_t, db_t = sync_backward_sums(dgamma, dbeta, count, sg[0])          # over the global batch, divided by its count
         inv_n = 1.0
     else:
         dg_t, db_t, inv_n = dgamma, dbeta, 1.0 / P
-    check(lib().hvpr_bn_relu_bwd_apply_nhwc_f32(*common, kernels._ptr(dgate), dz.data_ptr(), dg_t.data_ptr(), db_t.data_ptr(), inv_n,
-                                                kernels._stream()), "hvpr_bn_relu_bwd_apply_nhwc_f32")
+    call("hvpr_bn_relu_bwd_apply_nhwc_f32", *common, dgate, dz, dg_t, db_t, inv_n, kernels._stream())
     return dz, dgamma, dbeta, dgate
 
 
@@ -357,15 +347,11 @@ def conv_wgrad(x, dz, taps, stride, cout, cin):
     if taps == 9 and stride == 1 and kernels.conv_algo() == "winograd" and _wino_wgrad_fits(H, W, cin, cout):
         nbytes = lib().hvpr_conv2d_wino_wgrad_workspace_bytes(N, H, W, cin, cout)
         ws = _workspace(nbytes, x.device)
-        check(lib().hvpr_conv2d_wino_wgrad_nhwc_f32(kernels._ptr(x, torch.float32, "x"), N, H, W, cin, kernels._ptr(dz, torch.float32, "dz"),
-                                                    cout, dw.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-              "hvpr_conv2d_wino_wgrad_nhwc_f32")
+        call("hvpr_conv2d_wino_wgrad_nhwc_f32", x, N, H, W, cin, dz, cout, dw, ws, ws.numel(), kernels._stream())
         return dw
     nbytes = lib().hvpr_conv2d_wgrad_workspace_bytes(N, OH, OW, cin, cout, taps, stride)
     ws = _workspace(nbytes, x.device)
-    check(lib().hvpr_conv2d_wgrad_nhwc_f32(kernels._ptr(x, torch.float32, "x"), N, H, W, cin, kernels._ptr(dz, torch.float32, "dz"),
-                                           cout, taps, stride, dw.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-          "hvpr_conv2d_wgrad_nhwc_f32")
+    call("hvpr_conv2d_wgrad_nhwc_f32", x, N, H, W, cin, dz, cout, taps, stride, dw, ws, ws.numel(), kernels._stream())
     return dw
 
 
@@ -603,10 +589,8 @@ class _GateTrain(torch.autograd.Function):
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         gate = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
         ws = _workspace(lib().hvpr_spatial_gate_train_workspace_bytes(N, H, W), dev)
-        check(lib().hvpr_spatial_gate_train_fwd_f32(kernels._ptr(y, torch.float32, "y"), N, H, W, C, w18.data_ptr(), b.data_ptr(), g_.data_ptr(),
-                                                    be.data_ptr(), float(eps), pooled.data_ptr(), argmax.data_ptr(), a.data_ptr(),
-                                                    stats.data_ptr(), gate.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-              "hvpr_spatial_gate_train_fwd_f32")
+        call("hvpr_spatial_gate_train_fwd_f32", y, N, H, W, C, w18, b, g_, be, float(eps), pooled, argmax, a, stats, gate, ws, ws.numel(),
+             kernels._stream())
         ctx.save_for_backward(gate, a, stats, pooled, argmax, w18, g_)
         ctx.dims = (N, H, W, C)
         ctx.wshape = tuple(weight.shape)
@@ -627,10 +611,8 @@ class _GateTrain(torch.autograd.Function):
         dw = torch.empty(18, dtype=torch.float32, device=dev)
         db, dgam, dbet = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(3))
         ws = _workspace(lib().hvpr_spatial_gate_train_workspace_bytes(N, H, W), dev)
-        check(lib().hvpr_spatial_gate_train_bwd_f32(kernels._ptr(dgate, torch.float32, "dgate"), gate.data_ptr(), a.data_ptr(), stats.data_ptr(),
-                                                    pooled.data_ptr(), argmax.data_ptr(), w18.data_ptr(), g_.data_ptr(), N, H, W, C, dy.data_ptr(),
-                                                    dw.data_ptr(), db.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    kernels._stream()), "hvpr_spatial_gate_train_bwd_f32")
+        call("hvpr_spatial_gate_train_bwd_f32", dgate, gate, a, stats, pooled, argmax, w18, g_, N, H, W, C, dy, dw, db, dgam, dbet, ws,
+             ws.numel(), kernels._stream())
         return dy, dw.view(ctx.wshape), db, dgam, dbet, None
 
 

@@ -14,20 +14,21 @@ import os
 
 import numpy as np
 
+from ._lib import read_header
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 
 def _lib():
     global _LIB
     if _LIB is None:
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhvpr_cpu.so")
+        path = os.path.join(_HERE, "libhvpr_cpu.so")
         if not os.path.exists(path):
             raise RuntimeError("hvpr_amd: libhvpr_cpu.so is missing — run `python -m hvpr_amd.build`")
         _LIB = ctypes.CDLL(path)
-        _LIB.hvpr_points_in_boxes_cpu.restype = ctypes.c_int
-        _LIB.hvpr_points_in_boxes_cpu.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        _LIB.hvpr_boxes_bev_iou_cpu.restype = ctypes.c_int
-        _LIB.hvpr_boxes_bev_iou_cpu.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        for name, (res, args, _) in read_header(os.path.join(os.path.dirname(_HERE), "include", "hvpr_cpu.h")).items():
+            getattr(_LIB, name).restype, getattr(_LIB, name).argtypes = res, args
     return _LIB
 
 

@@ -1,29 +1,21 @@
 """Tensor-level wrappers over the C-ABI (include/hvpr_amd.h): torch is used for device memory and streams only.
 
-Every wrapper validates its tensors (device, dtype, contiguity), passes raw pointers plus the current HIP
-stream, and raises on a non-zero status.  There is no CPU path: CPU tensors are rejected.
+Every wrapper hands its tensors and the current HIP stream to _lib.call, which checks each tensor against the header's
+parameter (device, dtype, contiguity), passes its pointer and raises on a non-zero status.  There is no CPU path: CPU
+tensors are rejected.  Host-side arguments (pinned host tensors, numpy and ctypes arrays) go as raw addresses.
 """
 import os
 
 import torch
 
-from ._lib import check, lib
+from ._lib import call, check, lib  # noqa: F401  (check: callers reach it as kernels.check)
 
 
 def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t, dtype=None, name="tensor"):
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError(f"hvpr_amd: {name} must live on the GPU (the HIP path has no CPU fallback)")
-    if dtype is not None and t.dtype != dtype:
-        raise TypeError(f"hvpr_amd: {name} must be {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"hvpr_amd: {name} must be contiguous")
-    return t.data_ptr()
+    try:
+        return torch.cuda.current_stream().cuda_stream
+    except RuntimeError as e:        # no usable GPU: say so in the words every other refusal of a CPU run uses
+        raise RuntimeError(f"hvpr_amd needs a GPU (the HIP path has no CPU fallback): {e}") from e
 
 
 # ------------------------------------------------------------------------------------------------ voxelizer
@@ -40,15 +32,13 @@ class VoxelizeWorkspace:
 
     def reset(self):
         batch, n_points, (nx, ny, nz), _ = self.key
-        check(lib().hvpr_voxelize_workspace_reset(self.buf.data_ptr(), self.buf.numel(), batch, n_points, nx, ny, nz,
-                                                  _stream()), "hvpr_voxelize_workspace_reset")
+        call("hvpr_voxelize_workspace_reset", self.buf, self.buf.numel(), batch, n_points, nx, ny, nz, _stream())
 
     def status(self):
         """SYNCHRONISES the current stream; raises when a one-launch index kernel (encode_fwd(index_mode=1)) gave up a wait on this
         workspace since its last reset (that call and every later one reported zero pillars): reset() it."""
         batch, n_points, (nx, ny, nz), _ = self.key
-        check(lib().hvpr_voxelize_workspace_status(self.buf.data_ptr(), self.buf.numel(), batch, n_points, nx, ny, nz,
-                                                   _stream()), "hvpr_voxelize_workspace_status")
+        call("hvpr_voxelize_workspace_status", self.buf, self.buf.numel(), batch, n_points, nx, ny, nz, _stream())
 
 
 def voxelize(points, frame_offsets, batch, point_cloud_range, voxel_size, grid, max_points, max_voxels, workspace,
@@ -72,12 +62,9 @@ def voxelize(points, frame_offsets, batch, point_cloud_range, voxel_size, grid, 
     vs = [float(torch.tensor(v, dtype=torch.float32)) for v in voxel_size]
     if workspace.key[0] < batch or workspace.key[1] < n:
         raise ValueError("voxelize workspace too small for this call")
-    check(lib().hvpr_voxelize_f32(_ptr(points, torch.float32, "points"), n, stride, xyz_col, n_feat,
-                                  _ptr(frame_offsets, torch.int32, "frame_offsets"), batch, lo[0], lo[1], lo[2],
-                                  vs[0], vs[1], vs[2], nx, ny, nz, int(max_points), int(max_voxels), int(cap_mode),
-                                  voxels.data_ptr(), coords.data_ptr(), num.data_ptr(), offs.data_ptr(), capacity,
-                                  workspace.buf.data_ptr(), workspace.buf.numel(), workspace.key[0], workspace.key[1],
-                                  _stream()), "hvpr_voxelize_f32")
+    call("hvpr_voxelize_f32", points, n, stride, xyz_col, n_feat, frame_offsets, batch, lo[0], lo[1], lo[2], vs[0], vs[1], vs[2], nx, ny,
+         nz, int(max_points), int(max_voxels), int(cap_mode), voxels, coords, num, offs, capacity, workspace.buf, workspace.buf.numel(),
+         workspace.key[0], workspace.key[1], _stream())
     return voxels, coords, num, offs
 
 
@@ -91,14 +78,9 @@ def pillar_vfe_fwd(voxels, num_points, coords, folded, voxel_size, offsets, m_de
     pf = torch.empty((M, 64), dtype=torch.float32, device=dev)
     sf = torch.empty((M, 32), dtype=torch.float32, device=dev)
     mask = torch.empty((M, P, 1), dtype=torch.float32, device=dev) if want_mask else None
-    check(lib().hvpr_pillar_vfe_fwd_f32(
-        _ptr(voxels, torch.float32, "voxels"), _ptr(num_points, torch.int32, "voxel_num_points"),
-        _ptr(coords, torch.int32, "voxel_coords"), M, P, _ptr(m_device, torch.int32, "m_device"),
-        float(voxel_size[0]), float(voxel_size[1]), float(voxel_size[2]), float(offsets[0]), float(offsets[1]),
-        float(offsets[2]), _ptr(folded["w0"], torch.float32), _ptr(folded["b0"], torch.float32),
-        _ptr(folded["w1"], torch.float32), _ptr(folded["b1"], torch.float32), _ptr(folded["ws0"], torch.float32),
-        _ptr(folded["bs0"], torch.float32), _ptr(folded["ws1"], torch.float32), _ptr(folded["bs1"], torch.float32),
-        pf.data_ptr(), sf.data_ptr(), _ptr(mask), _stream()), "hvpr_pillar_vfe_fwd_f32")
+    call("hvpr_pillar_vfe_fwd_f32", voxels, num_points, coords, M, P, m_device, float(voxel_size[0]), float(voxel_size[1]),
+         float(voxel_size[2]), float(offsets[0]), float(offsets[1]), float(offsets[2]), folded["w0"], folded["b0"], folded["w1"],
+         folded["b1"], folded["ws0"], folded["bs0"], folded["ws1"], folded["bs1"], pf, sf, mask, _stream())
     return pf, sf, mask
 
 
@@ -117,26 +99,22 @@ class PackedBank:
         self.shape = w.shape
         self.rows = w                 # row-major copy: the k selected rows are gathered from it
         self.data = torch.empty(lib().hvpr_memory_bank_packed_floats(self.n_items), dtype=torch.float32, device=w.device)
-        check(lib().hvpr_memory_bank_pack_f32(_ptr(w, torch.float32, "memory.weight"), self.n_items, self.data.data_ptr(), _stream()),
-              "hvpr_memory_bank_pack_f32")
+        call("hvpr_memory_bank_pack_f32", w, self.n_items, self.data, _stream())
 
 
 def _bank_args(bank):
     """(row-major pointer, packed pointer, n_items) of a PackedBank; a plain (n_items, 64) tensor is packed here (callers that
     reuse a bank pack it once themselves)."""
     if not isinstance(bank, PackedBank):
-        _ptr(bank, torch.float32, "memory.weight")
         bank = PackedBank(bank)
-    return bank.rows.data_ptr(), bank.data.data_ptr(), bank.n_items
+    return bank.rows, bank.data, bank.n_items
 
 
 def memory_readout_fwd(f, bank, k, m_device=None, want_idx=False):
     M, C = f.shape
     out = torch.empty((M, C), dtype=torch.float32, device=f.device)
     idx = torch.empty((M, k), dtype=torch.int32, device=f.device) if want_idx else None
-    check(lib().hvpr_memory_readout_fwd_f32(_ptr(f, torch.float32, "pillar_features"), M,
-                                            _ptr(m_device, torch.int32, "m_device"), *_bank_args(bank), int(k),
-                                            out.data_ptr(), _ptr(idx), _stream()), "hvpr_memory_readout_fwd_f32")
+    call("hvpr_memory_readout_fwd_f32", f, M, m_device, *_bank_args(bank), int(k), out, idx, _stream())
     return (out, idx) if want_idx else out
 
 
@@ -182,12 +160,10 @@ def segment_sum_rows(src, src_off, C, edge_row, edge_w, chunk_ptr, dest_ptr, n_d
     hvpr_segment_sum_rows_f32: per chunk of <= _SEG_CHUNK edges, then per destination over its chunks (fixed order: reproducible)."""
     n_chunks = chunk_ptr.numel() - 1
     part = torch.empty((n_chunks, C), dtype=torch.float32, device=src.device)
-    check(lib().hvpr_segment_sum_rows_f32(_ptr(src, torch.float32, "src"), src.shape[-1], int(src_off), int(C), _ptr(edge_row, torch.int32, "edge_row"),
-                                          _ptr(edge_w, torch.float32, "edge_w"), _ptr(chunk_ptr, torch.int32, "chunk_ptr"), int(n_chunks),
-                                          part.data_ptr(), int(C), _stream()), "hvpr_segment_sum_rows_f32")
+    call("hvpr_segment_sum_rows_f32", src, src.shape[-1], int(src_off), int(C), edge_row, edge_w, chunk_ptr, int(n_chunks), part, int(C),
+         _stream())
     dst = torch.empty((n_dst, C), dtype=torch.float32, device=src.device)
-    check(lib().hvpr_segment_sum_rows_f32(part.data_ptr(), int(C), 0, int(C), None, None, _ptr(dest_ptr, torch.int32, "dest_ptr"), int(n_dst),
-                                          dst.data_ptr(), int(C), _stream()), "hvpr_segment_sum_rows_f32")
+    call("hvpr_segment_sum_rows_f32", part, int(C), 0, int(C), None, None, dest_ptr, int(n_dst), dst, int(C), _stream())
     return dst
 
 
@@ -264,11 +240,9 @@ def attend_rows(q, rows, idx=None, k=None):
     M, C = q.shape
     if rows.dim() != 2 or rows.shape[1] != C or (idx is not None and idx.shape[0] != M):
         raise ValueError("hvpr_amd: attend_rows needs q (M, C), rows (N, C) and idx (M, k)")
-    qp, rp, ip = _ptr(q, torch.float32, "q"), _ptr(rows, torch.float32, "rows"), _ptr(idx, torch.int32, "idx")
     out = torch.empty((M, C), dtype=torch.float32, device=q.device)
     w = torch.empty((M, int(k)), dtype=torch.float32, device=q.device)
-    check(lib().hvpr_attend_rows_fwd_f32(qp, M, rp, rows.shape[0], ip, int(k), C, out.data_ptr(), w.data_ptr(), _stream()),
-          "hvpr_attend_rows_fwd_f32")
+    call("hvpr_attend_rows_fwd_f32", q, M, rows, rows.shape[0], idx, int(k), C, out, w, _stream())
     return out, w
 
 
@@ -286,11 +260,8 @@ def scatter_bev_fwd(pillar, memory, scale, coords, batch, nx, ny, workspace, m_d
     dev = pillar.device
     spatial = torch.empty((batch, ny, nx, cp + cm), dtype=torch.float32, device=dev)
     spatial_scale = torch.empty((batch, ny, nx, cs), dtype=torch.float32, device=dev) if cs else None
-    check(lib().hvpr_scatter_bev_fwd_f32(_ptr(pillar, torch.float32, "pillar_features"), cp, _ptr(memory, torch.float32),
-                                         cm, _ptr(scale, torch.float32), cs, _ptr(coords, torch.int32, "voxel_coords"),
-                                         M, _ptr(m_device, torch.int32), batch, nx, ny, spatial.data_ptr(),
-                                         _ptr(spatial_scale), workspace.data_ptr(), workspace.numel() * 4, _stream()),
-          "hvpr_scatter_bev_fwd_f32")
+    call("hvpr_scatter_bev_fwd_f32", pillar, cp, memory, cm, scale, cs, coords, M, m_device, batch, nx, ny, spatial, spatial_scale,
+         workspace, workspace.numel() * 4, _stream())
     spatial = spatial.permute(0, 3, 1, 2)
     if spatial_scale is not None:
         spatial_scale = spatial_scale.permute(0, 3, 1, 2)
@@ -359,9 +330,8 @@ def deconv_nhwc_bf3(xs, pc, out, out_coff=0):
     N, H, W, groups, planes, _ = xs.shape
     assert groups * 8 == pc.cin and planes == pc.planes and xs.is_contiguous()
     assert out.shape[:3] == (N, H * pc.up, W * pc.up) and out.is_contiguous() and out.dtype == torch.float32
-    check(lib().hvpr_deconv_nhwc_bf16x3(xs.data_ptr(), N, H, W, pc.cin, pc.w.data_ptr(), pc.bias.data_ptr(), pc.cout, pc.cout_pad,
-                                        pc.up, 1 if pc.relu else 0, out.data_ptr(), out.shape[-1], out_coff, planes, _stream()),
-          "hvpr_deconv_nhwc_bf16x3")
+    call("hvpr_deconv_nhwc_bf16x3", xs, N, H, W, pc.cin, pc.w, pc.bias, pc.cout, pc.cout_pad, pc.up, 1 if pc.relu else 0, out,
+         out.shape[-1], out_coff, planes, _stream())
     return out
 
 
@@ -369,8 +339,7 @@ def split_bf16(x, planes=2):
     """fp32 NHWC (..., C), C % 8 == 0 -> split-bf16 NHWC as a bf16 tensor (..., C/8, planes, 8)."""
     assert x.is_contiguous() and x.shape[-1] % 8 == 0 and x.dtype == torch.float32
     out = torch.empty((*x.shape[:-1], x.shape[-1] // 8, planes, 8), dtype=torch.bfloat16, device=x.device)
-    check(lib().hvpr_split_bf16_f32(_ptr(x, torch.float32, "activations"), x.numel(), planes, out.data_ptr(), _stream()),
-          "hvpr_split_bf16_f32")
+    call("hvpr_split_bf16_f32", x, x.numel(), planes, out, _stream())
     return out
 
 
@@ -379,7 +348,7 @@ def unsplit_bf16(xs):
     assert xs.is_contiguous() and xs.dtype == torch.bfloat16 and xs.shape[-1] == 8
     planes = xs.shape[-2]
     out = torch.empty((*xs.shape[:-3], xs.shape[-3] * 8), dtype=torch.float32, device=xs.device)
-    check(lib().hvpr_unsplit_bf16_f32(xs.data_ptr(), out.numel(), planes, out.data_ptr(), _stream()), "hvpr_unsplit_bf16_f32")
+    call("hvpr_unsplit_bf16_f32", xs, out.numel(), planes, out, _stream())
     return out
 
 
@@ -394,11 +363,8 @@ def conv2d_nhwc_bf3(xs, pc, out_split=True, gate=None, resid=None):
         out = torch.empty((N, OH, OW, pc.cout // 8, planes, 8), dtype=torch.bfloat16, device=xs.device)
     else:
         out = torch.empty((N, OH, OW, pc.cout), dtype=torch.float32, device=xs.device)
-    check(lib().hvpr_conv2d_nhwc_bf16x3(xs.data_ptr(), N, H, W, cin, pc.w.data_ptr(), pc.bias.data_ptr(), pc.stride, pc.cout,
-                                        pc.cout_pad, 1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
-                                        None if resid is None else resid.data_ptr(), 0 if resid is None else resid.shape[3] * 8,
-                                        out.data_ptr(), 1 if out_split else 0, pc.cout, 0, pc.tile_cfg, planes, _stream()),
-          "hvpr_conv2d_nhwc_bf16x3")
+    call("hvpr_conv2d_nhwc_bf16x3", xs, N, H, W, cin, pc.w, pc.bias, pc.stride, pc.cout, pc.cout_pad, 1 if pc.relu else 0, gate, resid,
+         0 if resid is None else resid.shape[3] * 8, out, 1 if out_split else 0, pc.cout, 0, pc.tile_cfg, planes, _stream())
     return out
 
 
@@ -418,19 +384,15 @@ def memory_scatter_fwd(pillar, scale, coords, bank, k, batch, nx, ny, workspace,
         spatial_scale = torch.empty((batch, ny, nx, 32), dtype=torch.float32, device=dev)
     if pillar.shape[1] != 64 or scale.shape[1] != 32 or bank.shape[1] != 64:
         raise ValueError("memory_scatter_fwd is specialised for 64 pillar / 64 memory / 32 scale channels")
-    check(lib().hvpr_memory_scatter_fwd_f32(_ptr(pillar, torch.float32, "pillar_features"), _ptr(scale, torch.float32, "scale"),
-                                            _ptr(coords, torch.int32, "voxel_coords"), M, _ptr(m_device, torch.int32),
-                                            *_bank_args(bank), int(k), batch, nx, ny,
-                                            mem.data_ptr(), spatial.data_ptr(), spatial_scale.data_ptr(), workspace.data_ptr(),
-                                            workspace.numel() * 4, _stream()), "hvpr_memory_scatter_fwd_f32")
+    call("hvpr_memory_scatter_fwd_f32", pillar, scale, coords, M, m_device, *_bank_args(bank), int(k), batch, nx, ny, mem, spatial,
+         spatial_scale, workspace, workspace.numel() * 4, _stream())
     return mem, spatial.permute(0, 3, 1, 2), spatial_scale.permute(0, 3, 1, 2)
 
 
 def frame_offsets(points, batch):
     """(batch+1,) i32 frame offsets of a collated (N, C) point tensor whose column 0 is the batch index (one launch)."""
     offs = torch.empty((batch + 1,), dtype=torch.int32, device=points.device)
-    check(lib().hvpr_frame_offsets_f32(_ptr(points, torch.float32, "points"), points.shape[0], points.shape[1], int(batch),
-                                       offs.data_ptr(), _stream()), "hvpr_frame_offsets_f32")
+    call("hvpr_frame_offsets_f32", points, points.shape[0], points.shape[1], int(batch), offs, _stream())
     return offs
 
 
@@ -474,15 +436,11 @@ def encode_fwd(points, frame_offsets, batch, point_cloud_range, voxel_size, grid
     vs = [float(torch.tensor(v, dtype=torch.float32)) for v in voxel_size]
     if workspace.key[0] < batch or workspace.key[1] < n:
         raise ValueError("voxelize workspace too small for this call")
-    check(lib().hvpr_encode_fwd_f32(
-        _ptr(points, torch.float32, "points"), n, stride, xyz_col, n_feat, _ptr(frame_offsets, torch.int32, "frame_offsets"),
-        batch, lo[0], lo[1], lo[2], vs[0], vs[1], vs[2], nx, ny, nz, int(max_points), int(max_voxels), int(cap_mode),
-        float(offsets[0]), float(offsets[1]), float(offsets[2]),
-        _ptr(folded["w0"], torch.float32), _ptr(folded["b0"], torch.float32), _ptr(folded["w1"], torch.float32),
-        _ptr(folded["b1"], torch.float32), _ptr(folded["ws0"], torch.float32), _ptr(folded["bs0"], torch.float32),
-        _ptr(folded["ws1"], torch.float32), _ptr(folded["bs1"], torch.float32), *_bank_args(bank), int(k), _ptr(voxels), coords.data_ptr(), num.data_ptr(), offs.data_ptr(), capacity, pf.data_ptr(),
-        sf.data_ptr(), _ptr(mask), mem.data_ptr(), spatial.data_ptr(), spatial_scale.data_ptr(), _ptr(state), workspace.buf.data_ptr(),
-        workspace.buf.numel(), workspace.key[0], workspace.key[1], int(index_mode), _stream()), "hvpr_encode_fwd_f32")
+    call("hvpr_encode_fwd_f32", points, n, stride, xyz_col, n_feat, frame_offsets, batch, lo[0], lo[1], lo[2], vs[0], vs[1], vs[2], nx, ny,
+         nz, int(max_points), int(max_voxels), int(cap_mode), float(offsets[0]), float(offsets[1]), float(offsets[2]), folded["w0"],
+         folded["b0"], folded["w1"], folded["b1"], folded["ws0"], folded["bs0"], folded["ws1"], folded["bs1"], *_bank_args(bank), int(k),
+         voxels, coords, num, offs, capacity, pf, sf, mask, mem, spatial, spatial_scale, state, workspace.buf, workspace.buf.numel(),
+         workspace.key[0], workspace.key[1], int(index_mode), _stream())
     return {"voxels": voxels, "coords": coords, "num_points": num, "voxel_offsets": offs, "pillar_features": pf,
             "pillar_scale_features": sf, "pillar_mask": mask, "memory_features": mem,
             "spatial": spatial.permute(0, 3, 1, 2), "spatial_scale": spatial_scale.permute(0, 3, 1, 2)}
@@ -547,28 +505,26 @@ class PackedConvWino:
 
 
 def _walk_table(pc, N, H, W, device):
-    """Address of the packed layer's walk table for (N, H, W) — the items of the persistent kernel's walk, read instead of divided
-    for — or 0 (the in-kernel decode).  The table is a tensor on the packed-layer object, built by the first eager call with the
-    shape, so it lives as long as the packed weights a captured graph bakes in; a call inside a capture that finds none passes 0
+    """The packed layer's walk table for (N, H, W) — the items of the persistent kernel's walk, read instead of divided for — or
+    None (the in-kernel decode).  The table is a tensor on the packed-layer object, built by the first eager call with the
+    shape, so it lives as long as the packed weights a captured graph bakes in; a call inside a capture that finds none passes None
     and neither allocates nor launches the builder."""
     key = (N, H, W)
     t = pc.tabs.get(key)
     if t is None:
         if torch.cuda.is_current_stream_capturing():
-            return 0
+            return None
         if isinstance(pc, PackedConvWino):
-            shape = (N, H, W, pc.cout, pc.px_groups)
-            size, build = lib().hvpr_conv2d_wino_tab_bytes, lib().hvpr_conv2d_wino_tab_build
+            shape, op = (N, H, W, pc.cout, pc.px_groups), "hvpr_conv2d_wino_tab"
         else:
-            shape = (N, H, W, pc.taps, pc.stride, pc.cout_pad, pc.tile_cfg)
-            size, build = lib().hvpr_conv2d_tab_bytes, lib().hvpr_conv2d_tab_build
-        nbytes = size(*shape)
+            shape, op = (N, H, W, pc.taps, pc.stride, pc.cout_pad, pc.tile_cfg), "hvpr_conv2d_tab"
+        nbytes = getattr(lib(), op + "_bytes")(*shape)
         t = torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
         if nbytes:
-            check(build(*shape, t.data_ptr(), _stream()), "walk table build")
+            call(op + "_build", *shape, t, _stream())
             torch.cuda.current_stream().synchronize()      # once per layer and shape: later calls may come on any stream
         pc.tabs[key] = t
-    return t.data_ptr() if t.numel() else 0
+    return t if t.numel() else None
 
 
 def pack_conv_wino(weight, scale=None, shift=None, relu=True, px_groups=1, adjoint=False):
@@ -582,8 +538,7 @@ def pack_conv_wino(weight, scale=None, shift=None, relu=True, px_groups=1, adjoi
     cout_pad = (cout + 63) // 64 * 64
     wp = torch.empty((lib().hvpr_conv2d_wino_packed_floats(cin, cout),), dtype=torch.float32, device=w.device)
     sc = None if scale is None else scale.detach().float().contiguous()
-    check(lib().hvpr_conv2d_wino_pack_f32(_ptr(w, torch.float32, "conv weight"), _ptr(sc, torch.float32, "scale"), cout, cin,
-                                          1 if adjoint else 0, wp.data_ptr(), _stream()), "hvpr_conv2d_wino_pack_f32")
+    call("hvpr_conv2d_wino_pack_f32", w, sc, cout, cin, 1 if adjoint else 0, wp, _stream())
     if shift is None:                     # raw convolutions (training: packed every call) share one zero bias per size
         key = (cout_pad, w.device)
         if key not in _zero_bias:
@@ -605,13 +560,9 @@ def conv2d_wino_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None, bn_part
     if out is None:
         out = torch.empty((N, H, W, pc.cout), dtype=torch.float32, device=x.device)
     assert out.shape[:3] == (N, H, W) and out.is_contiguous()
-    tab = _walk_table(pc, N, H, W, x.device) if use_table and bn_partials is None and pc.px_groups == 1 else 0
-    check(lib().hvpr_conv2d_wino_nhwc_tab_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(), pc.bias.data_ptr(),
-                                              pc.cout, 1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
-                                              _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
-                                              out.data_ptr(), out.shape[-1], int(out_coff), pc.px_groups,
-                                              _ptr(bn_partials, torch.float32, "bn_partials"), tab, _stream()),
-          "hvpr_conv2d_wino_nhwc_tab_f32")
+    tab = _walk_table(pc, N, H, W, x.device) if use_table and bn_partials is None and pc.px_groups == 1 else None
+    call("hvpr_conv2d_wino_nhwc_tab_f32", x, N, H, W, cin, pc.w, pc.bias, pc.cout, 1 if pc.relu else 0, gate, resid,
+         0 if resid is None else resid.shape[-1], out, out.shape[-1], int(out_coff), pc.px_groups, bn_partials, tab, _stream())
     return out
 
 
@@ -672,13 +623,9 @@ def conv2d_nhwc(x, pc, out=None, out_coff=0, gate=None, resid=None, use_table=Fa
     if out is None:
         out = torch.empty((N, OH * pc.up, OW * pc.up, pc.cout), dtype=torch.float32, device=x.device)
     assert out.shape[:3] == (N, OH * pc.up, OW * pc.up) and out.is_contiguous()
-    tab = _walk_table(pc, N, H, W, x.device) if use_table else 0
-    check(lib().hvpr_conv2d_nhwc_tab_f32(_ptr(x, torch.float32, "conv input"), N, H, W, cin, pc.w.data_ptr(),
-                                         pc.bias.data_ptr(), pc.taps, pc.stride, pc.cout, pc.cout_pad, pc.up,
-                                         1 if pc.relu else 0, _ptr(gate, torch.float32, "gate"),
-                                         _ptr(resid, torch.float32, "resid"), 0 if resid is None else resid.shape[-1],
-                                         out.data_ptr(), out.shape[-1], int(out_coff), pc.tile_cfg, tab, _stream()),
-          "hvpr_conv2d_nhwc_tab_f32")
+    tab = _walk_table(pc, N, H, W, x.device) if use_table else None
+    call("hvpr_conv2d_nhwc_tab_f32", x, N, H, W, cin, pc.w, pc.bias, pc.taps, pc.stride, pc.cout, pc.cout_pad, pc.up, 1 if pc.relu else 0,
+         gate, resid, 0 if resid is None else resid.shape[-1], out, out.shape[-1], int(out_coff), pc.tile_cfg, tab, _stream())
     return out
 
 
@@ -697,8 +644,7 @@ def conv2d_s2_dgrad_nhwc(dz, weight, H, W, pc=None):
     if pc is None:
         pc = pack_conv_s2_dgrad(weight)                                                                    # (Cin, Cout, 3, 3): taps not flipped
     dx = torch.empty((N, H, W, cin), dtype=torch.float32, device=dz.device)
-    check(lib().hvpr_conv2d_s2_dgrad_nhwc_f32(_ptr(dz, torch.float32, "dz"), N, OH, OW, cout, pc.w.data_ptr(), pc.bias.data_ptr(), cin,
-                                              pc.cout_pad, H, W, dx.data_ptr(), cin, 0, _stream()), "hvpr_conv2d_s2_dgrad_nhwc_f32")
+    call("hvpr_conv2d_s2_dgrad_nhwc_f32", dz, N, OH, OW, cout, pc.w, pc.bias, cin, pc.cout_pad, H, W, dx, cin, 0, _stream())
     return dx
 
 
@@ -706,9 +652,7 @@ def conv2d_s2_dgrad_nhwc(dz, weight, H, W, pc=None):
 def spatial_gate(y_nhwc, w18, conv_bias, bn_scale, bn_shift):
     N, H, W, C = y_nhwc.shape
     gate = torch.empty((N, H, W), dtype=torch.float32, device=y_nhwc.device)
-    check(lib().hvpr_spatial_gate_f32(_ptr(y_nhwc, torch.float32, "scale features"), N, H, W, C,
-                                      _ptr(w18, torch.float32, "gate conv weight"), float(conv_bias), float(bn_scale),
-                                      float(bn_shift), gate.data_ptr(), _stream()), "hvpr_spatial_gate_f32")
+    call("hvpr_spatial_gate_f32", y_nhwc, N, H, W, C, w18, float(conv_bias), float(bn_scale), float(bn_shift), gate, _stream())
     return gate
 
 
@@ -726,11 +670,8 @@ def head_decode(head_nhwc, n_anchor, n_class, n_dir_bins, x_shifts, y_shifts, an
         box = torch.empty((N, A, 7), dtype=torch.float32, device=dev)
         scores = torch.empty((N, A), dtype=torch.float32, device=dev) if want_scores else None
         labels = torch.empty((N, A), dtype=torch.int32, device=dev) if want_scores else None
-    check(lib().hvpr_head_decode_f32(_ptr(head_nhwc, torch.float32, "head output"), N, H, W, CH, n_anchor, n_class,
-                                     n_dir_bins, _ptr(x_shifts, torch.float32), _ptr(y_shifts, torch.float32),
-                                     _ptr(anchor_table, torch.float32), float(dir_offset), float(dir_limit_offset),
-                                     float(period), _ptr(cls), box.data_ptr(), _ptr(scores), _ptr(labels), _stream()),
-          "hvpr_head_decode_f32")
+    call("hvpr_head_decode_f32", head_nhwc, N, H, W, CH, n_anchor, n_class, n_dir_bins, x_shifts, y_shifts, anchor_table, float(dir_offset),
+         float(dir_limit_offset), float(period), cls, box, scores, labels, _stream())
     return cls, box, scores, labels
 
 
@@ -764,9 +705,8 @@ def score_topk(scores, score_thresh, pre_max, ws, want_scores=True):
     ss = torch.empty((B, pre_max), dtype=torch.float32, device=dev) if want_scores else None
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     use = score_thresh is not None
-    check(lib().hvpr_score_topk_f32(_ptr(scores, torch.float32, "scores"), B, A, float(score_thresh) if use else 0.0,
-                                    1 if use else 0, int(pre_max), order.data_ptr(), _ptr(ss), counts.data_ptr(),
-                                    ws.topk.data_ptr(), ws.topk.numel(), _stream()), "hvpr_score_topk_f32")
+    call("hvpr_score_topk_f32", scores, B, A, float(score_thresh) if use else 0.0, 1 if use else 0, int(pre_max), order, ss, counts,
+         ws.topk, ws.topk.numel(), _stream())
     return order, ss, counts
 
 
@@ -775,10 +715,8 @@ def nms_bev(boxes, order, n_device, n_max, thresh, max_keep, ws_nms, map_through
     dev = boxes.device
     keep = torch.zeros((max(max_keep, 1),), dtype=torch.int32, device=dev)   # rows past keep_count stay valid ids
     kc = torch.empty((1,), dtype=torch.int32, device=dev)
-    check(lib().hvpr_nms_bev_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[1], _ptr(order, torch.int32),
-                                 _ptr(n_device, torch.int32), int(n_max), float(thresh), int(max_keep),
-                                 1 if map_through_order else 0, keep.data_ptr(), kc.data_ptr(), ws_nms.data_ptr(),
-                                 ws_nms.numel(), _stream()), "hvpr_nms_bev_f32")
+    call("hvpr_nms_bev_f32", boxes, boxes.shape[1], order, n_device, int(n_max), float(thresh), int(max_keep),
+         1 if map_through_order else 0, keep, kc, ws_nms, ws_nms.numel(), _stream())
     return keep, kc
 
 
@@ -791,9 +729,7 @@ def gather_predictions(boxes, scores, labels, keep):
     os_ = torch.empty((K,), dtype=torch.float32, device=dev)
     ol = torch.empty((K,), dtype=torch.int64, device=dev)
     osel = torch.empty((K,), dtype=torch.int64, device=dev)
-    check(lib().hvpr_gather_predictions_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[1], _ptr(scores, torch.float32, "scores"),
-                                            _ptr(labels, torch.int32, "labels"), _ptr(keep, torch.int32, "keep"), K, ob.data_ptr(),
-                                            os_.data_ptr(), ol.data_ptr(), osel.data_ptr(), _stream()), "hvpr_gather_predictions_f32")
+    call("hvpr_gather_predictions_f32", boxes, boxes.shape[1], scores, labels, keep, K, ob, os_, ol, osel, _stream())
     return ob, os_, ol, osel
 
 
@@ -835,10 +771,8 @@ def nms_bev_batched(boxes, order, n_device, n_max, thresh, max_keep, ws_nms, map
     dev = boxes.device
     keep = torch.zeros((S, max(max_keep, 1)), dtype=torch.int32, device=dev)   # rows past keep_count stay valid ids
     kc = torch.empty((S,), dtype=torch.int32, device=dev)
-    check(lib().hvpr_nms_bev_batched_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
-                                         int(segments_per_table), _ptr(order, torch.int32), _ptr(n_device, torch.int32), S, int(n_max),
-                                         float(thresh), int(max_keep), 1 if map_through_order else 0, keep.data_ptr(), kc.data_ptr(),
-                                         ws_nms.data_ptr(), ws_nms.numel(), _stream()), "hvpr_nms_bev_batched_f32")
+    call("hvpr_nms_bev_batched_f32", boxes, boxes.shape[2], boxes.shape[1] * boxes.shape[2], int(segments_per_table), order, n_device, S,
+         int(n_max), float(thresh), int(max_keep), 1 if map_through_order else 0, keep, kc, ws_nms, ws_nms.numel(), _stream())
     return keep, kc
 
 
@@ -854,11 +788,8 @@ def gather_predictions_batched(boxes, scores, labels, keep, segments_per_table=1
     os_ = torch.empty((S, K), dtype=torch.float32, device=dev)
     ol = torch.empty((S, K), dtype=torch.int64, device=dev)
     osel = torch.empty((S, K), dtype=torch.int64, device=dev)
-    check(lib().hvpr_gather_predictions_batched_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
-                                                    int(segments_per_table), _ptr(scores, torch.float32, "scores"),
-                                                    _ptr(labels, torch.int32, "labels"), scores.shape[1], _ptr(keep, torch.int32, "keep"),
-                                                    S, K, ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), osel.data_ptr(), _stream()),
-          "hvpr_gather_predictions_batched_f32")
+    call("hvpr_gather_predictions_batched_f32", boxes, boxes.shape[2], boxes.shape[1] * boxes.shape[2], int(segments_per_table), scores,
+         labels, scores.shape[1], keep, S, K, ob, os_, ol, osel, _stream())
     return ob, os_, ol, osel
 
 
@@ -878,11 +809,8 @@ def gather_predictions_multiclass(boxes, scores, keep, keep_count, num_class):
     ol = torch.empty((B, nc * K), dtype=torch.int64, device=dev)
     osel = torch.empty((B, nc * K), dtype=torch.int64, device=dev)
     oc = torch.empty((B,), dtype=torch.int32, device=dev)
-    check(lib().hvpr_gather_predictions_multiclass_f32(_ptr(boxes, torch.float32, "boxes"), boxes.shape[2], boxes.shape[1] * boxes.shape[2],
-                                                       _ptr(scores, torch.float32, "scores"), scores.shape[1],
-                                                       _ptr(keep, torch.int32, "keep"), _ptr(keep_count, torch.int32, "keep_count"),
-                                                       B, nc, K, ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), osel.data_ptr(),
-                                                       oc.data_ptr(), _stream()), "hvpr_gather_predictions_multiclass_f32")
+    call("hvpr_gather_predictions_multiclass_f32", boxes, boxes.shape[2], boxes.shape[1] * boxes.shape[2], scores, scores.shape[1], keep,
+         keep_count, B, nc, K, ob, os_, ol, osel, oc, _stream())
     return ob, os_, ol, osel, oc
 
 
@@ -891,8 +819,7 @@ def boxes_pairwise(a, b, mode):
     a = a[:, :7].contiguous()
     b = b[:, :7].contiguous()
     out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    check(lib().hvpr_boxes_pairwise_f32(_ptr(a, torch.float32, "boxes_a"), a.shape[0], _ptr(b, torch.float32, "boxes_b"),
-                                        b.shape[0], int(mode), out.data_ptr(), _stream()), "hvpr_boxes_pairwise_f32")
+    call("hvpr_boxes_pairwise_f32", a, a.shape[0], b, b.shape[0], int(mode), out, _stream())
     return out
 
 
@@ -901,21 +828,15 @@ def boxes_pairwise_ragged(a, b, a_off, b_off, pair_off, n_pairs):
     """BEV overlap areas (mode 0) of F independent frames in one launch.  a (NA,7), b (NB,7) f32; a_off, b_off, pair_off (F+1,)
     int64 cuda -> (n_pairs,) f32, frame f at pair_off[f] as its (n_f, m_f) matrix, bit-equal to boxes_pairwise on that frame."""
     out = torch.empty((int(n_pairs),), dtype=torch.float32, device=pair_off.device)
-    check(lib().hvpr_boxes_pairwise_ragged_f32(_ptr(a, torch.float32, "boxes_a"), _ptr(b, torch.float32, "boxes_b"),
-                                               _ptr(a_off, torch.int64, "a_off"), _ptr(b_off, torch.int64, "b_off"),
-                                               _ptr(pair_off, torch.int64, "pair_off"), pair_off.numel() - 1, int(n_pairs),
-                                               out.data_ptr(), _stream()), "hvpr_boxes_pairwise_ragged_f32")
+    call("hvpr_boxes_pairwise_ragged_f32", a, b, a_off, b_off, pair_off, pair_off.numel() - 1, int(n_pairs), out, _stream())
     return out
 
 
 def kitti_overlaps(gt_rows, dt_rows, inter, gt_off, dt_off, pair_off, n_pairs, metric):
     """The host's frame_overlap for every frame: (n_pairs,) f64, frame f at pair_off[f] as its (nd_f, ng_f) matrix."""
     out = torch.empty((int(n_pairs),), dtype=torch.float64, device=pair_off.device)
-    check(lib().hvpr_kitti_overlaps_f64(_ptr(gt_rows, torch.float64, "gt_rows"), _ptr(dt_rows, torch.float64, "dt_rows"),
-                                        _ptr(inter, torch.float32, "inter"), _ptr(gt_off, torch.int64, "gt_off"),
-                                        _ptr(dt_off, torch.int64, "dt_off"), _ptr(pair_off, torch.int64, "pair_off"),
-                                        pair_off.numel() - 1, int(n_pairs), int(metric), out.data_ptr(), _stream()),
-          "hvpr_kitti_overlaps_f64")
+    call("hvpr_kitti_overlaps_f64", gt_rows, dt_rows, inter, gt_off, dt_off, pair_off, pair_off.numel() - 1, int(n_pairs), int(metric), out,
+         _stream())
     return out
 
 
@@ -935,20 +856,15 @@ def kitti_match(gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, p
     if thresholds is None:
         a, b = out if out is not None else (torch.empty((combos, NG), dtype=torch.float64, device=dev),
                                             torch.empty((C, 3), dtype=torch.int32, device=dev))
-        args = (None, None, 1, 0, _ptr(a, torch.float64, "tp_score"), _ptr(b, torch.int32, "n_valid"), None, None, None, 0)
+        args = (None, None, 1, 0, a, b, None, None, None, 0)
     else:
         T = thresholds.shape[1]
         a, b = out if out is not None else (torch.empty((combos, T, 3), dtype=torch.int32, device=dev),
                                             torch.empty((combos, T), dtype=torch.float64, device=dev))
         ws = torch.empty((lib().hvpr_kitti_match_workspace_bytes(F, C, K, T),), dtype=torch.uint8, device=dev)
-        args = (_ptr(thresholds, torch.float64, "thresholds"), _ptr(thresh_count, torch.int32, "thresh_count"), T, int(bool(compute_aos)),
-                None, None, _ptr(a, torch.int32, "counts"), _ptr(b, torch.float64, "sim"), ws.data_ptr(), ws.numel())
-    check(lib().hvpr_kitti_match_f64(_ptr(gt_rows, torch.float64, "gt_rows"), _ptr(gt_cls, torch.int32, "gt_cls"),
-                                     _ptr(gt_dontcare, torch.uint8, "gt_dontcare"), _ptr(dt_rows, torch.float64, "dt_rows"),
-                                     _ptr(dt_cls, torch.int32, "dt_cls"), _ptr(gt_off, torch.int64, "gt_off"),
-                                     _ptr(dt_off, torch.int64, "dt_off"), _ptr(pair_off, torch.int64, "pair_off"), F, NG,
-                                     _ptr(overlaps, torch.float64, "overlaps"), int(metric), 0 if thresholds is None else 1,
-                                     c_classes, C, c_mo, K, *args, _stream()), "hvpr_kitti_match_f64")
+        args = (thresholds, thresh_count, T, int(bool(compute_aos)), None, None, a, b, ws, ws.numel())
+    call("hvpr_kitti_match_f64", gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, pair_off, F, NG, overlaps, int(metric),
+         0 if thresholds is None else 1, c_classes, C, c_mo, K, *args, _stream())
     return a, b
 
 
@@ -967,9 +883,7 @@ def recall_record(pred_boxes, pred_count, gt_boxes, thresholds, counts=None, bes
     if tuple(counts.shape) != (B, 1 + T) or (best_iou is not None and tuple(best_iou.shape) != (B, G)):
         raise ValueError("recall_record: counts must be (B, 1 + T) and best_iou (B, G)")
     thr = (ctypes.c_float * max(T, 1))(*[float(t) for t in thresholds])
-    check(lib().hvpr_recall_record_f32(_ptr(pred_boxes, torch.float32, "pred_boxes"), _ptr(pred_count, torch.int32, "pred_count"), B, P,
-                                       _ptr(gt_boxes, torch.float32, "gt_boxes"), G, C, thr, T, _ptr(counts, torch.int32, "counts"),
-                                       _ptr(best_iou, torch.float32, "best_iou"), _stream()), "hvpr_recall_record_f32")
+    call("hvpr_recall_record_f32", pred_boxes, pred_count, B, P, gt_boxes, G, C, thr, T, counts, best_iou, _stream())
     return counts
 
 
@@ -989,14 +903,8 @@ def prediction_annos(pred_boxes, pred_scores, pred_labels, pred_count, calib, cl
         raise ValueError("prediction_annos: the tables must hold the same number of rows")
     n = len(class_of_label)
     cmap = (ctypes.c_int32 * max(n, 1))(*[int(c) for c in class_of_label])
-    check(lib().hvpr_prediction_annos_f32(_ptr(pred_boxes, torch.float32, "pred_boxes"), _ptr(pred_scores, torch.float32, "pred_scores"),
-                                          _ptr(pred_labels, torch.int64, "pred_labels"), _ptr(pred_count, torch.int32, "pred_count"),
-                                          B, P, _ptr(calib, torch.float32, "calib"), cmap, n, _ptr(row_base, torch.int64, "row_base"),
-                                          cap, int(frame_base), dt_off.numel() - 1, _ptr(dt_rows, torch.float64, "dt_rows"),
-                                          _ptr(dt_cls, torch.int32, "dt_cls"), _ptr(dt_label, torch.int32, "dt_label"),
-                                          _ptr(dt_box7, torch.float32, "dt_box7"), _ptr(boxes_lidar, torch.float32, "boxes_lidar"),
-                                          _ptr(dt_off, torch.int64, "dt_off"), _ptr(overflow, torch.int32, "overflow"), _stream()),
-          "hvpr_prediction_annos_f32")
+    call("hvpr_prediction_annos_f32", pred_boxes, pred_scores, pred_labels, pred_count, B, P, calib, cmap, n, row_base, cap,
+         int(frame_base), dt_off.numel() - 1, dt_rows, dt_cls, dt_label, dt_box7, boxes_lidar, dt_off, overflow, _stream())
 
 
 # ------------------------------------------------------------------------------------------------ f4: training augmentation
@@ -1010,8 +918,8 @@ def augment_collide(plan_host, plan_dev, words):
     device copy `plan_dev` was made from; the library checks it before it launches anything."""
     C = int(plan_host.numpy()[4])
     valid = torch.zeros((max(C, 1),), dtype=torch.int32, device=plan_dev.device)
-    check(lib().hvpr_augment_collide_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words), valid.data_ptr(),
-                                         _stream()), "hvpr_augment_collide_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_augment_collide_f32", plan_host.data_ptr(), plan_dev, int(words), valid, _stream())
     return valid[:C]
 
 
@@ -1024,10 +932,9 @@ def augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_o
         out = torch.empty((B, g_cap, 8), dtype=torch.float32, device=plan_dev.device)
     if count is None:
         count = torch.empty((B,), dtype=torch.int32, device=plan_dev.device)
-    check(lib().hvpr_augment_boxes_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words),
-                                       _ptr(valid, torch.int32, "valid"), rng6.ctypes.data, int(bool(remove_outside)), int(g_cap),
-                                       _ptr(out, torch.float32, "gt_boxes"), _ptr(count, torch.int32, "count"), _stream()),
-          "hvpr_augment_boxes_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_augment_boxes_f32", plan_host.data_ptr(), plan_dev, int(words), valid, rng6.ctypes.data, int(bool(remove_outside)),
+         int(g_cap), out, count, _stream())
     return out, count
 
 
@@ -1047,13 +954,9 @@ def augment_points(plan_host, plan_dev, words, valid, points, bank_points, bank_
     if out_off is None:
         out_off = torch.empty((B + 1,), dtype=torch.int32, device=points.device)
     ws = _workspace(None, lib().hvpr_augment_points_workspace_bytes(B, max_frame, C, n), points.device)
-    check(lib().hvpr_augment_points_f32(plan_host.data_ptr(), _ptr(plan_dev, torch.int32, "plan"), int(words),
-                                        _ptr(valid, torch.int32, "valid"), _ptr(points, torch.float32, "points"), n, F,
-                                        _ptr(bank_points, torch.float32, "bank points"), bank_points.shape[0],
-                                        _ptr(bank_boxes, torch.float32, "bank boxes"), bank_boxes.shape[0], bank_points.shape[1],
-                                        ex.ctypes.data, _ptr(out, torch.float32, "out_points"), out.shape[0],
-                                        _ptr(out_off, torch.int32, "out_off"), ws.data_ptr(), ws.numel(), _stream()),
-          "hvpr_augment_points_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_augment_points_f32", plan_host.data_ptr(), plan_dev, int(words), valid, points, n, F, bank_points, bank_points.shape[0],
+         bank_boxes, bank_boxes.shape[0], bank_points.shape[1], ex.ctypes.data, out, out.shape[0], out_off, ws, ws.numel(), _stream())
     return out, out_off
 
 
@@ -1091,11 +994,9 @@ def gt_database_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off,
     if obj_count is None:
         obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=points.device)[:n_obj]
     workspace = _gt_database_workspace(pt_off_host, n_obj, points.device, workspace)
-    check(lib().hvpr_gt_database_count_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
-                                           _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
-                                           box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"), n_obj,
-                                           _ptr(obj_count, torch.int32, "obj_count"), workspace.data_ptr(), workspace.numel(), _stream()),
-          "hvpr_gt_database_count_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_gt_database_count_f32", points, n, F, pt_off_host.data_ptr(), pt_off, B, boxes, box_off_host.data_ptr(), box_off, n_obj,
+         obj_count, workspace, workspace.numel(), _stream())
     return obj_count, workspace
 
 
@@ -1109,13 +1010,9 @@ def gt_database_extract(points, pt_off_host, pt_off, boxes, box_off_host, box_of
         raise ValueError("gt_database_extract: the arena must have the points' feature width")
     if obj_off is None:
         obj_off = torch.empty((n_obj + 1,), dtype=torch.int32, device=points.device)
-    check(lib().hvpr_gt_database_extract_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
-                                             _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
-                                             box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"),
-                                             _ptr(centres, torch.float64, "centres"), n_obj, obj_count_host.data_ptr(),
-                                             _ptr(obj_count, torch.int32, "obj_count"), _ptr(obj_off, torch.int32, "obj_off"),
-                                             _ptr(arena, torch.float32, "arena"), arena.shape[0], workspace.data_ptr(),
-                                             workspace.numel(), _stream()), "hvpr_gt_database_extract_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_gt_database_extract_f32", points, n, F, pt_off_host.data_ptr(), pt_off, B, boxes, box_off_host.data_ptr(), box_off, centres,
+         n_obj, obj_count_host.data_ptr(), obj_count, obj_off, arena, arena.shape[0], workspace, workspace.numel(), _stream())
     return obj_off
 
 
@@ -1145,12 +1042,9 @@ def kitti_infos_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off,
     off = pt_off_host.numpy()
     max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
     workspace = _workspace(workspace, lib().hvpr_kitti_infos_workspace_bytes(B, max_frame, n_obj), points.device)
-    check(lib().hvpr_kitti_infos_count_f32(_ptr(points, torch.float32, "points"), n, F, pt_off_host.data_ptr(),
-                                           _ptr(pt_off, torch.int32, "pt_off"), B, _ptr(boxes, torch.float32, "boxes"),
-                                           box_off_host.data_ptr(), _ptr(box_off, torch.int32, "box_off"), n_obj,
-                                           calib_host.data_ptr(), _ptr(calib, torch.float32, "calib"),
-                                           _ptr(obj_count, torch.int32, "obj_count"), _ptr(fov_count, torch.int32, "fov_count"),
-                                           workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_kitti_infos_count_f32")
+    # the *_host tensors live in host memory: raw addresses
+    call("hvpr_kitti_infos_count_f32", points, n, F, pt_off_host.data_ptr(), pt_off, B, boxes, box_off_host.data_ptr(), box_off, n_obj,
+         calib_host.data_ptr(), calib, obj_count, fov_count, workspace, workspace.numel(), _stream())
     return obj_count, fov_count, workspace
 
 
@@ -1174,8 +1068,7 @@ def _ragged_head(points, off, mask, calib, range_xy):
     rows, F = points.shape
     B = off.numel() - 1
     r = None if range_xy is None else np.ascontiguousarray(range_xy, np.float32).reshape(4)
-    head = (_ptr(points, torch.float32, "points"), rows, F, _ptr(off, torch.int32, "off"), B, int(mask),
-            _ptr(calib, torch.float32, "calib"), None if r is None else r.ctypes.data)
+    head = (points, rows, F, off, B, int(mask), calib, None if r is None else r.ctypes.data)
     return rows, F, B, head, r
 
 
@@ -1198,8 +1091,7 @@ def ragged_select_count(points, off, mask, calib=None, range_xy=None, new_off=No
     rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
     new_off = _offsets(new_off, B, points.device)
     workspace = _workspace(workspace, lib().hvpr_ragged_select_workspace_bytes(rows, B), points.device)
-    check(lib().hvpr_ragged_select_count_f32(*head, _ptr(new_off, torch.int32, "new_off"), workspace.data_ptr(),
-                                             workspace.numel(), _stream()), "hvpr_ragged_select_count_f32")
+    call("hvpr_ragged_select_count_f32", *head, new_off, workspace, workspace.numel(), _stream())
     return new_off, workspace
 
 
@@ -1210,10 +1102,8 @@ def ragged_select_write(points, off, mask, new_off, workspace, calib=None, range
     outside its frame, an output too small).  Without `out` the output is sized by the input rows: no read is needed."""
     rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
     out, flag = _out_and_flag(out, flag, rows, F + (1 if batch_column else 0), points.device)
-    check(lib().hvpr_ragged_select_write_f32(*head, _ptr(new_off, torch.int32, "new_off"), _ptr(inv_perm, torch.int32, "inv_perm"),
-                                             0 if inv_perm is None else inv_perm.numel(), int(bool(batch_column)),
-                                             _ptr(out, torch.float32, "out"), out.shape[0], _ptr(flag, torch.int32, "flag"),
-                                             workspace.data_ptr(), workspace.numel(), _stream()), "hvpr_ragged_select_write_f32")
+    call("hvpr_ragged_select_write_f32", *head, new_off, inv_perm, 0 if inv_perm is None else inv_perm.numel(), int(bool(batch_column)),
+         out, out.shape[0], flag, workspace, workspace.numel(), _stream())
     return out, flag
 
 
@@ -1223,9 +1113,7 @@ def ragged_sample_count(points, off, mask, calib=None, range_xy=None, near=40.0,
     rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
     new_off, near_off = _offsets(new_off, B, points.device), _offsets(near_off, B, points.device)
     workspace = _workspace(workspace, lib().hvpr_ragged_sample_workspace_bytes(rows, B), points.device)
-    check(lib().hvpr_ragged_sample_count_f32(*head, float(near), _ptr(new_off, torch.int32, "new_off"),
-                                             _ptr(near_off, torch.int32, "near_off"), workspace.data_ptr(), workspace.numel(),
-                                             _stream()), "hvpr_ragged_sample_count_f32")
+    call("hvpr_ragged_sample_count_f32", *head, float(near), new_off, near_off, workspace, workspace.numel(), _stream())
     return new_off, near_off, workspace
 
 
@@ -1239,12 +1127,8 @@ def ragged_sample_write(points, off, mask, new_off, near_off, mode, dest, num_po
     out, flag = _out_and_flag(out, flag, B * int(num_points), F + (1 if batch_column else 0), points.device)
     if mode.numel() != B or dest.dim() != 2 or dest.shape[1] != 2:
         raise ValueError("hvpr_amd: mode must be (B,) and dest (n, 2)")
-    check(lib().hvpr_ragged_sample_write_f32(*head, float(near), _ptr(new_off, torch.int32, "new_off"),
-                                             _ptr(near_off, torch.int32, "near_off"), _ptr(mode, torch.int32, "mode"),
-                                             _ptr(dest, torch.int32, "dest"), dest.shape[0], int(num_points),
-                                             int(bool(batch_column)), _ptr(out, torch.float32, "out"), out.shape[0],
-                                             _ptr(flag, torch.int32, "flag"), workspace.data_ptr(), workspace.numel(), _stream()),
-          "hvpr_ragged_sample_write_f32")
+    call("hvpr_ragged_sample_write_f32", *head, float(near), new_off, near_off, mode, dest, dest.shape[0], int(num_points),
+         int(bool(batch_column)), out, out.shape[0], flag, workspace, workspace.numel(), _stream())
     return out, flag
 
 
@@ -1300,13 +1184,9 @@ def render_bev(points, frame_offsets, point_cloud_range, pixel, palette, tables=
         for key, shape in (("count", (B,)), ("scores", (B, P)), ("labels", (B, P))):
             if t.get(key) is not None and tuple(t[key].shape) != shape:
                 raise ValueError(f"render_bev: {key} must be {shape}")
-        args += [_ptr(boxes, torch.float32, "boxes") if P else None, P, boxes.shape[2], _ptr(t.get("count"), torch.int32, "count"),
-                 _ptr(t.get("scores"), torch.float32, "scores"), float(t.get("thresh", 0.0)),
-                 _ptr(t.get("labels"), torch.int64, "labels"), int(t.get("ink", 1))]
+        args += [boxes if P else None, P, boxes.shape[2], t.get("count"), t.get("scores"), float(t.get("thresh", 0.0)), t.get("labels"),
+                 int(t.get("ink", 1))]
     workspace = _workspace(workspace, need, dev)
-    check(lib().hvpr_render_bev_u8(_ptr(points, torch.float32, "points") if n else None, n, stride, int(xyz_col),
-                                   _ptr(frame_offsets, torch.int32, "frame_offsets"), B, rng.ctypes.data, float(pixel), *args,
-                                   _ptr(palette, torch.uint8, "palette"), palette.shape[0], int(thickness), int(heading_sign),
-                                   _ptr(image, torch.uint8, "image"), _ptr(counts, torch.int32, "counts"), workspace.data_ptr(),
-                                   workspace.numel(), _stream()), "hvpr_render_bev_u8")
+    call("hvpr_render_bev_u8", points if n else None, n, stride, int(xyz_col), frame_offsets, B, rng.ctypes.data, float(pixel), *args,
+         palette, palette.shape[0], int(thickness), int(heading_sign), image, counts, workspace, workspace.numel(), _stream())
     return image, counts, workspace

@@ -31,13 +31,10 @@ class _RpnLosses(torch.autograd.Function):
         g_dir = None if dir_c is None else torch.empty_like(dir_c)
         ws = torch.empty(int(L.hvpr_rpn_losses_workspace_bytes(B, A)), dtype=torch.uint8, device=cls_c.device)
         cw = (ctypes.c_float * 7)(*[float(v) for v in weights["code_weights"]])
-        kernels.check(L.hvpr_rpn_losses_f32(
-            cls_c.data_ptr(), box_c.data_ptr(), None if dir_c is None else dir_c.data_ptr(), kernels._ptr(labels, torch.int32, "labels"),
-            kernels._ptr(reg_targets, torch.float32, "reg_targets"), None if dir_c is None else kernels._ptr(anchor_rot, torch.float32, "anchor_rot"),
-            kernels._ptr(pos_count, torch.int32, "positives_per_frame"), B, A, int(num_class), int(num_dir_bins if dir_c is not None else 0),
-            float(alpha), float(gamma), float(beta), ctypes.cast(cw, ctypes.c_void_p), float(weights["cls_weight"]), float(weights["loc_weight"]),
-            float(weights["dir_weight"]), float(dir_offset), out.data_ptr(), g_cls.data_ptr(), g_box.data_ptr(),
-            None if g_dir is None else g_dir.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_rpn_losses_f32")
+        kernels.call("hvpr_rpn_losses_f32", cls_c, box_c, dir_c, labels, reg_targets, None if dir_c is None else anchor_rot, pos_count, B,
+                     A, int(num_class), int(num_dir_bins if dir_c is not None else 0), float(alpha), float(gamma), float(beta),
+                     ctypes.cast(cw, ctypes.c_void_p), float(weights["cls_weight"]), float(weights["loc_weight"]),
+                     float(weights["dir_weight"]), float(dir_offset), out, g_cls, g_box, g_dir, ws, ws.numel(), kernels._stream())
         ctx.save_for_backward(g_cls, g_box, g_dir)
         ctx.shapes = (cls_preds.shape, box_preds.shape, None if dir_preds is None else dir_preds.shape)
         return out
@@ -76,8 +73,7 @@ class _MseLoss(torch.autograd.Function):
         out = torch.empty((), dtype=torch.float32, device=xc.device)
         gx = torch.empty_like(xc)
         ws = torch.empty(int(L.hvpr_mse_loss_workspace_bytes()), dtype=torch.uint8, device=xc.device)
-        kernels.check(L.hvpr_mse_loss_f32(xc.data_ptr(), tc.data_ptr(), xc.shape[0], xc.shape[1], float(weight), out.data_ptr(), gx.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_mse_loss_f32")
+        kernels.call("hvpr_mse_loss_f32", xc, tc, xc.shape[0], xc.shape[1], float(weight), out, gx, ws, ws.numel(), kernels._stream())
         ctx.save_for_backward(gx)
         return out
 

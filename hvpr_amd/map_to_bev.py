@@ -93,9 +93,7 @@ class _MemoryTrain(torch.autograd.Function):
         y = torch.empty_like(x)
         stats = torch.empty((R, 4), dtype=torch.float32, device=x.device)
         ws = _MemoryTrain._ws(n_items, x.device)
-        kernels.check(kernels.lib().hvpr_memory_train_fwd_f32(kernels._ptr(x, torch.float32, "x"), R, kernels._ptr(w, torch.float32, "memory.weight"),
-                                                              n_items, lambd, y.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                              kernels._stream()), "hvpr_memory_train_fwd_f32")
+        kernels.call("hvpr_memory_train_fwd_f32", x, R, w, n_items, lambd, y, stats, ws, ws.numel(), kernels._stream())
         ctx.save_for_backward(x, w, stats)
         ctx.lambd = lambd
         return y
@@ -108,9 +106,8 @@ class _MemoryTrain(torch.autograd.Function):
         dx, dw = torch.empty_like(x), torch.empty_like(w)
         scratch = torch.empty((2 * max(R, 1),), dtype=torch.float32, device=x.device)
         ws = _MemoryTrain._ws(n_items, x.device)
-        kernels.check(kernels.lib().hvpr_memory_train_bwd_f32(x.data_ptr(), kernels._ptr(dy, torch.float32, "dy"), R, w.data_ptr(), n_items, ctx.lambd,
-                                                              stats.data_ptr(), dx.data_ptr(), dw.data_ptr(), scratch.data_ptr(), ws.data_ptr(),
-                                                              ws.numel(), kernels._stream()), "hvpr_memory_train_bwd_f32")
+        kernels.call("hvpr_memory_train_bwd_f32", x, dy, R, w, n_items, ctx.lambd, stats, dx, dw, scratch, ws, ws.numel(),
+                     kernels._stream())
         return dx, dw, None
 
 
@@ -126,8 +123,7 @@ class _GatherRows(torch.autograd.Function):
         ctx.plan = plan if plan is not None else kernels.EdgePlan(idx, rows.shape[0])
         flat = ctx.plan.idx32().reshape(-1)
         out = torch.empty((flat.numel(), rows.shape[1]), dtype=torch.float32, device=rows.device)
-        kernels.check(kernels.lib().hvpr_gather_rows_f32(kernels._ptr(rows, torch.float32, "rows"), rows.shape[0], rows.shape[1], flat.data_ptr(),
-                                                         flat.numel(), out.data_ptr(), kernels._stream()), "hvpr_gather_rows_f32")
+        kernels.call("hvpr_gather_rows_f32", rows, rows.shape[0], rows.shape[1], flat, flat.numel(), out, kernels._stream())
         return out.view(*idx.shape, rows.shape[1])
 
     @staticmethod
@@ -196,8 +192,7 @@ class _ScatterCanvas(torch.autograd.Function):
         g = grad.permute(0, 2, 3, 1).contiguous()                     # NHWC (a view when grad is channels_last)
         cells, ch = g.shape[0] * g.shape[1] * g.shape[2], g.shape[3]
         out = torch.empty((rows.shape[0], ch), dtype=torch.float32, device=g.device)
-        kernels.check(kernels.lib().hvpr_gather_rows_f32(kernels._ptr(g, torch.float32, "grad canvas"), cells, ch, rows.data_ptr(), rows.shape[0],
-                                                         out.data_ptr(), kernels._stream()), "hvpr_gather_rows_f32")
+        kernels.call("hvpr_gather_rows_f32", g, cells, ch, rows, rows.shape[0], out, kernels._stream())
         return (out if ch == ctx.c else out[:, :ctx.c].contiguous()), None, None, None, None, None
 
 
@@ -308,9 +303,7 @@ class PointPillarScatter_Agg_Memory_1_scale(_ScatterBase):
         pf, pts = pillars.contiguous(), points.contiguous()
         packed = kernels.PackedBank(pts)                               # fp16 operand tiles + channel maxima of this sample's points
         idx = torch.empty((pf.shape[0], k), dtype=torch.int32, device=pf.device)
-        kernels.check(kernels.lib().hvpr_point_pillar_topk_f32(kernels._ptr(pf, torch.float32, "pillars"), pf.shape[0], packed.rows.data_ptr(),
-                                                               packed.data.data_ptr(), N, k, idx.data_ptr(), kernels._stream()),
-                      "hvpr_point_pillar_topk_f32")
+        kernels.call("hvpr_point_pillar_topk_f32", pf, pf.shape[0], packed.rows, packed.data, N, k, idx, kernels._stream())
         return idx.long()
 
     def _forward_train(self, batch_dict):

@@ -202,11 +202,8 @@ class _FlatOptimizer:
 
     def _call(self, name, *args):
         """ONE launch of the step kernel `name` over the flat buffers: (params, grads, *args, grad scale, stream)."""
-        from ._lib import check, lib
-        if not self.flat_p.is_cuda:
-            raise RuntimeError("hvpr_amd: %s steps on the GPU (the HIP path has no CPU fallback)" % type(self).__name__)
-        check(getattr(lib(), name)(self.flat_p.data_ptr(), self.flat_g.data_ptr(), *args,
-                                   None if self._scale is None else self._scale.data_ptr(), self._kernels._stream()), name)
+        from ._lib import call
+        call(name, self.flat_p, self.flat_g, *args, self._scale, self._kernels._stream())
         # the kernel writes the parameters through a raw pointer: torch's version counters do not see it, so whatever is derived from
         # the weights and cached by version (conv_train's packed Winograd filters) is told here
         from . import conv_train
@@ -237,7 +234,7 @@ class FusedAdamOneCycle(_FlatOptimizer):
 
     def _launch(self):
         """ONE launch of hvpr_fused_adam_truewd_f32 over the flat buffers."""
-        self._call("hvpr_fused_adam_truewd_f32", self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel, self._lr, self._mom,
+        self._call("hvpr_fused_adam_truewd_f32", self.exp_avg, self.exp_avg_sq, self.numel, self._lr, self._mom,
                    self.beta2, self.eps, self.wd, self.steps)
 
     def state_dict(self):
@@ -348,7 +345,7 @@ class FusedAdam(_FlatTorchOptimizer):
 
     def _launch(self):
         g = self.param_groups[0]
-        self._call("hvpr_fused_adam_l2_f32", self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.numel, g["lr"], g["betas"][0],
+        self._call("hvpr_fused_adam_l2_f32", self.exp_avg, self.exp_avg_sq, self.numel, g["lr"], g["betas"][0],
                    g["betas"][1], g["eps"], g["weight_decay"], self.steps)
 
 
@@ -371,7 +368,7 @@ class FusedSGD(_FlatTorchOptimizer):
         g = self.param_groups[0]
         if (g["momentum"] != 0) != (self.momentum_buffer is not None):
             raise ValueError("FusedSGD: momentum changed between zero and non-zero after construction")
-        self._call("hvpr_fused_sgd_f32", None if self.momentum_buffer is None else self.momentum_buffer.data_ptr(), self.numel, g["lr"],
+        self._call("hvpr_fused_sgd_f32", self.momentum_buffer, self.numel, g["lr"],
                    g["momentum"], g["weight_decay"])
 
 

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels
-from ._lib import check, lib
+from ._lib import call
 
 
 # ------------------------------------------------------------------------------------------------ index ops (HIP)
@@ -21,8 +21,7 @@ def furthest_point_sample(xyz, npoint):
     """xyz (B,N,3) f32 cuda -> idx (B,npoint) i32; first pick is index 0, ties -> lowest index."""
     B, N, _ = xyz.shape
     idx = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
-    check(lib().hvpr_furthest_point_sample_f32(kernels._ptr(xyz.contiguous(), torch.float32, "xyz"), B, N, int(npoint),
-                                               idx.data_ptr(), kernels._stream()), "hvpr_furthest_point_sample_f32")
+    call("hvpr_furthest_point_sample_f32", xyz.contiguous(), B, N, int(npoint), idx, kernels._stream())
     return idx
 
 
@@ -31,9 +30,7 @@ def ball_query(radius, nsample, xyz, new_xyz):
     B, N, _ = xyz.shape
     M = new_xyz.shape[1]
     idx = torch.empty((B, M, nsample), dtype=torch.int32, device=xyz.device)
-    check(lib().hvpr_ball_query_f32(kernels._ptr(xyz.contiguous(), torch.float32, "xyz"),
-                                    kernels._ptr(new_xyz.contiguous(), torch.float32, "new_xyz"), B, N, M, float(radius),
-                                    int(nsample), idx.data_ptr(), kernels._stream()), "hvpr_ball_query_f32")
+    call("hvpr_ball_query_f32", xyz.contiguous(), new_xyz.contiguous(), B, N, M, float(radius), int(nsample), idx, kernels._stream())
     return idx
 
 
@@ -43,9 +40,7 @@ def three_nn(unknown, known):
     m = known.shape[1]
     dist = torch.empty((B, n, 3), dtype=torch.float32, device=unknown.device)
     idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknown.device)
-    check(lib().hvpr_three_nn_f32(kernels._ptr(unknown.contiguous(), torch.float32, "unknown"),
-                                  kernels._ptr(known.contiguous(), torch.float32, "known"), B, n, m, dist.data_ptr(),
-                                  idx.data_ptr(), kernels._stream()), "hvpr_three_nn_f32")
+    call("hvpr_three_nn_f32", unknown.contiguous(), known.contiguous(), B, n, m, dist, idx, kernels._stream())
     return dist, idx
 
 
@@ -60,8 +55,7 @@ class _GroupPoints(torch.autograd.Function):
         B, C, N = features.shape
         _, np_, ns = idx.shape
         out = torch.empty((B, C, np_, ns), dtype=torch.float32, device=features.device)
-        check(lib().hvpr_group_points_f32(kernels._ptr(features, torch.float32, "features"), kernels._ptr(idx, torch.int32, "idx"),
-                                          B, C, N, np_, ns, out.data_ptr(), kernels._stream()), "hvpr_group_points_f32")
+        call("hvpr_group_points_f32", features, idx, B, C, N, np_, ns, out, kernels._stream())
         ctx.save_for_backward(idx)
         ctx.N = N
         return out
@@ -85,9 +79,7 @@ class _ThreeInterpolate(torch.autograd.Function):
         B, C, m = features.shape
         n = idx.shape[1]
         out = torch.empty((B, C, n), dtype=torch.float32, device=features.device)
-        check(lib().hvpr_three_interpolate_f32(kernels._ptr(features, torch.float32, "features"), kernels._ptr(idx, torch.int32, "idx"),
-                                               kernels._ptr(weight, torch.float32, "weight"), B, C, m, n, out.data_ptr(),
-                                               kernels._stream()), "hvpr_three_interpolate_f32")
+        call("hvpr_three_interpolate_f32", features, idx, weight, B, C, m, n, out, kernels._stream())
         ctx.save_for_backward(idx, weight)
         ctx.m = m
         return out
@@ -139,9 +131,7 @@ class _GroupRows(torch.autograd.Function):
         xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
         features = None if features is None else features.contiguous()
         out = torch.empty((B * np_ * ns, cpad), dtype=torch.float32, device=xyz.device)
-        check(lib().hvpr_group_rows_f32(kernels._ptr(xyz, torch.float32, "xyz"), kernels._ptr(features, torch.float32, "features"),
-                                        kernels._ptr(new_xyz, torch.float32, "new_xyz"), kernels._ptr(idx, torch.int32, "idx"), B, N, C, np_, ns,
-                                        cpad, out.data_ptr(), kernels._stream()), "hvpr_group_rows_f32")
+        call("hvpr_group_rows_f32", xyz, features, new_xyz, idx, B, N, C, np_, ns, cpad, out, kernels._stream())
         ctx.dims = (B, N, C)
         return out
 
@@ -166,8 +156,7 @@ class _MaxSamples(torch.autograd.Function):
         G = y.shape[0] // ns
         out = torch.empty((G, C), dtype=torch.float32, device=y.device)
         arg = torch.empty((G, C), dtype=torch.uint8, device=y.device)
-        check(lib().hvpr_max_samples_f32(kernels._ptr(y, torch.float32, "y"), G, ns, C, out.data_ptr(), arg.data_ptr(), kernels._stream()),
-              "hvpr_max_samples_f32")
+        call("hvpr_max_samples_f32", y, G, ns, C, out, arg, kernels._stream())
         ctx.save_for_backward(arg)
         ctx.ns = ns
         return out
@@ -178,8 +167,7 @@ class _MaxSamples(torch.autograd.Function):
         grad = grad.contiguous()
         G, C = grad.shape
         gy = torch.empty((G * ctx.ns, C), dtype=torch.float32, device=grad.device)
-        check(lib().hvpr_max_samples_grad_f32(kernels._ptr(grad, torch.float32, "grad_out"), arg.data_ptr(), G, ctx.ns, C, gy.data_ptr(),
-                                              kernels._stream()), "hvpr_max_samples_grad_f32")
+        call("hvpr_max_samples_grad_f32", grad, arg, G, ctx.ns, C, gy, kernels._stream())
         return gy, None
 
 
@@ -196,9 +184,7 @@ class _FpRows(torch.autograd.Function):
         n = idx.shape[1]
         C2 = 0 if skip is None else skip.shape[-1]
         out = torch.empty((B * n, cpad), dtype=torch.float32, device=known.device)
-        check(lib().hvpr_fp_rows_f32(kernels._ptr(known, torch.float32, "known"), kernels._ptr(idx, torch.int32, "idx"),
-                                     kernels._ptr(weight, torch.float32, "weight"), kernels._ptr(skip, torch.float32, "skip"), B, m, n, C1, C2, cpad,
-                                     out.data_ptr(), kernels._stream()), "hvpr_fp_rows_f32")
+        call("hvpr_fp_rows_f32", known, idx, weight, skip, B, m, n, C1, C2, cpad, out, kernels._stream())
         ctx.plan = plan if plan is not None else kernels.EdgePlan.batched(idx, m)
         ctx.save_for_backward(weight)
         ctx.dims = (B, m, n, C1, C2)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import kernels
-from ._lib import check, lib
+from ._lib import call, lib
 
 
 def _flags(points, mode, range_xy=None, near=40.0, fov=None):
@@ -27,10 +27,7 @@ def _flags(points, mode, range_xy=None, near=40.0, fov=None):
     h = w = 0
     if fov is not None:
         a, p, (h, w) = fov
-    check(lib().hvpr_point_flags_f32(kernels._ptr(points, torch.float32, "points"), n, points.shape[1], mode,
-                                     kernels._ptr(range_xy, torch.float32), float(near), kernels._ptr(a, torch.float32),
-                                     kernels._ptr(p, torch.float32), int(h), int(w), flags.data_ptr(), kernels._stream()),
-          "hvpr_point_flags_f32")
+    call("hvpr_point_flags_f32", points, n, points.shape[1], mode, range_xy, float(near), a, p, int(h), int(w), flags, kernels._stream())
     return flags
 
 
@@ -63,9 +60,7 @@ def compact_rows(rows, flags, count_only=False):
     out = torch.empty_like(rows)
     count = torch.zeros((1,), dtype=torch.int32, device=rows.device)
     ws = torch.empty((lib().hvpr_compact_workspace_bytes(n),), dtype=torch.uint8, device=rows.device)
-    check(lib().hvpr_compact_rows_f32(kernels._ptr(rows, torch.float32, "rows"), n, w, kernels._ptr(flags, torch.uint8, "flags"),
-                                      out.data_ptr(), n, count.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-          "hvpr_compact_rows_f32")
+    call("hvpr_compact_rows_f32", rows, n, w, flags, out, n, count, ws, ws.numel(), kernels._stream())
     return out, count
 
 
@@ -73,9 +68,7 @@ def gather_rows(rows, idx):
     rows = rows.contiguous()
     idx = idx.to(torch.int32).contiguous()
     out = torch.empty((idx.shape[0], rows.shape[1]), dtype=torch.float32, device=rows.device)
-    check(lib().hvpr_gather_rows_f32(kernels._ptr(rows, torch.float32, "rows"), rows.shape[0], rows.shape[1],
-                                     kernels._ptr(idx, torch.int32, "idx"), idx.shape[0], out.data_ptr(), kernels._stream()),
-          "hvpr_gather_rows_f32")
+    call("hvpr_gather_rows_f32", rows, rows.shape[0], rows.shape[1], idx, idx.shape[0], out, kernels._stream())
     return out
 
 

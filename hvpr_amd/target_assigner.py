@@ -60,9 +60,8 @@ class AxisAlignedTargetAssigner:
         ws = torch.empty(max(int(L.hvpr_assign_targets_workspace_bytes(B, G)), 256), dtype=torch.uint8, device=gt.device)
         off = 0
         for cname, (a, per_loc) in zip(self.anchor_class_names, sets):
-            kernels.check(L.hvpr_assign_targets_f32(a.data_ptr(), a.shape[0], gt.data_ptr(), B, G, self.class_names.index(cname),
-                                                    len(self.class_names), float(self.matched[cname]), float(self.unmatched[cname]),
-                                                    per_loc, stride, off, A, labels.data_ptr(), targets.data_ptr(), weights.data_ptr(),
-                                                    pos.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()), "hvpr_assign_targets_f32")
+            kernels.call("hvpr_assign_targets_f32", a, a.shape[0], gt, B, G, self.class_names.index(cname), len(self.class_names),
+                         float(self.matched[cname]), float(self.unmatched[cname]), per_loc, stride, off, A, labels, targets, weights, pos,
+                         ws, ws.numel(), kernels._stream())
             off += per_loc
         return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "positives_per_frame": pos}

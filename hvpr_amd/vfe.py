@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels
-from ._lib import check, lib
+from ._lib import call, lib
 from .folding import FoldCache, bn_scale_shift
 
 
@@ -116,12 +116,8 @@ class _PfnTrain(torch.autograd.Function):
         m0, v0 = torch.empty(16, device=dev), torch.empty(16, device=dev)
         m1, v1 = torch.empty(64, device=dev), torch.empty(64, device=dev)
         ws = _train_ws(dev)
-        check(lib().hvpr_pillar_vfe_train_fwd_f32(kernels._ptr(voxels, torch.float32, "voxels"), kernels._ptr(num, torch.int32, "voxel_num_points"),
-                                                  kernels._ptr(coords, torch.int32, "voxel_coords"), M, P,
-                                                  *[kernels._ptr(a, torch.float32, "PFN parameter") for a in args], float(eps),
-                                                  vs[0], vs[1], vs[2], off[0], off[1], off[2], out.data_ptr(), m0.data_ptr(), v0.data_ptr(),
-                                                  m1.data_ptr(), v1.data_ptr(), ws.data_ptr(), ws.numel(), kernels._stream()),
-              "hvpr_pillar_vfe_train_fwd_f32")
+        call("hvpr_pillar_vfe_train_fwd_f32", voxels, num, coords, M, P, *args, float(eps), vs[0], vs[1], vs[2], off[0],
+             off[1], off[2], out, m0, v0, m1, v1, ws, ws.numel(), kernels._stream())
         ctx.save_for_backward(voxels, num, coords, *args)
         ctx.geom = (float(eps), tuple(vs), tuple(off))
         ctx.mark_non_differentiable(m0, v0, m1, v1)
@@ -137,11 +133,8 @@ class _PfnTrain(torch.autograd.Function):
         M, P, _ = voxels.shape
         grads = [torch.empty_like(t) for t in (w0, g0, b0, w1, g1, b1)]
         ws = _train_ws(voxels.device)
-        check(lib().hvpr_pillar_vfe_bwd_f32(voxels.data_ptr(), num.data_ptr(), coords.data_ptr(), M, P, w0.data_ptr(), g0.data_ptr(),
-                                            b0.data_ptr(), w1.data_ptr(), g1.data_ptr(), b1.data_ptr(), eps, vs[0], vs[1], vs[2],
-                                            off[0], off[1], off[2], kernels._ptr(d_out.contiguous(), torch.float32, "d pillar_features"),
-                                            *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel(), kernels._stream()),
-              "hvpr_pillar_vfe_bwd_f32")
+        call("hvpr_pillar_vfe_bwd_f32", voxels, num, coords, M, P, w0, g0, b0, w1, g1, b1, eps, vs[0], vs[1], vs[2], off[0], off[1], off[2],
+             d_out.contiguous(), *grads, ws, ws.numel(), kernels._stream())
         return (None, None, None, *grads, None, None, None)
 
 

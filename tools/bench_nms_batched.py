@@ -9,7 +9,8 @@ median of --reps repetitions is reported with the 10th and 90th percentile.  One
 --loop-only times the loop leg alone and needs only the single entry point, so it also runs on a library from before the
 batched call: HVPR_AMD_LIB=/path/to/older/libhvpr_amd.so python tools/bench_nms_batched.py --loop-only.  (In a build that has
 the batched call the single call IS the batched kernel with one segment, so its own loop leg is not an independent baseline.)
-The library is bound here with ctypes, not through hvpr_amd._lib, which insists on every symbol of its own version."""
+The library is loaded here with ctypes, not through hvpr_amd._lib.lib(), which insists on every symbol of its own version; the
+prototypes come from hvpr_amd._lib.SIGNATURES (include/hvpr_amd.h)."""
 import argparse
 import ctypes
 import json
@@ -22,7 +23,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = torch.device("cuda", 0)
 N, THRESH = 4096, 0.1
-_P, _I, _F, _Z, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_longlong
+sys.path.insert(0, ROOT)
+from hvpr_amd._lib import SIGNATURES  # noqa: E402  (the header's prototypes; the library itself is loaded here)
 
 
 def car_boxes(rng, n, spread=40.0):
@@ -38,13 +40,11 @@ def car_boxes(rng, n, spread=40.0):
 def load(loop_only):
     path = os.environ.get("HVPR_AMD_LIB", os.path.join(ROOT, "hvpr_amd", "libhvpr_amd.so"))
     L = ctypes.CDLL(path)
-    L.hvpr_nms_workspace_bytes.restype, L.hvpr_nms_workspace_bytes.argtypes = _Z, [_I]
-    L.hvpr_nms_bev_f32.restype = _I
-    L.hvpr_nms_bev_f32.argtypes = [_P, _I, _P, _P, _I, _F, _I, _I, _P, _P, _P, _Z, _P]
+    names = ["hvpr_nms_workspace_bytes", "hvpr_nms_bev_f32"]
     if not loop_only:
-        L.hvpr_nms_bev_batched_workspace_bytes.restype, L.hvpr_nms_bev_batched_workspace_bytes.argtypes = _Z, [_I, _I]
-        L.hvpr_nms_bev_batched_f32.restype = _I
-        L.hvpr_nms_bev_batched_f32.argtypes = [_P, _I, _LL, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]
+        names += ["hvpr_nms_bev_batched_workspace_bytes", "hvpr_nms_bev_batched_f32"]
+    for name in names:
+        getattr(L, name).restype, getattr(L, name).argtypes = SIGNATURES[name]
     return L, path
 
 
