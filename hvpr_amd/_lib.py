@@ -1,4 +1,5 @@
-"""ctypes binding of libhvpr_amd.so, derived from the one declaration of its C-ABI: include/hvpr_amd.h.
+"""ctypes binding of libhvpr_amd.so, derived from the declaration of its C-ABI: include/hvpr_amd.h, and include/hvpr_amd_ext.h
+for the entry points added since that file was pinned (EXT_SIGNATURES / EXT_PARAMS: same parser, tables of their own).
 
 parse_header turns the header's prototypes into ctypes signatures (SIGNATURES) and, per parameter, the element type a
 tensor passed there must have; call() checks every tensor against that before it becomes a pointer.
@@ -14,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 8          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
 LIB_PATH = os.environ.get("HVPR_AMD_LIB", os.path.join(_HERE, "libhvpr_amd.so"))   # override: kernel experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd.h")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd_ext.h")
 
 _c = ctypes
 # hvpr_allreduce_fn: (double *buf, int n, hvpr_stream_t stream, void *ctx) -> int
@@ -69,6 +71,12 @@ PARAMS = {}              # name -> ((parameter name, kind), ...)
 SIGNATURES = {}          # name -> (restype, argtypes)
 for _name, (_res, _args, _params) in read_header(HEADER_PATH).items():
     SIGNATURES[_name], PARAMS[_name] = (_res, _args), _params
+EXT_PARAMS = {}          # the same two tables for include/hvpr_amd_ext.h
+EXT_SIGNATURES = {}
+for _name, (_res, _args, _params) in read_header(EXT_HEADER_PATH).items():
+    if _name in SIGNATURES:
+        raise HvprLibraryError(f"{_name} is declared in both {HEADER_PATH} and {EXT_HEADER_PATH}")
+    EXT_SIGNATURES[_name], EXT_PARAMS[_name] = (_res, _args), _params
 
 _lib = None
 _calls = {}              # name -> (bound function, ((index, name, kind) of each pointer), (index of each scalar)): made once in lib(),
@@ -86,12 +94,12 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise HvprLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
             if res is _c.c_int:
-                kinds = PARAMS[name]
+                kinds = PARAMS[name] if name in PARAMS else EXT_PARAMS[name]
                 _calls[name] = (fn, tuple((i, p, k) for i, (p, k) in enumerate(kinds) if k is not None),
                                 tuple(i for i, (_, k) in enumerate(kinds) if k is None))
         if L.hvpr_abi_version() != ABI_VERSION:      # a stale .so next to newer Python wrappers (buffer sizes, argument lists)
@@ -117,14 +125,14 @@ def call(name, *args):
     if _lib is None:
         lib()
     if name not in _calls:
-        raise HvprLibraryError(f"{name} is not a status-returning function of {HEADER_PATH}")
+        raise HvprLibraryError(f"{name} is not a status-returning function of {HEADER_PATH} or {EXT_HEADER_PATH}")
     fn, pointers, scalars = _calls[name]
     if len(args) != len(pointers) + len(scalars):
         raise TypeError(f"{name} takes {len(pointers) + len(scalars)} arguments, got {len(args)}")
     if not _PLAIN.issuperset(map(type, map(args.__getitem__, scalars))):      # one pass in C: this runs hundreds of times a step
         for i in scalars:
             if isinstance(args[i], torch.Tensor):
-                raise TypeError(f"{name}: {PARAMS[name][i][0]} is a scalar, got a tensor")
+                raise TypeError(f"{name}: {(PARAMS.get(name) or EXT_PARAMS[name])[i][0]} is a scalar, got a tensor")
     argv = list(args)
     for i, pname, kind in pointers:
         t = argv[i]

@@ -4,8 +4,12 @@ AxisAlignedTargetAssigner (pcdet/models/dense_heads/target_assigner/axis_aligned
 boxes3d_nearest_bev_iou (pcdet/utils/box_utils.py:252-323) and ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:13-43):
 hvpr_assign_targets_f32, two launches per anchor set for the whole batch, results written in the head's anchor order.  The
 reference trims padded ground-truth rows with a python loop over `.sum()` and takes its arg-maxes through `.cpu().numpy()`
-(:53-57,:148,:153): two host syncs per frame; here there is none.  POS_FRACTION < 0 (no sampling) and NORM_BY_NUM_EXAMPLES
-false, as hvpr.yaml:114-124 sets.  CPU tensors raise (torch form: tests/torch_forms.py)."""
+(:53-57,:148,:153): two host syncs per frame; here there is none.  MATCH_HEIGHT True (the rotated 3-D IoU in place of the
+nearest-axis one, :145) and NORM_BY_NUM_EXAMPLES True (:201-204) go through hvpr_assign_targets_ex_f32; with both false, as
+hvpr.yaml:114-124 sets them, the call is the one it always was.  The head's losses rebuild their weights from the labels
+(anchor_head_template.py:113-119, 190-192), so NORM_BY_NUM_EXAMPLES only changes the returned reg_weights, in the reference as
+here.  POS_FRACTION < 0 only: the reference's sampling branch (:173-184) is not built.  CPU tensors raise (torch form:
+tests/torch_forms.py)."""
 import torch
 
 from . import kernels
@@ -13,7 +17,6 @@ from . import kernels
 
 class AxisAlignedTargetAssigner:
     def __init__(self, model_cfg, class_names, box_coder, match_height=False):
-        assert not match_height, "hvpr path: MATCH_HEIGHT False (hvpr.yaml:124)"
         acfg = model_cfg.ANCHOR_GENERATOR_CONFIG
         tcfg = model_cfg.TARGET_ASSIGNER_CONFIG
         assert tcfg.POS_FRACTION < 0, "hvpr path: no fg/bg sampling (hvpr.yaml:122)"
@@ -22,7 +25,8 @@ class AxisAlignedTargetAssigner:
         self.anchor_class_names = [c["class_name"] for c in acfg]
         self.matched = {c["class_name"]: c["matched_threshold"] for c in acfg}
         self.unmatched = {c["class_name"]: c["unmatched_threshold"] for c in acfg}
-        self.norm_by_num_examples = tcfg.NORM_BY_NUM_EXAMPLES
+        self.norm_by_num_examples = bool(tcfg.NORM_BY_NUM_EXAMPLES)
+        self.match_height = bool(match_height)
         self._flat = None
 
     def _anchor_sets(self, all_anchors, device):
@@ -43,8 +47,6 @@ class AxisAlignedTargetAssigner:
         gt = gt_boxes_with_classes
         if not gt.is_cuda or gt.dtype != torch.float32:
             raise RuntimeError("hvpr_amd: the target assigner needs fp32 GPU tensors (the HIP path has no CPU fallback)")
-        if self.norm_by_num_examples:
-            raise ValueError("hvpr_amd: NORM_BY_NUM_EXAMPLES is not built (hvpr.yaml:123 sets it False)")
         gt = gt.contiguous()
         B, G = int(gt.shape[0]), int(gt.shape[1])
         sets = self._anchor_sets(all_anchors, gt.device)
@@ -57,11 +59,20 @@ class AxisAlignedTargetAssigner:
         weights = torch.empty((B, A), dtype=torch.float32, device=gt.device)
         pos = torch.zeros((B,), dtype=torch.int32, device=gt.device)
         L = kernels.lib()
-        ws = torch.empty(max(int(L.hvpr_assign_targets_workspace_bytes(B, G)), 256), dtype=torch.uint8, device=gt.device)
+        ex = self.match_height or self.norm_by_num_examples
+        if ex:
+            need = max(int(L.hvpr_assign_targets_ex_workspace_bytes(B, G, a.shape[0], int(self.match_height))) for a, _ in sets)
+        else:
+            need = int(L.hvpr_assign_targets_workspace_bytes(B, G))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=gt.device)
         off = 0
         for cname, (a, per_loc) in zip(self.anchor_class_names, sets):
-            kernels.call("hvpr_assign_targets_f32", a, a.shape[0], gt, B, G, self.class_names.index(cname), len(self.class_names),
-                         float(self.matched[cname]), float(self.unmatched[cname]), per_loc, stride, off, A, labels, targets, weights, pos,
-                         ws, ws.numel(), kernels._stream())
+            args = (a, a.shape[0], gt, B, G, self.class_names.index(cname), len(self.class_names), float(self.matched[cname]),
+                    float(self.unmatched[cname]), per_loc, stride, off, A, labels, targets, weights, pos)
+            if ex:
+                kernels.call("hvpr_assign_targets_ex_f32", *args, int(self.match_height), int(self.norm_by_num_examples), ws, ws.numel(),
+                             kernels._stream())
+            else:
+                kernels.call("hvpr_assign_targets_f32", *args, ws, ws.numel(), kernels._stream())
             off += per_loc
         return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "positives_per_frame": pos}

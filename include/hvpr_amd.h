@@ -597,6 +597,8 @@ int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, int dy_cstride, int dy_coff
  *     113-213; POS_FRACTION < 0: no sampling, NORM_BY_NUM_EXAMPLES false, MATCH_HEIGHT false, as hvpr.yaml:114-124) with
  *     boxes3d_nearest_bev_iou (pcdet/utils/box_utils.py:252-323) and ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:
  *     13-43).  Two launches, no host round trip (the reference: two `.cpu().numpy()` arg-maxes per frame, :148,:153).
+ *     MATCH_HEIGHT true (the rotated 3-D IoU as the matcher) and NORM_BY_NUM_EXAMPLES true: the same arguments plus two flags,
+ *     declared in hvpr_amd_ext.h.
  *     anchors        [n_anchors, 7] f32 of this set, order (z, y, x, size, rotation); per_loc of them per BEV location
  *     gt_boxes       [batch, n_gt, 8] f32 [x, y, z, dx, dy, dz, heading, class]; trailing rows whose signed sum over the 7 box
  *                    fields (class excluded) is exactly 0 are padding, row 0 is always kept (:53-57, the reference's own rule);
