@@ -129,12 +129,20 @@ class AnchorHeadTemplate(nn.Module):
         return x.to(device), y.to(device), torch.tensor(rows, dtype=torch.float32, device=device)
 
     def assign_targets(self, gt_boxes):
-        """anchor_head_template.py:89-99 -> AxisAlignedTargetAssigner (device, no host syncs)."""
+        """anchor_head_template.py:54-71, 89-99 -> AxisAlignedTargetAssigner or ATSSTargetAssigner (device, no host syncs).  The
+        reference's ATSS branch passes its constructor a `use_multihead` it does not take (TypeError); here it is built with the
+        evident intent: TOPK, the box coder, MATCH_HEIGHT."""
         if self.target_assigner is None:
-            from .target_assigner import AxisAlignedTargetAssigner
-            assert self.model_cfg.TARGET_ASSIGNER_CONFIG.NAME == "AxisAlignedTargetAssigner"
-            self.target_assigner = AxisAlignedTargetAssigner(self.model_cfg, self.class_names, self.box_coder,
-                                                             self.model_cfg.TARGET_ASSIGNER_CONFIG.MATCH_HEIGHT)
+            from .target_assigner import ATSSTargetAssigner, AxisAlignedTargetAssigner
+            tcfg = self.model_cfg.TARGET_ASSIGNER_CONFIG
+            if tcfg.NAME == "ATSS":
+                if "TOPK" not in tcfg:
+                    raise KeyError("TARGET_ASSIGNER_CONFIG.TOPK is missing: NAME: ATSS needs it")
+                self.target_assigner = ATSSTargetAssigner(tcfg.TOPK, self.box_coder, tcfg.MATCH_HEIGHT, n_classes=len(self.class_names))
+            elif tcfg.NAME == "AxisAlignedTargetAssigner":
+                self.target_assigner = AxisAlignedTargetAssigner(self.model_cfg, self.class_names, self.box_coder, tcfg.MATCH_HEIGHT)
+            else:
+                raise NotImplementedError(f"TARGET_ASSIGNER_CONFIG.NAME {tcfg.NAME!r}")
         return self.target_assigner.assign_targets([a.to(gt_boxes.device) for a in self.anchors], gt_boxes)
 
     def _anchor_rot(self, device):

@@ -19,7 +19,8 @@ PER_FILE = {"iou3d_nms.hip": ["-ffp-contract=off"], "voxelize.hip": ["-ffp-contr
             "preprocess.hip": ["-ffp-contract=off"], "assign_loss.hip": ["-ffp-contract=off"], "kitti_ap.hip": ["-ffp-contract=off"],
             "augment.hip": ["-ffp-contract=off"], "eval_tail.hip": ["-ffp-contract=off"],
             "gt_database.hip": ["-ffp-contract=off"], "collate.hip": ["-ffp-contract=off"],
-            "kitti_infos.hip": ["-ffp-contract=off"], "bev_render.hip": ["-ffp-contract=off"]}
+            "kitti_infos.hip": ["-ffp-contract=off"], "bev_render.hip": ["-ffp-contract=off"],
+            "assign_atss.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):
@@ -35,7 +36,7 @@ def build(force=False, verbose=False, timing=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("hvpr_amd.h", "hvpr_amd_ext.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("hvpr_amd.h", "hvpr_amd_ext.h", "hvpr_amd_atss.h")]
     objdir = os.path.join(HERE, "csrc", "_obj_timing" if timing else "_obj")
     out = os.path.join(HERE, "libhvpr_amd_timing.so") if timing else OUT
     extra = (["-DHVPR_EXP_TIMING"] + os.environ.get("HVPR_EXP_DEFINES", "").split()) if timing else []

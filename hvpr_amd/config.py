@@ -32,6 +32,10 @@ def _wrap(v):
     return v
 
 
+def _has_include(d):
+    return isinstance(d, dict) and ("_BASE_CONFIG_" in d or any(_has_include(v) for v in d.values()))
+
+
 def _merge(config, new, base_dir):
     if "_BASE_CONFIG_" in new:
         path = new["_BASE_CONFIG_"]
@@ -41,7 +45,11 @@ def _merge(config, new, base_dir):
                     path = os.path.join(root, path)
                     break
         with open(path) as f:
-            config.update(AttrDict(yaml.safe_load(f)))
+            base = yaml.safe_load(f)
+        if _has_include(base):
+            _merge(config, base, base_dir)        # a base that includes files itself, at any depth (a model yaml as the base of another one)
+        else:
+            config.update(AttrDict(base))
     for k, v in new.items():
         if not isinstance(v, dict):
             config[k] = v
@@ -105,6 +113,11 @@ CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfgs")
 
 def hvpr_car_cfg():
     return cfg_from_yaml_file(os.path.join(CFG_DIR, "kitti_models", "hvpr_car.yaml"))
+
+
+def hvpr_car_atss_cfg():
+    """hvpr_car.yaml with TARGET_ASSIGNER_CONFIG.NAME: ATSS, TOPK 9."""
+    return cfg_from_yaml_file(os.path.join(CFG_DIR, "kitti_models", "hvpr_car_atss.yaml"))
 
 
 def hvpr_3class_cfg():

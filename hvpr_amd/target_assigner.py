@@ -9,7 +9,7 @@ nearest-axis one, :145) and NORM_BY_NUM_EXAMPLES True (:201-204) go through hvpr
 hvpr.yaml:114-124 sets them, the call is the one it always was.  The head's losses rebuild their weights from the labels
 (anchor_head_template.py:113-119, 190-192), so NORM_BY_NUM_EXAMPLES only changes the returned reg_weights, in the reference as
 here.  POS_FRACTION < 0 only: the reference's sampling branch (:173-184) is not built.  CPU tensors raise (torch form:
-tests/torch_forms.py)."""
+tests/torch_forms.py).  NAME: ATSS selects ATSSTargetAssigner below (hvpr_assign_targets_atss_f32)."""
 import torch
 
 from . import kernels
@@ -74,5 +74,52 @@ class AxisAlignedTargetAssigner:
                              kernels._stream())
             else:
                 kernels.call("hvpr_assign_targets_f32", *args, ws, ws.numel(), kernels._stream())
+            off += per_loc
+        return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "positives_per_frame": pos}
+
+
+class ATSSTargetAssigner:
+    """TARGET_ASSIGNER_CONFIG.NAME: ATSS (pcdet/models/dense_heads/target_assigner/atss_target_assigner.py:7-141) through
+    hvpr_assign_targets_atss_f32: per anchor set seven launches for the whole batch, no (N, M) table and no host read
+    (the reference trims padded rows with a host read per row and builds dense IoU and distance tables per frame).  Every ground
+    truth of every class is matched against every anchor set, as in the reference; labels are int32 with no -1 band; several
+    anchor sets come back in the head's order, not set after set.  CPU tensors raise."""
+
+    _anchor_sets = AxisAlignedTargetAssigner._anchor_sets
+
+    def __init__(self, topk, box_coder, match_height=False, n_classes=None):
+        """n_classes: class values outside 0 .. n_classes label an anchor 0 (the head passes its class count; None: 0 .. 255)."""
+        if not 1 <= int(topk) <= 64:
+            raise ValueError(f"hvpr_amd: ATSS TOPK must be 1 .. 64, got {topk}")
+        self.topk = int(topk)
+        self.box_coder = box_coder
+        self.match_height = bool(match_height)
+        self.n_classes = 255 if n_classes is None else int(n_classes)
+        self._flat = None
+
+    def assign_targets(self, all_anchors, gt_boxes_with_classes):
+        """all_anchors: list of (nz,ny,nx,S,R,7); gt (B,G,8).  The four keys of AxisAlignedTargetAssigner.assign_targets."""
+        gt = gt_boxes_with_classes
+        if not gt.is_cuda or gt.dtype != torch.float32:
+            raise RuntimeError("hvpr_amd: the target assigner needs fp32 GPU tensors (the HIP path has no CPU fallback)")
+        gt = gt.contiguous()
+        B, G = int(gt.shape[0]), int(gt.shape[1])
+        sets = self._anchor_sets(all_anchors, gt.device)
+        stride = sum(p for _, p in sets)
+        n_loc = sets[0][0].shape[0] // sets[0][1]
+        assert all(a.shape[0] // p == n_loc for a, p in sets), "every anchor set covers the same feature map"
+        A = n_loc * stride
+        labels = torch.empty((B, A), dtype=torch.int32, device=gt.device)
+        targets = torch.empty((B, A, self.box_coder.code_size), dtype=torch.float32, device=gt.device)
+        weights = torch.empty((B, A), dtype=torch.float32, device=gt.device)
+        pos = torch.zeros((B,), dtype=torch.int32, device=gt.device)
+        L = kernels.lib()
+        need = max(int(L.hvpr_assign_targets_atss_workspace_bytes(B, G, a.shape[0], self.topk)) for a, _ in sets)
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=gt.device)
+        off = 0
+        rows = gt if G else gt.new_zeros((B, 1, 8))        # G == 0: an empty tensor has no address to pass; n_gt 0 reads no row
+        for a, per_loc in sets:
+            kernels.call("hvpr_assign_targets_atss_f32", a, a.shape[0], rows, B, G, self.n_classes, self.topk, int(self.match_height), per_loc,
+                         stride, off, A, labels, targets, weights, pos, ws, ws.numel(), kernels._stream())
             off += per_loc
         return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "positives_per_frame": pos}
