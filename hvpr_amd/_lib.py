@@ -1,6 +1,4 @@
-"""ctypes binding of libhvpr_amd.so, derived from the declaration of its C-ABI: include/hvpr_amd.h, and include/hvpr_amd_ext.h
-for the entry points added since that file was pinned (EXT_SIGNATURES / EXT_PARAMS: same parser, tables of their own), and the
-headers of MORE_HEADER_PATHS for those added since that one was pinned too (MORE_SIGNATURES / MORE_PARAMS).
+"""ctypes binding of libhvpr_amd.so, derived from the declaration of its C-ABI, include/hvpr_amd.h: one header, one pair of tables.
 
 parse_header turns the header's prototypes into ctypes signatures (SIGNATURES) and, per parameter, the element type a
 tensor passed there must have; call() checks every tensor against that before it becomes a pointer.
@@ -16,7 +14,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 8          # hvpr_abi_version() of the library these wrappers were written against (csrc/abi.hip)
 LIB_PATH = os.environ.get("HVPR_AMD_LIB", os.path.join(_HERE, "libhvpr_amd.so"))   # override: kernel experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd.h")
-EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd_ext.h")
 
 _c = ctypes
 # hvpr_allreduce_fn: (double *buf, int n, hvpr_stream_t stream, void *ctx) -> int
@@ -40,7 +37,7 @@ _PARAMETER = re.compile(r"(?:const )?([\w ]+?) ?(\*)? ?(\w+)")
 
 def parse_header(text):
     """name -> (restype, argtypes, params) for every `ret name(params);` of a C header; params is a tuple of (name, kind) with kind
-    a torch dtype for a typed pointer, ANY for a `void *` and None for a scalar."""
+    a torch dtype for a typed pointer, ANY for a `void *` and None for a scalar.  A name declared twice raises."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"^\s*(#|typedef\b|extern\b).*$", "", text, flags=re.M)
     table = {}
@@ -57,6 +54,8 @@ def parse_header(text):
                 raise HvprLibraryError(f"unknown parameter type `{p.strip()}` in `{proto}`")
             argtypes.append(_c.c_void_p if pm.group(2) else _SCALARS[pm.group(1)])
             kinds.append((pm.group(3), _ELEMENTS[pm.group(1)] if pm.group(2) else None))
+        if name in table:
+            raise HvprLibraryError(f"{name} is declared twice")
         table[name] = (_RETURNS[ret], argtypes, tuple(kinds))
     return table
 
@@ -72,37 +71,6 @@ PARAMS = {}              # name -> ((parameter name, kind), ...)
 SIGNATURES = {}          # name -> (restype, argtypes)
 for _name, (_res, _args, _params) in read_header(HEADER_PATH).items():
     SIGNATURES[_name], PARAMS[_name] = (_res, _args), _params
-EXT_PARAMS = {}          # the same two tables for include/hvpr_amd_ext.h
-EXT_SIGNATURES = {}
-for _name, (_res, _args, _params) in read_header(EXT_HEADER_PATH).items():
-    if _name in SIGNATURES:
-        raise HvprLibraryError(f"{_name} is declared in both {HEADER_PATH} and {EXT_HEADER_PATH}")
-    EXT_SIGNATURES[_name], EXT_PARAMS[_name] = (_res, _args), _params
-# further extension headers, each added after the one before it was pinned: the same parser, tables of their own
-MORE_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd_atss.h"),)
-
-
-def read_more_headers(paths, taken):
-    """(signatures, params) of the prototypes of `paths`; a name declared twice, in `taken` or among the paths, raises."""
-    signatures, params, seen = {}, {}, {n: "an earlier header" for n in taken}
-    for path in paths:
-        for name, (res, args, kinds) in read_header(path).items():
-            if name in seen:
-                raise HvprLibraryError(f"{name} is declared in both {seen[name]} and {path}")
-            seen[name] = path
-            signatures[name], params[name] = (res, args), kinds
-    return signatures, params
-
-
-MORE_SIGNATURES, MORE_PARAMS = read_more_headers(MORE_HEADER_PATHS, list(SIGNATURES) + list(EXT_SIGNATURES))
-
-
-def params_of(name):
-    for table in (PARAMS, EXT_PARAMS, MORE_PARAMS):
-        if name in table:
-            return table[name]
-    raise HvprLibraryError(f"{name} is declared in none of the headers")
-
 
 _lib = None
 _calls = {}              # name -> (bound function, ((index, name, kind) of each pointer), (index of each scalar)): made once in lib(),
@@ -120,12 +88,12 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise HvprLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(MORE_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
             if res is _c.c_int:
-                kinds = params_of(name)
+                kinds = PARAMS[name]
                 _calls[name] = (fn, tuple((i, p, k) for i, (p, k) in enumerate(kinds) if k is not None),
                                 tuple(i for i, (_, k) in enumerate(kinds) if k is None))
         if L.hvpr_abi_version() != ABI_VERSION:      # a stale .so next to newer Python wrappers (buffer sizes, argument lists)
@@ -151,14 +119,14 @@ def call(name, *args):
     if _lib is None:
         lib()
     if name not in _calls:
-        raise HvprLibraryError(f"{name} is not a status-returning function of {HEADER_PATH}, {EXT_HEADER_PATH} or a further header")
+        raise HvprLibraryError(f"{name} is not a status-returning function of {HEADER_PATH}")
     fn, pointers, scalars = _calls[name]
     if len(args) != len(pointers) + len(scalars):
         raise TypeError(f"{name} takes {len(pointers) + len(scalars)} arguments, got {len(args)}")
     if not _PLAIN.issuperset(map(type, map(args.__getitem__, scalars))):      # one pass in C: this runs hundreds of times a step
         for i in scalars:
             if isinstance(args[i], torch.Tensor):
-                raise TypeError(f"{name}: {params_of(name)[i][0]} is a scalar, got a tensor")
+                raise TypeError(f"{name}: {PARAMS[name][i][0]} is a scalar, got a tensor")
     argv = list(args)
     for i, pname, kind in pointers:
         t = argv[i]

@@ -16,7 +16,8 @@
 // hvpr_group_points_grad_f32, hvpr_three_interpolate_grad_f32 and hvpr_scatter_add_rows_f32 (float atomics) are gone: every scattering
 // gradient is hvpr_segment_sum_rows_f32 over a plan of its edges.  Later within 8 (no signature changed): hvpr_fused_adam_l2_f32 and
 // hvpr_fused_sgd_f32 are added (csrc/train_ops.hip); hvpr_assign_targets_ex_f32 and hvpr_assign_targets_ex_workspace_bytes are added
-// (csrc/assign_loss.hip; declared in include/hvpr_amd_ext.h: MATCH_HEIGHT and NORM_BY_NUM_EXAMPLES of the target assigner)
+// (csrc/assign_loss.hip: MATCH_HEIGHT and NORM_BY_NUM_EXAMPLES of the target assigner); hvpr_assign_targets_atss_f32 and
+// hvpr_assign_targets_atss_workspace_bytes are added (csrc/assign_atss.hip: NAME: ATSS)
 extern "C" int hvpr_abi_version(void) { return 8; }
 
 extern "C" const char *hvpr_status_string(int status) {

@@ -10,8 +10,8 @@
 //     candidates  per (ground truth, frame) one wave merges the chunk lists, clips its TOPK anchors against the ground truth, one per
 //                 lane, takes mean + unbiased std + 1e-6 (float64 sums in key order), applies the inside test (:95-111) and raises
 //                 the anchor's entry of a (batch, n_anchors) key plane: (IoU, lowest g) (:117-123)
-//     best        per ground truth the best IoU over ALL anchors and its lowest anchor index: the sweep of k_assign3d
-//                 (assign_loss.hip) — exact rejects on the whole table, the polygon clip on densely packed survivors only (:126)
+//     best        per ground truth the best IoU over ALL anchors and its lowest anchor index: sweep_pairs (assign_common.h), as
+//                 k_assign3d — exact rejects on the whole table, the polygon clip on densely packed survivors only (:126)
 //     forced      the best anchor of every ground truth takes it, the highest g wins (:127-128)
 //     write       label, box code, weight in the head's anchor order, every output row exactly once, and the positive count (:130-139)
 //   The IoU of a pair is iou_bev / iou_3d of iou_geom.h on boxes rebuilt by make_box from the two rows: the bits of
@@ -19,23 +19,14 @@
 //   (hvpr_amd/build.py) like every file that includes iou_geom.h.
 #include "common.h"
 #include "iou_geom.h"
-#include "../../include/hvpr_amd_atss.h"
+#include "assign_common.h"
 
 namespace {
 
-constexpr int kAtssMaxGt = 256;      // ground-truth rows per frame
 constexpr int kAtssMaxK = 64;        // TOPK: the sorted list is one key per lane of a wave
 constexpr int kAtssChunk = 2048;     // anchors a wave of the nearest kernel streams
-constexpr int kAtssRing = 128;       // pairs; a step adds at most 64 to fewer than 64
 constexpr unsigned long long kAtssNone = ~0ull;              // above every key
 constexpr unsigned long long kAtssForced = 1ull << 62;       // key-plane bit of a forced match; the low 8 bits are g
-
-// ord_of / of_ord of assign_loss.hip, repeated: that file stays byte for byte what it is, so nothing moves out of it into a header
-__device__ __forceinline__ unsigned atss_ord_of(float v) {   // order-preserving map to unsigned; 0 is below every float
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float atss_of_ord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
 // Lane i of the wave holds the i-th smallest key seen so far (kAtssNone where there is none yet); c, wave-uniform, goes to its place
 // and the 64th key falls off.  Keys are unique (they end in the anchor index).
@@ -66,20 +57,12 @@ __global__ void __launch_bounds__(256) k_atss_clear(unsigned long long *__restri
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0ull;
 }
 
-// :40-46 — trailing rows whose SIGNED fp32 sum over the 7 box fields is exactly 0 are cut, row 0 never is; n_rows = last + 1
+// :40-46 — n_rows = last_real_row + 1
 __global__ void __launch_bounds__(256) k_atss_trim(const float *__restrict__ gt, int G, int *__restrict__ n_rows) {
     __shared__ int s_last;
     const int b = blockIdx.x;
-    if (threadIdx.x == 0) s_last = 0;
-    __syncthreads();
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        const float *p = gt + ((size_t)b * G + g) * 8;
-        float sum = 0.f;
-        for (int j = 0; j < 7; ++j) sum += p[j];                      // left to right, as written
-        if (sum != 0.f) atomicMax(&s_last, g);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) n_rows[b] = s_last + 1;
+    const int last = last_real_row(gt + (size_t)b * G * 8, G, &s_last);
+    if (threadIdx.x == 0) n_rows[b] = last + 1;
 }
 
 // grid (chunk, g, frame), one wave: the k nearest anchors of the chunk, ascending, into partial[((frame * G + g) * chunks + chunk) * k ..]
@@ -157,39 +140,30 @@ __global__ void __launch_bounds__(64) k_atss_candidates(const float *__restrict_
     const float lx = pb[4], ly = pb[3];
     const bool inside = xl <= lx / 2 && xl >= -lx / 2 && yl <= ly / 2 && yl >= -ly / 2;
     if (v >= thresh && inside)                                        // the maximum is the highest IoU, then the lowest g (:123)
-        atomicMax(&plane[(size_t)b * A + a], ((unsigned long long)atss_ord_of(v) << 8) | (unsigned)(255 - g));
+        atomicMax(&plane[(size_t)b * A + a], ((unsigned long long)ord_of(v) << 8) | (unsigned)(255 - g));
 }
 
-// ---- the best anchor of every ground truth: the sweep of k_assign3d (assign_loss.hip) with no class mask ------------------------------
+// ---- the best anchor of every ground truth: sweep_pairs (assign_common.h) over every row that stays, no class mask ---------------------
 struct AtssLds {
     PolyStore ps;
-    __attribute__((aligned(16))) BoxLite gl[kAtssMaxGt];
-    unsigned long long gv[kAtssMaxGt];       // the workgroup's best (ord_of(iou), ~anchor) per ground truth; 0: no pair reached the clip
-    unsigned short ring[kAtssRing];          // (anchor in workgroup) << 8 | g
+    __attribute__((aligned(16))) BoxLite gl[kMaxGt];
+    unsigned long long gv[kMaxGt];           // the workgroup's best (ord_of(iou), ~anchor) per ground truth; 0: no pair reached the clip
+    unsigned short ring[kSweepRing];         // (anchor in workgroup) << 8 | g
 };
-
-// the circum-circle test of far_apart() (iou_geom.h) on the BoxLite records, as a3_far_apart of assign_loss.hip: rad is far_apart's
-// ra / rb, the same expression.  The sweep's "a rejected pair is IoU +0" holds only while this IS far_apart's test: change them together
-// (tests/test_gpu_atss.py compares the sweep's best anchors with hvpr_boxes_pairwise_f32's table, which runs far_apart itself).
-__device__ __forceinline__ bool atss_far_apart(const BoxLite &A, const BoxLite &B) {
-    const float ddx = A.x - B.x, ddy = A.y - B.y;
-    const float lim = A.rad + B.rad + 0.05f;
-    return ddx * ddx + ddy * ddy > lim * lim * 1.0001f;
-}
 
 template <int MATCH_HEIGHT>
 __device__ __forceinline__ void atss_clip_round(AtssLds &s, const float *__restrict__ anchors, int a0, const float *__restrict__ gt_frame,
                                                 int head, int n) {
     const int lane = threadIdx.x;
     if (lane < n) {
-        const int e = s.ring[(head + lane) & (kAtssRing - 1)];
+        const int e = s.ring[(head + lane) & (kSweepRing - 1)];
         const int al = e >> 8, g = e & 255;
         const float *pa = anchors + (size_t)(a0 + al) * 7, *pb = gt_frame + (size_t)g * 8;
         Box A, B;
         make_box(pa, A);
         make_box(pb, B);
         const float v = MATCH_HEIGHT ? iou_3d(pa, pb, A, B, s.ps, lane) : iou_bev(A, B, s.ps, lane);
-        atomicMax(&s.gv[g], ((unsigned long long)atss_ord_of(v) << 32) | (unsigned)~(unsigned)(a0 + al));
+        atomicMax(&s.gv[g], ((unsigned long long)ord_of(v) << 32) | (unsigned)~(unsigned)(a0 + al));
     }
 }
 
@@ -215,25 +189,8 @@ __global__ void __launch_bounds__(64) k_atss_best(const float *__restrict__ anch
         make_box(anchors + (size_t)a * 7, ab);
         al = lite_of(ab);
     }
-    int head = 0, tail = 0;
-    for (int g = 0; g < n; ++g) {
-        const BoxLite gl = s.gl[g];
-        const bool near = valid && !atss_far_apart(al, gl);
-        bool live = false;
-        if (__ballot(near)) live = near && !axes_separate(al, gl);
-        const unsigned long long m = __ballot(live);
-        if (!m) continue;                                                 // the workgroup is one wave: uniform
-        if (live) s.ring[(tail + __popcll(m & ((1ull << lane) - 1ull))) & (kAtssRing - 1)] = (unsigned short)((lane << 8) | g);
-        tail += __popcll(m);
-        __syncthreads();
-        if (tail - head >= 64) {
-            atss_clip_round<MATCH_HEIGHT>(s, anchors, a0, gt_frame, head, 64);
-            head += 64;
-            __syncthreads();                                              // the round's ring slots are free again
-        }
-    }
-    if (tail > head) atss_clip_round<MATCH_HEIGHT>(s, anchors, a0, gt_frame, head, tail - head);
-    __syncthreads();
+    sweep_pairs(s.ring, s.gl, n, al, valid, [](int) { return true; },
+                [&](int head, int cnt) { atss_clip_round<MATCH_HEIGHT>(s, anchors, a0, gt_frame, head, cnt); });
     for (int g = lane; g < n; g += 64)
         if (s.gv[g]) atomicMax(&gbest[(size_t)b * G + g], s.gv[g]);
 }
@@ -248,7 +205,7 @@ __global__ void __launch_bounds__(256) k_atss_forced(int A, int G, int batch, co
     if (g >= n_rows[b]) return;
     const unsigned long long key = gbest[t];
     unsigned a = 0u;
-    if (key && atss_of_ord((unsigned)(key >> 32)) > 0.f) a = ~(unsigned)key;
+    if (key && of_ord((unsigned)(key >> 32)) > 0.f) a = ~(unsigned)key;
     atomicMax(&plane[(size_t)b * A + a], kAtssForced | (unsigned)g);
 }
 
@@ -272,24 +229,11 @@ __global__ void __launch_bounds__(256) k_atss_write(const float *__restrict__ an
         }
         fg = lab > 0 ? 1 : 0;
         const float *an = anchors + (size_t)a * 7;
-        const long long idx = (long long)(a / per_loc) * loc_stride + loc_offset + (a % per_loc);
-        const size_t o = (size_t)b * a_total + idx;
+        const size_t o = (size_t)b * a_total + head_row(a, per_loc, loc_stride, loc_offset);
         labels[o] = lab;
         weights[o] = fg ? 1.f : 0.f;
         float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (fg) {                                                         // ResidualCoder.encode_torch, as k_assign_labels
-            const float *gp = gt + ((size_t)b * G + arg) * 8;
-            const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-            const float dxg = fmaxf(gp[3], 1e-5f), dyg = fmaxf(gp[4], 1e-5f), dzg = fmaxf(gp[5], 1e-5f);
-            const float diag = sqrtf(dxa * dxa + dya * dya);
-            t[0] = (gp[0] - an[0]) / diag;
-            t[1] = (gp[1] - an[1]) / diag;
-            t[2] = (gp[2] - an[2]) / dza;
-            t[3] = logf(dxg / dxa);
-            t[4] = logf(dyg / dya);
-            t[5] = logf(dzg / dza);
-            t[6] = gp[6] - an[6];
-        }
+        if (fg) encode_residual(an, gt + ((size_t)b * G + arg) * 8, t);
         for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
     }
     const unsigned long long m = __ballot(fg != 0);
@@ -297,8 +241,6 @@ __global__ void __launch_bounds__(256) k_atss_write(const float *__restrict__ an
     __syncthreads();
     if (threadIdx.x == 0 && s_pos) atomicAdd(&pos_count[b], s_pos);
 }
-
-size_t atss_round256(size_t n) { return (n + 255) / 256 * 256; }
 
 // workspace: [n_rows: batch ints][gbest: batch * n_gt keys][plane: batch * n_anchors keys] — cleared by k_atss_clear — then the chunk lists
 struct AtssLayout {
@@ -311,10 +253,10 @@ AtssLayout atss_layout(int batch, int n_gt, int n_anchors, int topk) {
     const size_t g = n_gt > 0 ? n_gt : 1;
     l.chunks = hvpr_cdiv(n_anchors, kAtssChunk);
     l.n_rows = 0;
-    l.gbest = atss_round256((size_t)batch * sizeof(int));
-    l.plane = l.gbest + atss_round256((size_t)batch * g * sizeof(unsigned long long));
-    l.partial = l.plane + atss_round256((size_t)batch * n_anchors * sizeof(unsigned long long));
-    l.total = l.partial + atss_round256((size_t)batch * g * l.chunks * topk * sizeof(unsigned long long));
+    l.gbest = round256((size_t)batch * sizeof(int));
+    l.plane = l.gbest + round256((size_t)batch * g * sizeof(unsigned long long));
+    l.partial = l.plane + round256((size_t)batch * n_anchors * sizeof(unsigned long long));
+    l.total = l.partial + round256((size_t)batch * g * l.chunks * topk * sizeof(unsigned long long));
     return l;
 }
 
@@ -329,12 +271,11 @@ extern "C" int hvpr_assign_targets_atss_f32(const float *anchors, int n_anchors,
                                             int topk, int match_height, int per_loc, int loc_stride, int loc_offset,
                                             long long anchors_total, int32_t *labels, float *reg_targets, float *reg_weights,
                                             int32_t *pos_count, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
-    if (!anchors || !gt_boxes || !labels || !reg_targets || !reg_weights || !pos_count || !workspace) return HVPR_ERR_INVALID_ARG;
-    if (n_anchors < 1 || batch < 1 || n_gt < 0 || n_classes < 1 || per_loc < 1 || n_anchors % per_loc != 0 || loc_stride < per_loc ||
-        loc_offset < 0 || loc_offset + per_loc > loc_stride || anchors_total < (long long)(n_anchors / per_loc) * loc_stride)
-        return HVPR_ERR_INVALID_ARG;
+    const int bad = assign_args_status(anchors, n_anchors, gt_boxes, batch, n_gt, 0, n_classes, per_loc, loc_stride, loc_offset,
+                                       anchors_total, labels, reg_targets, reg_weights, pos_count, workspace);
+    if (bad) return bad;
     if (topk < 1 || topk > n_anchors) return HVPR_ERR_INVALID_ARG;       // torch.topk raises there
-    if (topk > kAtssMaxK || n_gt > kAtssMaxGt || batch > 65535) return HVPR_ERR_UNSUPPORTED;
+    if (topk > kAtssMaxK || n_gt > kMaxGt || batch > 65535) return HVPR_ERR_UNSUPPORTED;
     const AtssLayout l = atss_layout(batch, n_gt, n_anchors, topk);
     if (workspace_bytes < l.total) return HVPR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;

@@ -15,18 +15,11 @@
 // labels are compared exactly with the reference's: tests/golden G8, G16; hvpr_amd/build.py compiles this file with -ffp-contract=off).
 #include "common.h"
 #include "iou_geom.h"     // make_box, the two exact rejects, iou_3d: the MATCH_HEIGHT matcher
-#include "../../include/hvpr_amd_ext.h"
+#include "assign_common.h"
 
 namespace {
 
-constexpr int kMaxGt = 256;         // ground-truth rows per frame (hvpr.yaml pads to ~50)
 constexpr float kPi = 3.14159265358979323846f;
-
-__device__ __forceinline__ unsigned ord_of(float v) {          // order-preserving map to unsigned; 0 is below every float
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float of_ord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
 // box_utils.py:297-308: heading snapped to the nearest axis -> (x1, y1, x2, y2)
 __device__ __forceinline__ float4 nearest_bev(const float *b) {
@@ -51,30 +44,19 @@ struct GtLds {
     int cls[kMaxGt];
 };
 
-// the frame's ground truths in LDS: nearest-axis boxes, areas, and `use` = inside the valid range (trailing rows whose SIGNED sum
-// over the 7 box fields, class column excluded, is exactly 0 are padding; row 0 always stays: `while cnt > 0 and cur_gt[cnt].sum()
-// == 0`, axis_aligned_target_assigner.py:53-57) and of this anchor set's class (:62-66; python's class_names[c - 1]: class 0 wraps
-// to the last class)
+// the frame's ground truths in LDS: nearest-axis boxes, areas, and `use` = inside the valid range (last_real_row) and of this anchor
+// set's class (of_class)
 __device__ __forceinline__ void load_gt(GtLds &s, const float *__restrict__ gt, int b, int G, int class_index, int n_classes, int *s_last) {
-    if (threadIdx.x == 0) *s_last = 0;
-    __syncthreads();
+    const float *gt_frame = gt + (size_t)b * G * 8;
+    const int last = last_real_row(gt_frame, G, s_last);
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        const float *p = gt + ((size_t)b * G + g) * 8;
-        float sum = 0.f;
-        for (int j = 0; j < 7; ++j) sum += p[j];                  // left to right, as written (contraction is off for this file)
-        if (sum != 0.f) atomicMax(s_last, g);
-    }
-    __syncthreads();
-    const int last = *s_last;
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        const float *p = gt + ((size_t)b * G + g) * 8;
+        const float *p = gt_frame + (size_t)g * 8;
         const float4 bx = nearest_bev(p);
         const int c = (int)p[7];
-        int m = (c - 1) % n_classes;
-        if (m < 0) m += n_classes;
+        const bool mine = of_class(c, class_index, n_classes);
         s.box[g] = bx;
         s.area[g] = (bx.z - bx.x) * (bx.w - bx.y);
-        s.use[g] = (g <= last && m == class_index) ? 1 : 0;
+        s.use[g] = (g <= last && mine) ? 1 : 0;
         s.cls[g] = c;
     }
     __syncthreads();
@@ -150,24 +132,11 @@ __global__ void __launch_bounds__(256) k_assign_labels(const float *__restrict__
         if (best < unmatched_thr) lab = 0;
         if (force) lab = cls_of;                                  // forced matches win over background (:186-190)
         fg = lab > 0 ? 1 : 0;
-        const long long idx = (long long)(a / rots) * loc_stride + loc_offset + (a % rots);
-        const size_t o = (size_t)b * a_total + idx;
+        const size_t o = (size_t)b * a_total + head_row(a, rots, loc_stride, loc_offset);
         labels[o] = lab;
         weights[o] = fg ? 1.f : 0.f;
         float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (fg) {                                                 // ResidualCoder.encode_torch, box_coder_utils.py:13-43
-            const float *gp = gt + ((size_t)b * G + arg) * 8;
-            const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-            const float dxg = fmaxf(gp[3], 1e-5f), dyg = fmaxf(gp[4], 1e-5f), dzg = fmaxf(gp[5], 1e-5f);
-            const float diag = sqrtf(dxa * dxa + dya * dya);
-            t[0] = (gp[0] - an[0]) / diag;
-            t[1] = (gp[1] - an[1]) / diag;
-            t[2] = (gp[2] - an[2]) / dza;
-            t[3] = logf(dxg / dxa);
-            t[4] = logf(dyg / dya);
-            t[5] = logf(dzg / dza);
-            t[6] = gp[6] - an[6];
-        }
+        if (fg) encode_residual(an, gt + ((size_t)b * G + arg) * 8, t);
         for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
     }
     const unsigned long long m = __ballot(fg != 0);
@@ -179,18 +148,14 @@ __global__ void __launch_bounds__(256) k_assign_labels(const float *__restrict__
 // ---- a12 with MATCH_HEIGHT: the rotated 3-D IoU of iou_geom.h as the matcher -----------------------------------------------------------
 // The table entry of (anchor, ground truth) is iou_3d(anchor row, gt row, make_box(anchor), make_box(gt)): the bits of
 // hvpr_boxes_pairwise_f32 mode 2.  Its polygon clip costs ~18 k cycles and is data dependent, the two exact rejects cost ~50 flops and
-// leave a few hundred anchors per ground truth, so a workgroup is ONE wave that sweeps its 64 anchors over the frame's ground truths
-// (BoxLite records in LDS) with the rejects only and packs the surviving (anchor, g) pairs by ballot and prefix count into an LDS
-// ring; whenever the ring holds 64 pairs the wave clips them, one pair per lane, both boxes rebuilt from their rows — so every
-// clipping round but a workgroup's last has 64 live lanes, and no wave clips for one live lane.  A rejected pair counts as IoU
-// exactly +0, what box_overlap would have returned.  LDS per workgroup: PolyStore 18 KB + 256 BoxLite 8 KB + 3.3 KB of tables and
-// the ring = 29.9 KB static, five workgroups per CU.
+// leave a few hundred anchors per ground truth, so a workgroup is ONE wave that runs sweep_pairs (assign_common.h) over the frame's
+// ground truths (BoxLite records in LDS) and clips the packed survivors, one pair per lane, both boxes rebuilt from their rows.  A
+// rejected pair counts as IoU exactly +0, what box_overlap would have returned.  LDS per workgroup: PolyStore 18 KB + 256 BoxLite 8 KB
+// + 3.3 KB of tables and the ring = 29.9 KB static, five workgroups per CU.
 // Two launches of the same sweep: pass 1 gives the per-ground-truth maximum (LDS atomicMax per workgroup, then one global atomicMax
 // per ground truth on the order-preserving bits), pass 2 clips the same pairs with the same function — the forced-match test
 // `iou == g2a_max` is an equality on identical bits — and keeps per anchor the 64-bit key (ord_of(iou), 255 - g), whose maximum is
 // the FIRST maximum over g in any arrival order.  Integer atomics only: labels, targets and counts are the same bits on every run.
-constexpr int kA3Ring = 128;         // pairs; a step adds at most 64 to fewer than 64
-
 struct A3Lds {
     PolyStore ps;
     __attribute__((aligned(16))) BoxLite gl[kMaxGt];
@@ -198,26 +163,19 @@ struct A3Lds {
     unsigned gv[kMaxGt];             // pass 1: ord_of of the workgroup's best iou per ground truth; pass 2: the bits of g2a_max
     int cls[kMaxGt];
     int force[64];
-    unsigned short ring[kA3Ring];    // (anchor in workgroup) << 8 | g
+    unsigned short ring[kSweepRing]; // (anchor in workgroup) << 8 | g
     unsigned char use[kMaxGt];
     int last;
 };
 
 __device__ __forceinline__ unsigned long long a3_key(float v, int g) { return ((unsigned long long)ord_of(v) << 32) | (unsigned)(255 - g); }
 
-// the circum-circle test of far_apart() on the BoxLite records (rad is far_apart's ra / rb, the same expression)
-__device__ __forceinline__ bool a3_far_apart(const BoxLite &A, const BoxLite &B) {
-    const float ddx = A.x - B.x, ddy = A.y - B.y;
-    const float lim = A.rad + B.rad + 0.05f;
-    return ddx * ddx + ddy * ddy > lim * lim * 1.0001f;
-}
-
 template <int PASS>
 __device__ __forceinline__ void a3_clip_round(A3Lds &s, const float *__restrict__ anchors, int a0, const float *__restrict__ gt_frame,
                                               int head, int n) {
     const int lane = threadIdx.x;
     if (lane < n) {
-        const int e = s.ring[(head + lane) & (kA3Ring - 1)];
+        const int e = s.ring[(head + lane) & (kSweepRing - 1)];
         const int al = e >> 8, g = e & 255;
         const float *pa = anchors + (size_t)(a0 + al) * 7, *pb = gt_frame + (size_t)g * 8;
         Box A, B;
@@ -243,25 +201,15 @@ __global__ void __launch_bounds__(64) k_assign3d(const float *__restrict__ ancho
     const int lane = threadIdx.x, b = blockIdx.y;
     const float *gt_frame = gt + (size_t)b * G * 8;
     // the frame's ground truths: the trim and the class mask of load_gt, BoxLite records for the rejects
-    if (lane == 0) s.last = 0;
-    __syncthreads();
-    for (int g = lane; g < G; g += 64) {
-        const float *p = gt_frame + (size_t)g * 8;
-        float sum = 0.f;
-        for (int j = 0; j < 7; ++j) sum += p[j];
-        if (sum != 0.f) atomicMax(&s.last, g);
-    }
-    __syncthreads();
-    const int last = s.last;
+    const int last = last_real_row(gt_frame, G, &s.last);
     for (int g = lane; g < G; g += 64) {
         const float *p = gt_frame + (size_t)g * 8;
         Box bx;
         make_box(p, bx);
         s.gl[g] = lite_of(bx);
         const int c = (int)p[7];
-        int m = (c - 1) % n_classes;
-        if (m < 0) m += n_classes;
-        const bool use = g <= last && m == class_index;
+        const bool mine = of_class(c, class_index, n_classes);
+        const bool use = g <= last && mine;
         s.use[g] = use ? 1 : 0;
         s.cls[g] = c;
         if (PASS == 1) {
@@ -283,38 +231,19 @@ __global__ void __launch_bounds__(64) k_assign3d(const float *__restrict__ ancho
         make_box(anchors + (size_t)a * 7, ab);
         al = lite_of(ab);
     }
-    // the best of what never reaches the clip: masked ground truths are valued -2 (they exist whenever G > 0 and none is in use),
-    // rejected pairs +0
-    unsigned long long best_key = 0ull;
-    int head = 0, tail = 0;
-    for (int g = 0; g < G; ++g) {
-        if (!s.use[g]) continue;                                          // workgroup-uniform
-        const BoxLite gl = s.gl[g];
-        const bool near = valid && !a3_far_apart(al, gl);
-        bool live = false;
-        if (__ballot(near)) live = near && !axes_separate(al, gl);       // most rows are out of every lane's reach
-        if (PASS == 2 && valid && !live && !best_key) best_key = a3_key(0.f, g);   // g ascends: the first rejected row is the largest key
-        const unsigned long long m = __ballot(live);
-        if (!m) continue;                                                 // the workgroup is one wave: uniform
-        if (live) s.ring[(tail + __popcll(m & ((1ull << lane) - 1ull))) & (kA3Ring - 1)] = (unsigned short)((lane << 8) | g);
-        tail += __popcll(m);
-        __syncthreads();
-        if (tail - head >= 64) {
-            a3_clip_round<PASS>(s, anchors, a0, gt_frame, head, 64);
-            head += 64;
-            __syncthreads();                                              // the round's ring slots are free again
-        }
-    }
-    if (tail > head) a3_clip_round<PASS>(s, anchors, a0, gt_frame, head, tail - head);
-    __syncthreads();
+    const Swept sw = sweep_pairs(s.ring, s.gl, G, al, valid, [&](int g) { return s.use[g] != 0; },
+                                 [&](int head, int n) { a3_clip_round<PASS>(s, anchors, a0, gt_frame, head, n); });
     if (PASS == 1) {
         for (int g = lane; g < G; g += 64)
             if (s.gv[g]) atomicMax(&g2a_ord[(size_t)b * G + g], s.gv[g]);
-        if (lane == 0 && tail) atomicAdd(n_clipped, (unsigned long long)tail);
+        if (lane == 0 && sw.clipped) atomicAdd(n_clipped, (unsigned long long)sw.clipped);
         return;
     }
     int fg = 0;
     if (valid) {
+        // the best of what never reaches the clip: masked ground truths are valued -2 (they exist whenever G > 0 and none is in use),
+        // rejected pairs +0 — g ascends, so the first rejected row is the largest such key
+        const unsigned long long best_key = sw.first_miss >= 0 ? a3_key(0.f, sw.first_miss) : 0ull;
         float best;
         int arg;
         const unsigned long long k = s.key[lane] > best_key ? s.key[lane] : best_key;
@@ -334,24 +263,11 @@ __global__ void __launch_bounds__(64) k_assign3d(const float *__restrict__ ancho
         if (force) lab = cls_of;                                          // forced matches win over background (:186-190)
         fg = lab > 0 ? 1 : 0;
         const float *an = anchors + (size_t)a * 7;
-        const long long idx = (long long)(a / rots) * loc_stride + loc_offset + (a % rots);
-        const size_t o = (size_t)b * a_total + idx;
+        const size_t o = (size_t)b * a_total + head_row(a, rots, loc_stride, loc_offset);
         labels[o] = lab;
         weights[o] = fg ? 1.f : 0.f;
         float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (fg) {                                                         // ResidualCoder.encode_torch, as k_assign_labels
-            const float *gp = gt_frame + (size_t)arg * 8;
-            const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-            const float dxg = fmaxf(gp[3], 1e-5f), dyg = fmaxf(gp[4], 1e-5f), dzg = fmaxf(gp[5], 1e-5f);
-            const float diag = sqrtf(dxa * dxa + dya * dya);
-            t[0] = (gp[0] - an[0]) / diag;
-            t[1] = (gp[1] - an[1]) / diag;
-            t[2] = (gp[2] - an[2]) / dza;
-            t[3] = logf(dxg / dxa);
-            t[4] = logf(dyg / dya);
-            t[5] = logf(dzg / dza);
-            t[6] = gp[6] - an[6];
-        }
+        if (fg) encode_residual(an, gt_frame + (size_t)arg * 8, t);
         for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
     }
     const unsigned long long m = __ballot(fg != 0);
@@ -367,7 +283,7 @@ __global__ void __launch_bounds__(256) k_assign_count_cared(int A, int rots, int
     __syncthreads();
     const int a = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     bool cared = false;
-    if (a < A) cared = labels[(size_t)b * a_total + (long long)(a / rots) * loc_stride + loc_offset + (a % rots)] >= 0;
+    if (a < A) cared = labels[(size_t)b * a_total + head_row(a, rots, loc_stride, loc_offset)] >= 0;
     const unsigned long long m = __ballot(cared);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_n, __popcll(m));
     __syncthreads();
@@ -379,7 +295,7 @@ __global__ void __launch_bounds__(256) k_assign_norm_weights(int A, int rots, in
                                                              float *__restrict__ weights) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (a >= A) return;
-    const size_t o = (size_t)b * a_total + (long long)(a / rots) * loc_stride + loc_offset + (a % rots);
+    const size_t o = (size_t)b * a_total + head_row(a, rots, loc_stride, loc_offset);
     const int n = n_cared[b];
     weights[o] = labels[o] > 0 ? 1.f / (float)(n > 1 ? n : 1) : 0.f;
 }
@@ -533,20 +449,21 @@ __global__ void __launch_bounds__(256) k_mse_sum(const float *__restrict__ parti
 
 }  // namespace
 
+// the per-ground-truth maxima, one word per (frame, row): the whole workspace of hvpr_assign_targets_f32
+static size_t g2a_bytes(int batch, int n_gt) { return round256((size_t)batch * (n_gt > 0 ? n_gt : 1) * sizeof(unsigned)); }
+
 extern "C" size_t hvpr_assign_targets_workspace_bytes(int batch, int n_gt) {
     if (batch < 1 || n_gt < 0) return 0;
-    return (((size_t)batch * (n_gt > 0 ? n_gt : 1) * sizeof(unsigned) + 255) / 256) * 256;
+    return g2a_bytes(batch, n_gt);
 }
 
 extern "C" int hvpr_assign_targets_f32(const float *anchors, int n_anchors, const float *gt_boxes, int batch, int n_gt, int class_index,
                                        int n_classes, float matched_thr, float unmatched_thr, int rots, int loc_stride, int loc_offset,
                                        long long anchors_total, int32_t *labels, float *reg_targets, float *reg_weights,
                                        int32_t *pos_count, void *workspace, size_t workspace_bytes, hvpr_stream_t stream) {
-    if (!anchors || !gt_boxes || !labels || !reg_targets || !reg_weights || !pos_count || !workspace) return HVPR_ERR_INVALID_ARG;
-    if (n_anchors < 1 || batch < 1 || n_gt < 0 || n_classes < 1 || class_index < 0 || class_index >= n_classes || rots < 1 ||
-        n_anchors % rots != 0 || loc_stride < rots || loc_offset < 0 || loc_offset + rots > loc_stride ||
-        anchors_total < (long long)(n_anchors / rots) * loc_stride)
-        return HVPR_ERR_INVALID_ARG;
+    const int bad = assign_args_status(anchors, n_anchors, gt_boxes, batch, n_gt, class_index, n_classes, rots, loc_stride, loc_offset,
+                                       anchors_total, labels, reg_targets, reg_weights, pos_count, workspace);
+    if (bad) return bad;
     if (n_gt > kMaxGt || batch > 65535) return HVPR_ERR_UNSUPPORTED;
     if (workspace_bytes < hvpr_assign_targets_workspace_bytes(batch, n_gt)) return HVPR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -564,12 +481,10 @@ extern "C" int hvpr_assign_targets_f32(const float *anchors, int n_anchors, cons
 // workspace of the _ex entry point: [0, 256) counters (the first 8 bytes: pairs that reached the clip, per pass), the per-ground-truth
 // maxima where hvpr_assign_targets_f32 keeps them — offset 0 there, so with match_height 0 the old entry point gets the tail — and
 // one int per frame for NORM_BY_NUM_EXAMPLES
-static size_t a3_g2a_bytes(int batch, int n_gt) { return (((size_t)batch * (n_gt > 0 ? n_gt : 1) * sizeof(unsigned) + 255) / 256) * 256; }
-
 extern "C" size_t hvpr_assign_targets_ex_workspace_bytes(int batch, int n_gt, int n_anchors, int match_height) {
     (void)match_height;                 // one layout for both matchers
     if (batch < 1 || n_gt < 0 || n_anchors < 1) return 0;
-    return 256 + a3_g2a_bytes(batch, n_gt) + (((size_t)batch * sizeof(int) + 255) / 256) * 256;
+    return 256 + g2a_bytes(batch, n_gt) + round256((size_t)batch * sizeof(int));
 }
 
 extern "C" int hvpr_assign_targets_ex_f32(const float *anchors, int n_anchors, const float *gt_boxes, int batch, int n_gt, int class_index,
@@ -581,11 +496,9 @@ extern "C" int hvpr_assign_targets_ex_f32(const float *anchors, int n_anchors, c
         return hvpr_assign_targets_f32(anchors, n_anchors, gt_boxes, batch, n_gt, class_index, n_classes, matched_thr, unmatched_thr, rots,
                                        loc_stride, loc_offset, anchors_total, labels, reg_targets, reg_weights, pos_count, workspace,
                                        workspace_bytes, stream);
-    if (!anchors || !gt_boxes || !labels || !reg_targets || !reg_weights || !pos_count || !workspace) return HVPR_ERR_INVALID_ARG;
-    if (n_anchors < 1 || batch < 1 || n_gt < 0 || n_classes < 1 || class_index < 0 || class_index >= n_classes || rots < 1 ||
-        n_anchors % rots != 0 || loc_stride < rots || loc_offset < 0 || loc_offset + rots > loc_stride ||
-        anchors_total < (long long)(n_anchors / rots) * loc_stride)
-        return HVPR_ERR_INVALID_ARG;
+    const int bad = assign_args_status(anchors, n_anchors, gt_boxes, batch, n_gt, class_index, n_classes, rots, loc_stride, loc_offset,
+                                       anchors_total, labels, reg_targets, reg_weights, pos_count, workspace);
+    if (bad) return bad;
     if (n_gt > kMaxGt || batch > 65535) return HVPR_ERR_UNSUPPORTED;
     const size_t need = hvpr_assign_targets_ex_workspace_bytes(batch, n_gt, n_anchors, match_height);
     if (workspace_bytes < need) return HVPR_ERR_WORKSPACE;
@@ -593,7 +506,7 @@ extern "C" int hvpr_assign_targets_ex_f32(const float *anchors, int n_anchors, c
     char *ws = (char *)workspace;
     unsigned long long *n_clipped = (unsigned long long *)ws;
     unsigned *g2a = (unsigned *)(ws + 256);
-    int *n_cared = (int *)(ws + 256 + a3_g2a_bytes(batch, n_gt));
+    int *n_cared = (int *)(ws + 256 + g2a_bytes(batch, n_gt));
     if (match_height) {
         if (hipMemsetAsync(ws, 0, need, s) != hipSuccess) return HVPR_ERR_LAUNCH;
         const dim3 grid(hvpr_cdiv(n_anchors, 64), batch);
@@ -609,7 +522,7 @@ extern "C" int hvpr_assign_targets_ex_f32(const float *anchors, int n_anchors, c
         if (hipMemsetAsync(n_cared, 0, (size_t)batch * sizeof(int), s) != hipSuccess) return HVPR_ERR_LAUNCH;
         const int rc = hvpr_assign_targets_f32(anchors, n_anchors, gt_boxes, batch, n_gt, class_index, n_classes, matched_thr, unmatched_thr,
                                                rots, loc_stride, loc_offset, anchors_total, labels, reg_targets, reg_weights, pos_count,
-                                               g2a, a3_g2a_bytes(batch, n_gt), stream);
+                                               g2a, g2a_bytes(batch, n_gt), stream);
         if (rc != HVPR_OK) return rc;
     }
     if (norm_by_num_examples) {

@@ -76,16 +76,27 @@ __device__ __forceinline__ bool far_apart(const Box &A, const Box &B) {
     return ddx * ddx + ddy * ddy > lim * lim * 1.0001f;
 }
 
-// Exact reject no. 2, separating axes: if the two rectangles are more than 5 cm apart along one of their four edge
-// normals, no edges cross and no corner passes the 1 cm in-box margin (that margin widens a box by at most 1.42 cm in any
-// direction), so the polygon routine would return exactly 0.  About half of the pairs the circum-circle test lets through
-// (cars: circum-radius 2.1 m around a 3.9 x 1.6 m box) end here, for ~35 flops instead of the ~18 k-cycle clip.
+// What the two rejects need of a box, for the sweeps that run them over a whole table (assign_common.h); rad is far_apart's ra / rb,
+// the same expression.
 struct BoxLite { float x, y, hx, hy, cs, sn, rad, pad; };   // 32 bytes: two broadcast 16-byte LDS reads
 
 __device__ __forceinline__ BoxLite lite_of(const Box &B) {
     return BoxLite{B.x, B.y, 0.5f * B.dx, 0.5f * B.dy, B.cs, B.sn, 0.5f * sqrtf(B.dx * B.dx + B.dy * B.dy), 0.f};
 }
 
+// far_apart on the BoxLite records.  A sweep counts a rejected pair as IoU +0, which holds only while this IS the test above: change
+// them together (tests/test_gpu_assign3d.py and tests/test_gpu_atss.py compare the sweeps with hvpr_boxes_pairwise_f32's table, which
+// runs the Box form).
+__device__ __forceinline__ bool far_apart(const BoxLite &A, const BoxLite &B) {
+    const float ddx = A.x - B.x, ddy = A.y - B.y;
+    const float lim = A.rad + B.rad + 0.05f;
+    return ddx * ddx + ddy * ddy > lim * lim * 1.0001f;
+}
+
+// Exact reject no. 2, separating axes: if the two rectangles are more than 5 cm apart along one of their four edge
+// normals, no edges cross and no corner passes the 1 cm in-box margin (that margin widens a box by at most 1.42 cm in any
+// direction), so the polygon routine would return exactly 0.  About half of the pairs the circum-circle test lets through
+// (cars: circum-radius 2.1 m around a 3.9 x 1.6 m box) end here, for ~35 flops instead of the ~18 k-cycle clip.
 // branch-free (all lanes run it on densely packed pairs)
 __device__ __forceinline__ bool axes_separate(const BoxLite &A, const BoxLite &B) {
     const float ddx = B.x - A.x, ddy = B.y - A.y;

@@ -598,7 +598,7 @@ int hvpr_bn_relu_bwd_apply_nhwc_f32(const float *dy, int dy_cstride, int dy_coff
  *     boxes3d_nearest_bev_iou (pcdet/utils/box_utils.py:252-323) and ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:
  *     13-43).  Two launches, no host round trip (the reference: two `.cpu().numpy()` arg-maxes per frame, :148,:153).
  *     MATCH_HEIGHT true (the rotated 3-D IoU as the matcher) and NORM_BY_NUM_EXAMPLES true: the same arguments plus two flags,
- *     declared in hvpr_amd_ext.h.
+ *     hvpr_assign_targets_ex_f32 below.
  *     anchors        [n_anchors, 7] f32 of this set, order (z, y, x, size, rotation); per_loc of them per BEV location
  *     gt_boxes       [batch, n_gt, 8] f32 [x, y, z, dx, dy, dz, heading, class]; trailing rows whose signed sum over the 7 box
  *                    fields (class excluded) is exactly 0 are padding, row 0 is always kept (:53-57, the reference's own rule);
@@ -614,6 +614,62 @@ int hvpr_assign_targets_f32(const float *anchors, int n_anchors, const float *gt
                             int n_classes, float matched_thr, float unmatched_thr, int per_loc, int loc_stride, int loc_offset,
                             long long anchors_total, int32_t *labels, float *reg_targets, float *reg_weights, int32_t *pos_count,
                             void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * a12 (training)  hvpr_assign_targets_f32 with the two remaining switches of TARGET_ASSIGNER_CONFIG
+ *     (pcdet/models/dense_heads/target_assigner/axis_aligned_target_assigner.py:113-213); every argument up to pos_count, the
+ *     trim of padded rows, the class mask, the first maximum over the ground truths, the forced matches, the box code and the
+ *     head's anchor order are those of hvpr_assign_targets_f32 above.
+ *     match_height          0: boxes3d_nearest_bev_iou, the kernels of hvpr_assign_targets_f32.  non-zero: MATCH_HEIGHT True (:145) —
+ *                           the table entry of (anchor, ground truth) is the rotated 3-D IoU, bit for bit what
+ *                           hvpr_boxes_pairwise_f32 mode 2 gives for the two rows (the reference's absent native
+ *                           boxes_iou3d_gpu).  Two launches: exact rejects on the whole table, the polygon clip on densely packed
+ *                           survivors only, once per pass with the same bits; integer atomics only, so labels, targets and
+ *                           counts are the same bits on every run.
+ *     norm_by_num_examples  non-zero: NORM_BY_NUM_EXAMPLES True (:201-204) — per frame and anchor set n = #(labels >= 0) and
+ *                           reg_weights = 1 / max(n, 1) (fp32) on the positives, two small launches more, no host read.  labels,
+ *                           reg_targets and pos_count do not depend on it.  The head's losses do not consume reg_weights: they
+ *                           rebuild their weights from the labels (anchor_head_template.py:113-119, 190-192), so this flag only
+ *                           changes the returned tensor, in the reference as here.
+ *     Both 0: the call IS hvpr_assign_targets_f32 (same launches, same bits).  n_gt <= 256; POS_FRACTION sampling is not built.
+ *     workspace: hvpr_assign_targets_ex_workspace_bytes(batch, n_gt, n_anchors, match_height) bytes (>= what
+ *     hvpr_assign_targets_f32 asks).  After a match_height call its first 8 bytes hold, as one uint64, the number of (anchor,
+ *     ground truth) pairs that passed the rejects and were clipped, counted once (pass 1), summed over the frames.
+ * ------------------------------------------------------------------------------------------- */
+size_t hvpr_assign_targets_ex_workspace_bytes(int batch, int n_gt, int n_anchors, int match_height);
+int hvpr_assign_targets_ex_f32(const float *anchors, int n_anchors, const float *gt_boxes, int batch, int n_gt, int class_index,
+                               int n_classes, float matched_thr, float unmatched_thr, int per_loc, int loc_stride, int loc_offset,
+                               long long anchors_total, int32_t *labels, float *reg_targets, float *reg_weights, int32_t *pos_count,
+                               int match_height, int norm_by_num_examples, void *workspace, size_t workspace_bytes,
+                               hvpr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * a12 (training)  TARGET_ASSIGNER_CONFIG.NAME: ATSS — ATSSTargetAssigner.assign_targets for one anchor set and a whole batch
+ *     (pcdet/models/dense_heads/target_assigner/atss_target_assigner.py:16-141), written in the head's anchor order like
+ *     hvpr_assign_targets_f32: output row (a / per_loc) * loc_stride + loc_offset + a % per_loc of anchors_total, each exactly once.
+ *     anchors (n_anchors, 7), gt_boxes (batch, n_gt, 8) with the class in column 7.  Per frame:
+ *       - trailing rows whose signed fp32 sum over the 7 box columns is 0 are cut, row 0 never is; NO class mask: every remaining
+ *         row of every class takes part;
+ *       - the IoU of (anchor, ground truth) is the bits of hvpr_boxes_pairwise_f32 mode 1 (match_height 0) or mode 2 (non-zero);
+ *       - candidates of a ground truth: the topk anchors with the smallest 64-bit key (bits of the fp32 squared centre distance
+ *         (dx*dx + dy*dy) + dz*dz, then anchor index); thresh = float(mean) + float(std) + 1e-6f of their IoUs, mean and unbiased
+ *         variance summed in float64 in key order (topk 1: NaN, nothing positive); a candidate is positive when iou >= thresh
+ *         and its centre passes the reference's inside test (rotate by -heading, x against dy / 2, y against dx / 2, closed);
+ *       - an anchor takes the ground truth of its highest positive IoU, the lowest row on ties;
+ *       - then every ground truth, in ascending order, takes the anchor of its maximum IoU over ALL anchors (lowest index on ties,
+ *         anchor 0 where the maximum is 0): no `> 0` guard, the highest row wins a shared anchor;
+ *       - labels = class of the matched row (int32; 0 for an unmatched anchor and for a class outside 0 .. n_classes), no -1 band;
+ *         reg_targets = ResidualCoder.encode_torch where label > 0, zero elsewhere; reg_weights = 1 / 0; pos_count[frame] +=
+ *         #(label > 0) (the caller zeroes it).
+ *     n_gt == 0 writes background.  Limits: 1 <= topk <= 64, topk <= n_anchors, n_gt <= 256.  Integer atomics only: the same bytes
+ *     on every run; capturable.  workspace: hvpr_assign_targets_atss_workspace_bytes(batch, n_gt, n_anchors, topk) bytes (0 for
+ *     arguments the call would refuse).
+ * ------------------------------------------------------------------------------------------- */
+size_t hvpr_assign_targets_atss_workspace_bytes(int batch, int n_gt, int n_anchors, int topk);
+int hvpr_assign_targets_atss_f32(const float *anchors, int n_anchors, const float *gt_boxes, int batch, int n_gt, int n_classes,
+                                 int topk, int match_height, int per_loc, int loc_stride, int loc_offset, long long anchors_total,
+                                 int32_t *labels, float *reg_targets, float *reg_weights, int32_t *pos_count,
+                                 void *workspace, size_t workspace_bytes, hvpr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a13 (training)  The three losses of ONE prediction stream of the anchor head AND their gradients w.r.t. the predictions, one launch

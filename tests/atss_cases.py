@@ -1,6 +1,6 @@
 """Shared bodies of the ATSS target-assigner checks (tests/test_atss_host.py on the CPU, tests/test_gpu_atss.py on the device): a
 numpy host form of hvpr_assign_targets_atss_f32 over ANY (anchors, ground truths) -> IoU table, the frames fixture G27 adds to
-G18's and G26's, and the fixture's reader.  The host form states the semantics of include/hvpr_amd_atss.h: the reference's
+G18's and G26's, and the fixture's reader.  The host form states the semantics include/hvpr_amd.h declares for it: the reference's
 ATSSTargetAssigner (atss_target_assigner.py:16-141) with the product's own tie rules — the 64-bit key (bits of the fp32 squared
 centre distance, then anchor index) for the TOPK nearest, the first maximum over the ground truths, the last write of the forced
 matches — and float64 statistics summed in key order.  G27 (tests/golden/make_golden_atss.py) pins it to the reference's own

@@ -1,7 +1,7 @@
 """CPU: the MATCH_HEIGHT / NORM_BY_NUM_EXAMPLES target assigner without a device.  The numpy host form of tests/assign3d_cases.py over
 the build's CPU oracle of the rotated 3-D IoU reproduces fixture G26 — the reference's own AxisAlignedTargetAssigner with
 MATCH_HEIGHT True (tests/golden/make_golden_assign3d.py) — so the GPU suite may use that form, fed with any IoU table, as its
-statement of the semantics; and the two new entry points are exported, bound from include/hvpr_amd_ext.h and sized on the host."""
+statement of the semantics; and the two _ex entry points are exported, bound from include/hvpr_amd.h and sized on the host."""
 import ctypes
 
 import numpy as np
@@ -56,18 +56,20 @@ def test_g26_cases_do_what_they_are_for(g26):
     assert A3.pairs_per_workgroup(sets[0][0], g26["car.stacked10.gt"], 0, 1).max() >= 8 * 64
 
 
-def test_new_entry_points_are_exported_and_bound_from_the_extension_header():
+def test_ex_entry_points_are_exported_and_bound_from_the_header():
     from hvpr_amd import _lib, build
     L = ctypes.CDLL(build.build())
-    assert sorted(_lib.EXT_SIGNATURES) == ["hvpr_assign_targets_ex_f32", "hvpr_assign_targets_ex_workspace_bytes"]
-    for n in _lib.EXT_SIGNATURES:
-        assert hasattr(L, n) and n not in _lib.SIGNATURES, n
-    old, new = _lib.SIGNATURES["hvpr_assign_targets_f32"], _lib.EXT_SIGNATURES["hvpr_assign_targets_ex_f32"]
+    ex = ["hvpr_assign_targets_ex_f32", "hvpr_assign_targets_ex_workspace_bytes"]
+    assert sorted(n for n in _lib.SIGNATURES if n.startswith("hvpr_assign_targets_ex_")) == ex
+    for n in ex:
+        assert hasattr(L, n) and n in _lib.PARAMS, n
+    old, new = _lib.SIGNATURES["hvpr_assign_targets_f32"], _lib.SIGNATURES["hvpr_assign_targets_ex_f32"]
     assert new[0] is ctypes.c_int and new[1] == old[1][:17] + [ctypes.c_int, ctypes.c_int] + old[1][17:]
-    names = [p for p, _ in _lib.EXT_PARAMS["hvpr_assign_targets_ex_f32"]]
+    names = [p for p, _ in _lib.PARAMS["hvpr_assign_targets_ex_f32"]]
     assert names[:17] == [p for p, _ in _lib.PARAMS["hvpr_assign_targets_f32"]][:17]
     assert names[17:] == ["match_height", "norm_by_num_examples", "workspace", "workspace_bytes", "stream"]
     assert _lib.lib().hvpr_abi_version() == 8
+    assert "hvpr_assign_targets_ex_f32" in _lib._calls
 
 
 def test_ex_workspace_query_needs_no_gpu():

@@ -1,7 +1,7 @@
 """CPU: the ATSS target assigner without a device.  The numpy host form of tests/atss_cases.py over the build's CPU oracle of the
 rotated BEV / 3-D IoU reproduces fixture G27 — the reference's own ATSSTargetAssigner (tests/golden/make_golden_atss.py) — on every
-pinned frame, so the GPU suite may use that form, fed with any IoU table, as its statement of the semantics; the two new entry
-points are exported, bound from include/hvpr_amd_atss.h and sized on the host; hvpr_car_atss.yaml loads and the head picks the class."""
+pinned frame, so the GPU suite may use that form, fed with any IoU table, as its statement of the semantics; the two ATSS entry
+points are exported, bound from include/hvpr_amd.h and sized on the host; hvpr_car_atss.yaml loads and the head picks the class."""
 import ctypes
 
 import numpy as np
@@ -112,36 +112,28 @@ def test_odd_topk_and_ties_run_through_the_host_form_alone(g27, topk):
         assert not bool(g27[f"car.k8.mh0.{name}.pinned"])
 
 
-def test_new_entry_points_are_exported_and_bound_from_their_own_header(tmp_path):
+def test_atss_entry_points_are_exported_and_bound_from_the_header():
+    """A name declared twice and a missing header: test_capi_symbols.py (the parser's duplicate case, test_missing_header_is_named)."""
     from hvpr_amd import _lib, build
     L = ctypes.CDLL(build.build())
-    assert sorted(_lib.MORE_SIGNATURES) == ["hvpr_assign_targets_atss_f32", "hvpr_assign_targets_atss_workspace_bytes"]
-    for n in _lib.MORE_SIGNATURES:
-        assert hasattr(L, n) and n not in _lib.SIGNATURES and n not in _lib.EXT_SIGNATURES, n
-    res, args = _lib.MORE_SIGNATURES["hvpr_assign_targets_atss_f32"]
+    atss = ["hvpr_assign_targets_atss_f32", "hvpr_assign_targets_atss_workspace_bytes"]
+    assert sorted(n for n in _lib.SIGNATURES if n.startswith("hvpr_assign_targets_atss_")) == atss
+    for n in atss:
+        assert hasattr(L, n) and n in _lib.PARAMS, n
+    res, args = _lib.SIGNATURES["hvpr_assign_targets_atss_f32"]
     i, ll, p, z = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_size_t
     assert res is i and args == [p, i, p, i, i, i, i, i, i, i, i, ll, p, p, p, p, p, z, p]
     import torch
-    kinds = _lib.MORE_PARAMS["hvpr_assign_targets_atss_f32"]
+    kinds = _lib.PARAMS["hvpr_assign_targets_atss_f32"]
     assert [n for n, _ in kinds] == ["anchors", "n_anchors", "gt_boxes", "batch", "n_gt", "n_classes", "topk", "match_height", "per_loc",
                                      "loc_stride", "loc_offset", "anchors_total", "labels", "reg_targets", "reg_weights", "pos_count",
                                      "workspace", "workspace_bytes", "stream"]
     assert {n: k for n, k in kinds if k is not None} == {"anchors": torch.float32, "gt_boxes": torch.float32, "labels": torch.int32,
                                                          "reg_targets": torch.float32, "reg_weights": torch.float32,
                                                          "pos_count": torch.int32, "workspace": _lib.ANY}
-    assert _lib.MORE_SIGNATURES["hvpr_assign_targets_atss_workspace_bytes"] == (z, [i, i, i, i])
-    assert _lib.params_of("hvpr_assign_targets_atss_f32") is kinds and _lib.params_of("hvpr_assign_targets_f32") is _lib.PARAMS["hvpr_assign_targets_f32"]
+    assert _lib.SIGNATURES["hvpr_assign_targets_atss_workspace_bytes"] == (z, [i, i, i, i])
     assert _lib.lib().hvpr_abi_version() == 8
     assert "hvpr_assign_targets_atss_f32" in _lib._calls
-    # a name declared twice raises: against the pinned headers, and between two further headers
-    dup = tmp_path / "dup.h"
-    dup.write_text("int hvpr_assign_targets_f32(const float *anchors, int n);\n")
-    with pytest.raises(_lib.HvprLibraryError, match="hvpr_assign_targets_f32 is declared in both"):
-        _lib.read_more_headers((str(dup),), list(_lib.SIGNATURES) + list(_lib.EXT_SIGNATURES))
-    with pytest.raises(_lib.HvprLibraryError, match="hvpr_assign_targets_atss_workspace_bytes is declared in both"):
-        _lib.read_more_headers(_lib.MORE_HEADER_PATHS + _lib.MORE_HEADER_PATHS, list(_lib.SIGNATURES))
-    with pytest.raises(_lib.HvprLibraryError, match="is missing"):
-        _lib.read_more_headers((str(tmp_path / "absent.h"),), [])
 
 
 def test_atss_workspace_query_needs_no_gpu():

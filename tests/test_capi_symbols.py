@@ -94,7 +94,7 @@ def test_parameter_kinds_come_from_the_header():
     assert kinds["n_frames"] is None and kinds["n_gt_total"] is None and kinds["stream"] is None   # scalars (the frame count F)
     assert dict(_lib.PARAMS["hvpr_max_samples_f32"])["G"] is None
     every = [k for ps in _lib.PARAMS.values() for _, k in ps if k is not None]
-    assert len(every) == 555 and {k for k in every} == {torch.float32, torch.int32, torch.int64, torch.float64, torch.uint8, _lib.ANY}
+    assert len(every) == 569 and {k for k in every} == {torch.float32, torch.int32, torch.int64, torch.float64, torch.uint8, _lib.ANY}
 
 
 def test_parser_on_synthetic_headers():
@@ -121,6 +121,9 @@ def test_parser_on_synthetic_headers():
                 "unsigned f(int n);", "int f(int);"):
         with pytest.raises(_lib.HvprLibraryError, match=r"f\("):
             _lib.parse_header("size_t ok(int n);\n" + bad)
+    # one name declared twice, whatever the two declarations say, raises and is named
+    with pytest.raises(_lib.HvprLibraryError, match="again is declared twice"):
+        _lib.parse_header("size_t ok(int n);\nint again(const float *x, int n);\nint other(int n);\nsize_t again(void);\n")
 
 
 def test_missing_header_is_named(tmp_path):
