@@ -14,24 +14,13 @@
 // lanes 0-31 supply the 8 channels of the even chunk, lanes 32-63 those of the odd chunk.
 #include <type_traits>
 
-#include "common.h"
+#include "conv_common.h"      // KC, lds_dma16, conv_walk_blocks
+#include "conv_walk.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int KC = 8;
 
-__device__ __forceinline__ void lds_dma16(const void *sbase_uniform, unsigned voff_bytes, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff_bytes), "s"(sbase_uniform), "s"(lds_dst_uniform)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr_of(const void *p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void *)p;
-}
 __device__ __forceinline__ bf16x8 as_bf(float4 v) {
     union { float4 f; bf16x8 b; } u;
     u.f = v;
@@ -144,9 +133,8 @@ __global__ void __launch_bounds__(64 * NWAVES) k_conv3(Conv3Args a) {
     const int total_walk = ((n_pt + 7) / 8) * 8 * a.n_ct;
     const int n_chunks = a.Cin / KSTAGE;
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
-    const int xcd = it & 7, j = it >> 3;
-    const int ct = j % a.n_ct;
-    int pt = (j / a.n_ct) * 8 + xcd;
+    int ct;
+    int pt = conv_walk_step(it, a.n_ct, ct);
     if (pt >= n_pt) continue;
     const int tx = pt % a.tiles_x; pt /= a.tiles_x;
     const int ty = pt % a.tiles_y;
@@ -346,20 +334,9 @@ int launch3(Conv3Args a, hipStream_t s) {
     constexpr int PPAD = (PH * PITCH + 63) / 64 * 64;
     constexpr int NT = 64 * NWAVES;
     constexpr int NLD_P = ((ONE ? 4 : 1) * 2 * NPL * PPAD + NT - 1) / NT, NLD_W = ((ONE ? 4 : (ROWS ? 3 : 9)) * 2 * NPL * BN + NT - 1) / NT;
-    const size_t lds = (size_t)2 * (NLD_P + NLD_W) * NT * 16;
-    const long long tiles = (long long)a.N * a.tiles_x * a.tiles_y * a.n_ct;
-    static int resident = 0;
-    if (resident == 0) {
-        if (hipFuncSetAttribute((const void *)k_conv3<TH, TW, BN, S, WGM, NPL, NWAVES, ROWS, ONE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return HVPR_ERR_LAUNCH;
-        int per_cu = 0, dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv3<TH, TW, BN, S, WGM, NPL, NWAVES, ROWS, ONE>, NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        resident = per_cu * cus;
-    }
-    long long blocks = tiles < resident ? (tiles + 7) / 8 * 8 : resident;
-    if (blocks > resident && resident >= 8) blocks = resident / 8 * 8;
+    constexpr int lds = 2 * (NLD_P + NLD_W) * NT * 16;
+    const int blocks = conv_walk_blocks<k_conv3<TH, TW, BN, S, WGM, NPL, NWAVES, ROWS, ONE>>(NT, lds, (long long)a.N * a.tiles_x * a.tiles_y * a.n_ct);
+    if (blocks < 0) return HVPR_ERR_LAUNCH;
     hipLaunchKernelGGL((k_conv3<TH, TW, BN, S, WGM, NPL, NWAVES, ROWS, ONE>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
     return HVPR_OK;
 }

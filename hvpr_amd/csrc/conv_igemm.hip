@@ -17,32 +17,10 @@
 // permutation as long as A and B agree.
 #include <type_traits>
 
-#include "common.h"
+#include "conv_common.h"      // KC, lds_dma16, tab_load, conv_walk_blocks, HVPR_IF_TIMING
+#include "conv_walk.h"        // the walk's step decode and the table entry
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int KC = 8;   // input channels per K chunk
-
-// One LDS-DMA piece: 16 B per lane, global (per-lane address) -> LDS (M0 = wave-uniform base, + lane * 16).
-// Issued through inline asm on purpose: hipcc would otherwise put s_waitcnt vmcnt(0) in front of the next ds_read (it
-// must assume the DMA write aliases it), which serialises the stream behind the multiply.  The wait is placed by hand
-// in front of the per-chunk barrier instead (cdna_hip_programming.md §5.7 recipe).
-// Address form: SGPR base + 32-bit VGPR byte offset.  Everything that changes from chunk to chunk lives in the SGPR base
-// and in M0, so the steady-state loop issues NO vector-ALU instruction: measured on this chip, v_mfma_f32_32x32x2_f32
-// runs on the f32 vector lanes (it is rated at the vector FMA rate), and a co-resident wave that needs VALU slots for
-// address arithmetic is starved for as long as its neighbour multiplies.
-__device__ __forceinline__ void lds_dma16(const void *sbase_uniform, unsigned voff_bytes, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff_bytes), "s"(sbase_uniform), "s"(lds_dst_uniform)
-                 : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const void *p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void *)p;
-}
 
 struct ConvArgs {
     const float *in;      // [N, H, W, Cin]
@@ -60,22 +38,8 @@ struct ConvArgs {
     int up;               // 1, or the ConvTranspose stride s (kernel == stride): column = (ky*s+kx)*cout_real + co
     int cout_real;        // channels per sub-pixel when up > 1 (== cout_gemm when up == 1)
     int tiles_x, tiles_y, n_ct;
-    const unsigned long long *tab;   // one entry per walk step (k_conv_tab) or null: the walk is decoded in the kernel
+    const ConvTabEntry *tab;   // one entry per walk step (k_conv_tab) or null: the walk is decoded in the kernel
 };
-
-// Per-item work outside the K loop, each a compile-time switch of the forward instantiations (UP2 keeps the plain code), as in
-// conv_wino.hip:  OPT_TAB  the items come from a table (the instantiation a launch with a table runs);  OPT_PEEL  chunk 0 is peeled and its first MFMA per
-// accumulator block takes C = 0, no clear.
-enum { OPT_TAB = 1, OPT_PEEL = 2 };
-#ifndef HVPR_ITEM_OPT
-#define HVPR_ITEM_OPT (OPT_TAB | OPT_PEEL)      // the kept set
-#endif
-
-// Table entry of a walk step:  lo = tx [0..15] | ty [16..30] | hole [31]    hi = ct [0..11] | n [12..31]
-constexpr int TAB_MAX_TX = 1 << 16, TAB_MAX_TY = 1 << 15, TAB_MAX_CT = 1 << 12, TAB_MAX_N = 1 << 20;
-__device__ __forceinline__ unsigned long long tab_load(const unsigned long long *tab, int step) {      // uniform address: a scalar load
-    return *((const __attribute__((address_space(4))) unsigned long long *)(size_t)tab + step);
-}
 
 #ifdef HVPR_EXP_TIMING
 // kernel experiments: cycle stamps of the phases of every chunk of the SECOND tile of a few workgroups (all four waves), read
@@ -92,11 +56,14 @@ __device__ long long g_conv_dbg[8 * 4 * 64 * 4];
 // (conv_train.py ran that one on the Winograd kernel: 4.7 ms per layer at batch 16 for 173 GFLOP of useful work).  A 16 x 16 output
 // tile = 8 x 8 positions (a, b) x 4 classes; MFMA block mb of a wave IS class (mb >> 1, mb & 1) for the wave's 4 x 8 positions, so which
 // taps a block multiplies is known at compile time and every wave does the same 9 (tap, class) products per chunk.
-template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, int OPT = 0>
+//
+// Per-item work outside the K loop (as in conv_wino.hip):  TAB  the items come from a table, the instantiation a launch with a table
+// runs (forward only);  PEEL  the forward instantiations peel chunk 0 and its first MFMA per accumulator block takes C = 0, no clear.
+template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, bool TAB = false>
 __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     static_assert(!UP2 || (TAPS == 9 && S == 1 && TH == 16 && TW == 16), "UP2: 16 x 16 output tiles of a 3x3 stride-2 layer's data gradient");
-    static_assert(!UP2 || OPT == 0, "the item switches belong to the forward instantiations");
-    constexpr bool TAB = (OPT & OPT_TAB) != 0, PEEL = (OPT & OPT_PEEL) != 0;
+    static_assert(!UP2 || !TAB, "the walk table belongs to the forward instantiations");
+    constexpr bool PEEL = !UP2;
     constexpr int BM = TH * TW;
     constexpr int WM = BM / 2, WN = BN / 2;        // per-wave tile
     constexpr int MB = WM / 32, NB = WN / 32;
@@ -169,30 +136,23 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     const unsigned lds_w0 = lds_addr_of(&s_w[0][0]) + wave_s * 1024u;
 
     // Persistent workgroups: the grid is (resident workgroups per CU) x 256 and workgroup w walks tiles w, w+G, w+2G ...
-    // so that every CU ends up with the same number of tiles (+-1) whatever the dispatcher does after the first wave.
-    // XCD-aware order: consecutive workgroup ids land on consecutive XCDs (8 of them, each with its own L2), so the walk
-    // index is split as (xcd = it % 8, j = it / 8) and the n_ct cout tiles of ONE pixel tile are given to consecutive j of
-    // the SAME xcd: they run at the same time on the same L2 and the input patch is fetched from HBM once, not n_ct times.
+    // so that every CU ends up with the same number of tiles (+-1) whatever the dispatcher does after the first wave, in the
+    // XCD-aware order of conv_walk.h.
     const int n_pt = a.tiles_x * a.tiles_y * a.N;
     const int total_walk = ((n_pt + 7) / 8) * 8 * a.n_ct;
-#ifdef HVPR_EXP_TIMING
-    int dbg_tile = 0;
-    const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;
-#endif
-    unsigned long long e_next = 0ull;                          // the next step's entry, in flight while this item multiplies
+    HVPR_IF_TIMING(int dbg_tile = 0; const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;)
+    ConvTabEntry e_next = 0ull;                                // the next step's entry, in flight while this item multiplies
     if (TAB && (int)blockIdx.x < total_walk) e_next = tab_load(a.tab, blockIdx.x);
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
     int ct, tx, ty, n;
     if constexpr (TAB) {
-        const unsigned lo = (unsigned)e_next, hi = (unsigned)(e_next >> 32);
+        const unsigned lo = (unsigned)e_next, hi = (unsigned)(e_next >> 32);      // the fields of conv_tab_entry (conv_walk.h)
         if (it + (int)gridDim.x < total_walk) e_next = tab_load(a.tab, it + (int)gridDim.x);
         if (lo >> 31) continue;
         tx = (int)(lo & 0xffffu); ty = (int)(lo >> 16 & 0x7fffu); ct = (int)(hi & 0xfffu); n = (int)(hi >> 12);
         if (n >= a.N || ct >= a.n_ct) continue;                // a table of another shape cannot send an access out of bounds
     } else {
-        const int xcd = it & 7, j = it >> 3;
-        ct = j % a.n_ct;
-        int pt = (j / a.n_ct) * 8 + xcd;
+        int pt = conv_walk_step(it, a.n_ct, ct);
         if (pt >= n_pt) continue;
         tx = pt % a.tiles_x; pt /= a.tiles_x;
         ty = pt % a.tiles_y;
@@ -255,24 +215,18 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     const int n_chunks = a.Cin / KSTAGE;
     // one chunk: wait for it, let the next one stream into the other stage, multiply.  `buf` is a compile-time constant in
     // both call sites (the loop is unrolled by two) so that every LDS address is an immediate offset.
-    // FIRST: the peeled chunk 0 of an item (OPT_PEEL only)
+    // FIRST: the peeled chunk 0 of an item (PEEL only)
     auto chunk_step = [&](int c, auto buf_tag, auto first_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
         // chunk c has landed: this wave's DMA is waited for by hand, the barrier covers the other waves' and also
         // says that every wave is done reading the other stage
-#ifdef HVPR_EXP_TIMING
-        const long long q0 = __builtin_readcyclecounter();
-#endif
+        HVPR_IF_TIMING(const long long q0 = __builtin_readcyclecounter();)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-#ifdef HVPR_EXP_TIMING
-        const long long q1 = __builtin_readcyclecounter();
-#endif
+        HVPR_IF_TIMING(const long long q1 = __builtin_readcyclecounter();)
         if (DEAL == 0 && c + 1 < n_chunks) stage(c + 1, BUF ^ 1);
-#ifdef HVPR_EXP_TIMING
-        const long long q2 = __builtin_readcyclecounter();
-#endif
+        HVPR_IF_TIMING(const long long q2 = __builtin_readcyclecounter();)
         const float4 *sp = s_patch[BUF];
         const float4 *sw = s_w[BUF];
         // operand ring: LDS reads run PF taps ahead of the MFMAs that consume them (a dependent-accumulator
@@ -322,13 +276,11 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifdef HVPR_EXP_TIMING
-        if (dbg_slot >= 0 && dbg_tile == 1 && c < 64) {      // a uniform branch: every lane stores the same words
+        HVPR_IF_TIMING(if (dbg_slot >= 0 && dbg_tile == 1 && c < 64) {      // a uniform branch: every lane stores the same words
             asm volatile("" ::"v"(acc[0][0][0]));
             long long *d = g_conv_dbg + (((size_t)dbg_slot * 4 + wid) * 64 + c) * 4;
             d[0] = q0; d[1] = q1; d[2] = q2; d[3] = __builtin_readcyclecounter();
-        }
-#endif
+        })
     };
     stage(0, 0);
     if constexpr (PEEL) {
@@ -380,27 +332,15 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
         }
     }
     __syncthreads();   // the next tile re-zeroes and refills the LDS stages
-#ifdef HVPR_EXP_TIMING
-    ++dbg_tile;
-#endif
+    HVPR_IF_TIMING(++dbg_tile;)
     }
 }
 
-// the table of OPT_TAB: entry `it` is what the kernel's own arithmetic decodes step `it` to, one thread per step
-__global__ void k_conv_tab(int N, int tiles_x, int tiles_y, int n_ct, int total_walk, unsigned long long *__restrict__ tab) {
+// the walk table: entry `it` is what the kernel's own decode makes of step `it` (conv_walk.h), one thread per step
+__global__ void k_conv_tab(int N, int tiles_x, int tiles_y, int n_ct, int total_walk, ConvTabEntry *__restrict__ tab) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= total_walk) return;
-    const int xcd = it & 7, j = it >> 3;
-    const int ct = j % n_ct;
-    int pt = (j / n_ct) * 8 + xcd;
-    if (pt >= tiles_x * tiles_y * N) {
-        tab[it] = 1ull << 31;
-        return;
-    }
-    const int tx = pt % tiles_x; pt /= tiles_x;
-    const int ty = pt % tiles_y;
-    const int n = pt / tiles_y;
-    tab[it] = (unsigned long long)((unsigned)tx | (unsigned)ty << 16) | (unsigned long long)((unsigned)ct | (unsigned)n << 12) << 32;
+    tab[it] = conv_tab_entry(N, tiles_x, tiles_y, n_ct, it);
 }
 
 // tile grid of a forward layer under tile_cfg -> walk steps (0: no table for it)
@@ -410,29 +350,19 @@ static int conv_tab_grid(int N, int H, int W, int taps, int stride, int cout_pad
     const int tw = tile_cfg == 1 ? 8 : 16, bn = tile_cfg == 0 ? 128 : 64;
     if (OH < 1 || OW < 1 || cout_pad % bn != 0) return 0;
     tiles_x = (OW + tw - 1) / tw; tiles_y = (OH + 7) / 8; n_ct = cout_pad / bn;
-    if (tiles_x > TAB_MAX_TX || tiles_y > TAB_MAX_TY || n_ct > TAB_MAX_CT || N > TAB_MAX_N) return 0;
+    if (tiles_x > CONV_TAB_MAX_TX || tiles_y > CONV_TAB_MAX_TY || n_ct > CONV_TAB_MAX_CT || N > CONV_TAB_MAX_N) return 0;
     const long long steps = ((long long)N * tiles_x * tiles_y + 7) / 8 * 8 * n_ct;
     return steps < (1ll << 28) ? (int)steps : 0;
 }
 
-template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, int OPT = 0>
+template <int TH, int TW, int BN, int S, int TAPS, bool UP2 = false, bool TAB = false>
 int launch(ConvArgs a, hipStream_t s) {
     a.tiles_x = (a.OW + TW - 1) / TW;
     a.tiles_y = (a.OH + TH - 1) / TH;
     a.n_ct = a.cout_pad / BN;
     const long long tiles = (long long)a.N * a.tiles_x * a.tiles_y * a.n_ct;
-    static int resident = 0;   // workgroups of this instantiation that fit the chip at once
-    if (resident == 0) {
-        int per_cu = 0, dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv<TH, TW, BN, S, TAPS, UP2, OPT>, 256, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        resident = per_cu * cus;
-    }
-    long long blocks = tiles < resident ? (tiles + 7) / 8 * 8 : resident;   // a multiple of 8: workgroup id % 8 = its XCD
-    if (blocks > resident && resident >= 8) blocks = resident / 8 * 8;
-    hipLaunchKernelGGL((k_conv<TH, TW, BN, S, TAPS, UP2, OPT>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    const int blocks = conv_walk_blocks<k_conv<TH, TW, BN, S, TAPS, UP2, TAB>>(256, 0, tiles);
+    hipLaunchKernelGGL((k_conv<TH, TW, BN, S, TAPS, UP2, TAB>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     return 0;
 }
 
@@ -468,7 +398,7 @@ extern "C" int hvpr_conv2d_s2_dgrad_nhwc_f32(const float *dz, int N, int H, int 
 // The walk table of a forward layer: bytes for a shape (0: no table for it), and the fill.
 extern "C" size_t hvpr_conv2d_tab_bytes(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg) {
     int tiles_x, tiles_y, n_ct;
-    return (size_t)conv_tab_grid(N, H, W, taps, stride, cout_pad, tile_cfg, tiles_x, tiles_y, n_ct) * sizeof(unsigned long long);
+    return (size_t)conv_tab_grid(N, H, W, taps, stride, cout_pad, tile_cfg, tiles_x, tiles_y, n_ct) * sizeof(ConvTabEntry);
 }
 
 extern "C" int hvpr_conv2d_tab_build(int N, int H, int W, int taps, int stride, int cout_pad, int tile_cfg, void *table, hvpr_stream_t stream) {
@@ -477,7 +407,7 @@ extern "C" int hvpr_conv2d_tab_build(int N, int H, int W, int taps, int stride, 
     const int steps = conv_tab_grid(N, H, W, taps, stride, cout_pad, tile_cfg, tiles_x, tiles_y, n_ct);
     if (steps == 0) return HVPR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_conv_tab, dim3(hvpr_cdiv(steps, 256)), dim3(256), 0, (hipStream_t)stream, N, tiles_x, tiles_y, n_ct, steps,
-                       (unsigned long long *)table);
+                       (ConvTabEntry *)table);
     HVPR_CHECK_LAUNCH();
     return HVPR_OK;
 }
@@ -504,21 +434,20 @@ static int conv_nhwc(const float *in, int N, int H, int W, int Cin, const float 
     a.cout_pad = cout_pad; a.cout_real = cout;
     a.out_cstride = out_cstride; a.out_coff = out_coff; a.resid_cstride = resid_cstride;
     a.relu = relu; a.up = up;
-    a.tab = (HVPR_ITEM_OPT & OPT_TAB) ? (const unsigned long long *)table : nullptr;
+    a.tab = (const ConvTabEntry *)table;
     if (cout_pad < a.cout_gemm) return HVPR_ERR_INVALID_ARG;
     if (table && hvpr_conv2d_tab_bytes(N, H, W, taps, stride, cout_pad, tile_cfg) == 0) return HVPR_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     // tile_cfg: 0 = 128 px x 128 ch, 1 = 64 px x 64 ch, 2 = 128 px x 64 ch
     const int bn = tile_cfg == 0 ? 128 : 64;
     if (cout_pad % bn != 0) return HVPR_ERR_INVALID_ARG;
-    constexpr int OPT0 = HVPR_ITEM_OPT & ~OPT_TAB;
-#define HV_CASE(TH, TW, BN, OPT)                                                    \
-    if (taps == 9 && stride == 1) launch<TH, TW, BN, 1, 9, false, OPT>(a, s);       \
-    else if (taps == 9 && stride == 2) launch<TH, TW, BN, 2, 9, false, OPT>(a, s);  \
-    else if (wide1x1) launch<TH, TW, BN, 1, 4, false, OPT>(a, s);                   \
-    else launch<TH, TW, BN, 1, 1, false, OPT>(a, s);
+#define HV_CASE(TH, TW, BN, TAB)                                                    \
+    if (taps == 9 && stride == 1) launch<TH, TW, BN, 1, 9, false, TAB>(a, s);       \
+    else if (taps == 9 && stride == 2) launch<TH, TW, BN, 2, 9, false, TAB>(a, s);  \
+    else if (wide1x1) launch<TH, TW, BN, 1, 4, false, TAB>(a, s);                   \
+    else launch<TH, TW, BN, 1, 1, false, TAB>(a, s);
 #define HV_TILE(TH, TW, BN)                                                         \
-    if (a.tab) { HV_CASE(TH, TW, BN, OPT0 | OPT_TAB) } else { HV_CASE(TH, TW, BN, OPT0) }
+    if (a.tab) { HV_CASE(TH, TW, BN, true) } else { HV_CASE(TH, TW, BN, false) }
     if (tile_cfg == 0) { HV_TILE(8, 16, 128) }
     else if (tile_cfg == 1) { HV_TILE(8, 8, 64) }
     else if (tile_cfg == 2) { HV_TILE(8, 16, 64) }

@@ -21,30 +21,15 @@
 // in the direct kernel.  Persistent, XCD-aware tile walk as in conv_igemm.hip.
 #include <type_traits>
 
-#include "common.h"
+#include "conv_common.h"      // KC, lds_dma16, tab_load, conv_walk_blocks, HVPR_IF_TIMING
 #include "wino_walk.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int KC = 8;             // input channels per K chunk
 constexpr int BN = 64;            // output channels per workgroup
 constexpr int TW = 16, PW = TW + 2;
 constexpr int ROWP = 20;          // LDS slots (float4) per patch row: [parity 2][10]
 constexpr int W_V4 = 16 * 2 * BN; // float4 per U stage: [xi 16][half 2][co 64]
-
-// see conv_igemm.hip: LDS-DMA issued from inline asm so that hipcc does not serialise it against the ds_reads
-__device__ __forceinline__ void lds_dma16(const void *sbase_uniform, unsigned voff_bytes, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff_bytes), "s"(sbase_uniform), "s"(lds_dst_uniform)
-                 : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const void *p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void *)p;
-}
 
 struct WinoArgs {
     const float *in;      // [N, H, W, Cin]
@@ -60,27 +45,8 @@ struct WinoArgs {
     WinoWalk walk;        // tile grid and edge pairing of this shape (wino_walk.h)
     int n_ct;
     float *stats;         // optional [pixel tiles][2][cout]: per-tile sum / sum of squares of the raw output (train-mode BatchNorm)
-    const WinoTabEntry *tab;   // OPT_TAB: one entry per walk step (k_wino_tab), else unused
+    const WinoTabEntry *tab;   // one entry per walk step (k_wino_tab) or null: the walk is decoded in the kernel
 };
-
-// Per-item work outside the K loop that the eval-forward kernel (NG 1, NB 2, no statistics) can shed, each a compile-time switch
-// whose off state is the code every other instantiation runs:
-//   OPT_TAB   the item of a walk step comes from a table built once per shape instead of ~10 runtime integer divisions
-//   OPT_PEEL  chunk 0 is peeled and its first MFMA per accumulator block takes C = 0: no 128-register clear per item
-// (-DHVPR_ITEM_OPT=<bits> builds a library with another set, for measuring; a third switch, wave priority 1 outside the K loop, won
-// alone and lost beside these two and was removed: profiles/NOTES_r17.md §3)
-enum { OPT_TAB = 1, OPT_PEEL = 2 };
-#ifndef HVPR_ITEM_OPT
-#define HVPR_ITEM_OPT (OPT_TAB | OPT_PEEL)      // the kept set
-#endif
-
-// a table entry through the constant address space: the address is uniform, so this is one scalar 8-byte load
-__device__ __forceinline__ WinoTabEntry tab_load(const WinoTabEntry *tab, int step) {
-    const unsigned long long w = *((const __attribute__((address_space(4))) unsigned long long *)(size_t)tab + step);
-    WinoTabEntry e;
-    e.lo = (unsigned)w; e.hi = (unsigned)(w >> 32);
-    return e;
-}
 
 __device__ __forceinline__ float4 f4_fma(float s, float4 a, float4 b) {      // s * a + b, s = +-1: an exact add / subtract
     return make_float4(fmaf(s, a.x, b.x), fmaf(s, a.y, b.y), fmaf(s, a.z, b.z), fmaf(s, a.w, b.w));
@@ -94,10 +60,12 @@ __device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float
 __device__ long long g_wino_dbg[8 * 3 * 4];
 #endif
 
-template <int NG, bool STATS, int NB, int OPT = 0>
+// Per-item work outside the K loop that the eval-forward kernel (NG 1, NB 2, no statistics: PAIR below) sheds:
+//   TAB   the item of a walk step comes from a table built once per shape instead of ~10 runtime integer divisions: the instantiation
+//         a launch with a table runs
+//   PEEL  chunk 0 is peeled and its first MFMA per accumulator block takes C = 0: no 128-register clear per item
+template <int NG, bool STATS, int NB, bool TAB = false>
 __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2, NB == 2 ? 2 : 3))) k_wino(WinoArgs a) {
-    static_assert(OPT == 0 || (NG == 1 && NB == 2 && !STATS), "the item switches belong to the eval-forward kernel");
-    constexpr bool TAB = (OPT & OPT_TAB) != 0, PEEL = (OPT & OPT_PEEL) != 0;
     constexpr int NT = 256 * NG;
     constexpr int TH = 8 * NG, PH = TH + 2;
     constexpr int PPAD = (PH * ROWP + 63) / 64 * 64;          // float4 per channel-half plane
@@ -111,6 +79,8 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     // tiles (<= 2 live block rows each) share 12 patch rows (wino_walk.h) — the padding of ROWP and PPAD, so the K loop below is the
     // same for single and paired items: only what is staged where, two per-lane constants and the epilogue's pixel differ.
     constexpr bool PAIR = NG == 1 && NB == 2 && !STATS;
+    constexpr bool PEEL = PAIR;                                          // both mark the eval-forward kernel
+    static_assert(!TAB || PAIR, "the walk table belongs to the eval-forward kernel");
     constexpr int PH_S = PAIR ? 12 : PH, PW_S = PAIR ? 20 : PW;          // staged rows / columns
     constexpr int BIAS_SLOT = PH_S * ROWP;
     static_assert(W_V4T % NT == 0 && (NB == 2 || NG == 1), "whole DMA pieces");
@@ -149,17 +119,12 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
     const int n_pt = a.walk.per_image * a.N;
     const int total_walk = ((n_pt + 7) / 8) * 8 * a.n_ct;
     const int n_chunks = a.Cin / KC;
-#ifdef HVPR_EXP_TIMING
-    int dbg_item = 0;
-    const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;
-    long long q_in = 0, q_first = 0, q_k = 0;
-#endif
+    HVPR_IF_TIMING(int dbg_item = 0; const int dbg_slot = (blockIdx.x % 97 == 5 && blockIdx.x / 97 < 8) ? (int)(blockIdx.x / 97) : -1;)
+    HVPR_IF_TIMING(long long q_in = 0, q_first = 0, q_k = 0;)
     WinoTabEntry e_next = {0u, 0u};                            // the next step's entry, in flight while this item multiplies
     if (TAB && (int)blockIdx.x < total_walk) e_next = tab_load(a.tab, blockIdx.x);
     for (int it = blockIdx.x; it < total_walk; it += gridDim.x) {
-#ifdef HVPR_EXP_TIMING
-    q_in = __builtin_readcyclecounter();
-#endif
+    HVPR_IF_TIMING(q_in = __builtin_readcyclecounter();)
     int ct, pt = 0;
     int tx, ty, n, mode = WINO_SINGLE;
     if constexpr (TAB) {
@@ -169,7 +134,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         tx = wino_tab_tx(e); ty = wino_tab_ty(e); mode = wino_tab_mode(e); ct = wino_tab_ct(e); n = wino_tab_n(e);
         if (n >= a.N || ct >= a.n_ct) continue;                // a table of another shape cannot send an access out of bounds
     } else {
-    pt = wino_walk_step(it, a.n_ct, ct);
+    pt = conv_walk_step(it, a.n_ct, ct);
     if (pt >= n_pt) continue;
     if constexpr (PAIR) {
         const WinoItem w = wino_walk_item(a.walk, pt);
@@ -243,15 +208,13 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
                 for (int r = 0; r < 16; ++r) acc[b][nb][r] = 0.f;
     }
 
-    // FIRST: the peeled chunk 0 of an item (OPT_PEEL only)
+    // FIRST: the peeled chunk 0 of an item (PEEL only)
     auto chunk_step = [&](int c, auto buf_tag, auto first_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool FIRST = decltype(first_tag)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-#ifdef HVPR_EXP_TIMING
-        if (c == 0) q_first = __builtin_readcyclecounter();
-#endif
+        HVPR_IF_TIMING(if (c == 0) q_first = __builtin_readcyclecounter();)
         const float4 *sp = s_patch + BUF * PATCH_PAD;
         const float4 *sw = s_w + BUF * W_V4T;
         float4 d0[4], d1[4], u[4][NB];
@@ -320,10 +283,7 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         if (n_chunks & 1) chunk_step(n_chunks - 1, std::integral_constant<int, 0>{}, std::false_type{});
     }
 
-#ifdef HVPR_EXP_TIMING
-    asm volatile("" ::"v"(acc[3][NB - 1][15]));
-    q_k = __builtin_readcyclecounter();
-#endif
+    HVPR_IF_TIMING(asm volatile("" ::"v"(acc[3][NB - 1][15])); q_k = __builtin_readcyclecounter();)
     // ---- output transform + epilogue.  A lane holds block l31 and 16 channels per accumulator block (rows (r&3) + 8*(r>>2) +
     // 4*half: four runs of four).  Exchange area (float4): [grp][a][q][channel half of the pass][run][lane]. ----
     const int p = wa >> 1, q = wa & 1;
@@ -413,13 +373,11 @@ __global__ void __launch_bounds__(256 * NG) __attribute__((amdgpu_waves_per_eu(2
         }
     }
     __syncthreads();   // the next tile refills the LDS stages
-#ifdef HVPR_EXP_TIMING
-    if (dbg_slot >= 0 && dbg_item < 3 && tid == 0) {
+    HVPR_IF_TIMING(if (dbg_slot >= 0 && dbg_item < 3 && tid == 0) {
         long long *d = g_wino_dbg + (dbg_slot * 3 + dbg_item) * 4;
         d[0] = q_in; d[1] = q_first; d[2] = q_k; d[3] = __builtin_readcyclecounter();
     }
-    ++dbg_item;
-#endif
+    ++dbg_item;)
     }
 }
 
@@ -457,14 +415,14 @@ __global__ void k_wino_pack(const float *__restrict__ w, const float *__restrict
     }
 }
 
-// the table of OPT_TAB: entry `it` is what step `it` of the walk decodes to (wino_walk.h as it stands), one thread per step
+// the walk table: entry `it` is what step `it` of the walk decodes to (wino_walk.h as it stands), one thread per step
 __global__ void k_wino_tab(WinoWalk walk, int N, int n_ct, int total_walk, WinoTabEntry *__restrict__ tab) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= total_walk) return;
     tab[it] = wino_tab_entry(walk, N, n_ct, it);
 }
 
-template <int NG, bool STATS, int NB, int OPT = 0>
+template <int NG, bool STATS, int NB, bool TAB = false>
 int launch(WinoArgs a, hipStream_t s) {
     constexpr int NT = 256 * NG, TH = 8 * NG, PH = TH + 2;
     constexpr int PPAD = (PH * ROWP + 63) / 64 * 64;
@@ -472,20 +430,9 @@ int launch(WinoArgs a, hipStream_t s) {
     constexpr int lds = (2 * (16 * 2 * 32 * NB) + 2 * NLD_P * NT) * 16;
     a.walk = wino_walk_make(a.H, a.W, TH, NG == 1 && NB == 2 && !STATS);
     a.n_ct = a.cout_pad / (32 * NB);
-    static unsigned long long lds_set = 0ull;
-    if (hvpr_ensure_dyn_lds((const void *)k_wino<NG, STATS, NB, OPT>, lds, &lds_set) != 0) return -1;
-    const long long tiles = (long long)a.N * a.walk.per_image * a.n_ct;
-    static int resident = 0;
-    if (resident == 0) {
-        int per_cu = 0, dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wino<NG, STATS, NB, OPT>, NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        resident = per_cu * cus;
-    }
-    long long blocks = tiles < resident ? (tiles + 7) / 8 * 8 : resident;
-    if (blocks > resident && resident >= 8) blocks = resident / 8 * 8;
-    hipLaunchKernelGGL((k_wino<NG, STATS, NB, OPT>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
+    const int blocks = conv_walk_blocks<k_wino<NG, STATS, NB, TAB>>(NT, lds, (long long)a.N * a.walk.per_image * a.n_ct);
+    if (blocks < 0) return -1;
+    hipLaunchKernelGGL((k_wino<NG, STATS, NB, TAB>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
     return 0;
 }
 
@@ -565,13 +512,12 @@ static int wino_nhwc(const float *in, int N, int H, int W, int Cin, const float 
     a.out_cstride = out_cstride; a.out_coff = out_coff; a.resid_cstride = resid_cstride;
     a.relu = relu;
     a.stats = bn_partials;
-    a.tab = (HVPR_ITEM_OPT & OPT_TAB) ? (const WinoTabEntry *)table : nullptr;
+    a.tab = (const WinoTabEntry *)table;
     if (table && (px_groups != 1 || bn_partials || hvpr_conv2d_wino_tab_bytes(N, H, W, cout, px_groups) == 0)) return HVPR_ERR_UNSUPPORTED;
     if (bn_partials && (px_groups != 1 || relu || gate)) return HVPR_ERR_UNSUPPORTED;      // statistics of the RAW output, 8 x 16 tiles
     int rc;
-    constexpr int OPT0 = HVPR_ITEM_OPT & ~OPT_TAB;
     if (px_groups == 1 && bn_partials) rc = launch<1, true, 2>(a, (hipStream_t)stream);
-    else if (px_groups == 1) rc = a.tab ? launch<1, false, 2, OPT0 | OPT_TAB>(a, (hipStream_t)stream) : launch<1, false, 2, OPT0>(a, (hipStream_t)stream);
+    else if (px_groups == 1) rc = a.tab ? launch<1, false, 2, true>(a, (hipStream_t)stream) : launch<1, false, 2>(a, (hipStream_t)stream);
     else if (px_groups == 2) rc = launch<2, false, 2>(a, (hipStream_t)stream);
     else if (px_groups == 4) rc = launch<1, false, 1>(a, (hipStream_t)stream);      // 8 x 16 px x 32 channels: twice the tiles
     else return HVPR_ERR_INVALID_ARG;

@@ -16,11 +16,9 @@
 // blocks (16 ds_read_b32), forms row a of (A dY At) and of (Bt d B) in registers (~20 VALU) and issues 8 MFMAs.  The two signs
 // of A's last row / column are left out of the operands and applied by the reducing kernel.  Split-K over pixel tiles into
 // partials, summed in a fixed order by k_wgrad_wino_reduce, which also applies Gt . G: deterministic.
-#include "common.h"
+#include "conv_common.h"      // f32x16, HVPR_IF_TIMING
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WwArgs {
     const float *x;     // [N, H, W, Cin]
@@ -59,6 +57,9 @@ typedef __attribute__((address_space(3))) float *lds_fp;
 // pieces take an out-of-range offset and come back as zeros, so the loop has no branch).  One barrier per tile.  (Measured before:
 // issuing the 10 loads of a tile in one go cost 3.3 k cycles and the 10 LDS store pairs 2.4 k of the 25 k cycles per tile, with the
 // matrix cores idle — tools/wgrad_phases.py.)
+// Timing build: the cycles between consecutive stamps, summed per K step (and the closing barrier) over a workgroup's tiles.
+#define WW_NOW(t) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory")
+#define WW_STAMP(k) HVPR_IF_TIMING(do { WW_NOW(tnow); tph[k] += tnow - tprev; tprev = tnow; } while (0))
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) k_wgrad_wino(WwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem_w[];
     const lds_fp s0 = (lds_fp)smem_w;                  // stage: [co][pixel] pitch PA, then [ci][patch pixel] pitch PB
@@ -170,15 +171,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
         for (int u = 0; u < 2 * NIT; ++u) load_unit(u, t1);
     }
     __syncthreads();
-#ifdef HVPR_EXP_TIMING
-    unsigned long long tph[K_STEPS + 2], tprev, tnow;
-    for (int i = 0; i < K_STEPS + 2; ++i) tph[i] = 0;
-#define WW_NOW(t) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory")
-#define WW_STAMP(k) do { WW_NOW(tnow); tph[k] += tnow - tprev; tprev = tnow; } while (0)
-    WW_NOW(tprev);
-#else
-#define WW_STAMP(k)
-#endif
+    HVPR_IF_TIMING(unsigned long long tph[K_STEPS + 2], tprev, tnow; for (int i = 0; i < K_STEPS + 2; ++i) tph[i] = 0;)
+    HVPR_IF_TIMING(WW_NOW(tprev);)
     for (int k = 0; k < n_tiles; ++k) {
         const int cur = (k & 1) * STAGE_F;
         const lds_fp wr = s0 + (STAGE_F - cur);        // tile k + 1's stage
@@ -248,13 +242,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
         __syncthreads();                 // everybody is done reading stage `cur` and writing the other one
         WW_STAMP(K_STEPS + 1);
     }
-#ifdef HVPR_EXP_TIMING
-    if (lane == 0 && (wid == 0 || wid == 5) && ((ot == 0 && chunk == 0) || (ot == 1 && chunk == 3)))
+    HVPR_IF_TIMING(if (lane == 0 && (wid == 0 || wid == 5) && ((ot == 0 && chunk == 0) || (ot == 1 && chunk == 3)))
         printf("k_wgrad_wino wg (%d, %d) wave %d: %d tiles; cycles per tile: K steps %llu %llu %llu %llu | %llu %llu %llu %llu | %llu %llu %llu %llu | %llu %llu %llu %llu | "
                "barrier %llu\n", ot, chunk, wid, n_tiles, tph[1] / n_tiles, tph[2] / n_tiles, tph[3] / n_tiles, tph[4] / n_tiles, tph[5] / n_tiles,
                tph[6] / n_tiles, tph[7] / n_tiles, tph[8] / n_tiles, tph[9] / n_tiles, tph[10] / n_tiles, tph[11] / n_tiles, tph[12] / n_tiles,
-               tph[13] / n_tiles, tph[14] / n_tiles, tph[15] / n_tiles, tph[16] / n_tiles, tph[17] / n_tiles);
-#endif
+               tph[13] / n_tiles, tph[14] / n_tiles, tph[15] / n_tiles, tph[16] / n_tiles, tph[17] / n_tiles);)
     // partials [chunk][xi][co][ci]; C/D map of 32x32: column (ci) = lane & 31, row (co) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     float *out = a.part + (size_t)chunk * 16 * a.Cout * a.Cin;
 #pragma unroll

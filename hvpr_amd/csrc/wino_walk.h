@@ -11,11 +11,7 @@
 // with wi = tiles_x - 1 under right pairing (else tiles_x) and hi = tiles_y - 1 under bottom pairing (else tiles_y).
 #pragma once
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define HVPR_WALK_HD __host__ __device__ __forceinline__
-#else
-#define HVPR_WALK_HD inline
-#endif
+#include "conv_walk.h"      // HVPR_WALK_HD, conv_walk_step: step -> (channel tile, item)
 
 enum { WINO_SINGLE = 0, WINO_PAIR_RIGHT = 1, WINO_PAIR_BOTTOM = 2 };
 
@@ -49,15 +45,6 @@ HVPR_WALK_HD WinoWalk wino_walk_make(int H, int W, int tile_h, int pairing) {
     return w;
 }
 
-// Step `it` of the persistent walk over round_up(N * per_image, 8) * n_ct steps -> channel tile `ct` and item (may be >= N *
-// per_image: a hole of the last round).  Eight consecutive steps are the eight XCDs' (round-robin workgroup dispatch): they take
-// eight neighbouring items of the same channel tile, and an XCD's next step is the next channel tile of the same item (L2 reuse).
-HVPR_WALK_HD int wino_walk_step(int it, int n_ct, int &ct) {
-    const int xcd = it & 7, j = it >> 3;
-    ct = j % n_ct;
-    return (j / n_ct) * 8 + xcd;
-}
-
 // item `pt` of 0 .. N * per_image - 1
 HVPR_WALK_HD WinoItem wino_walk_item(const WinoWalk &w, int pt) {
     WinoItem it;
@@ -89,7 +76,7 @@ HVPR_WALK_HD int wino_walk_steps(const WinoWalk &w, int N, int n_ct) { return (N
 HVPR_WALK_HD WinoTabEntry wino_tab_entry(const WinoWalk &w, int N, int n_ct, int it) {
     WinoTabEntry e;
     int ct;
-    const int pt = wino_walk_step(it, n_ct, ct);
+    const int pt = conv_walk_step(it, n_ct, ct);
     if (pt >= N * w.per_image) {
         e.lo = 1u << 31; e.hi = 0u;
         return e;

@@ -143,3 +143,32 @@ def test_split_bf16_deconv_into_concat_slice(planes, s, cin, cout):
     o = kernels.deconv_nhwc_bf3(xs, pc, out, out_coff=24)
     _close(o[..., 24:24 + cout].permute(0, 3, 1, 2).cpu().double(), ref, tol=TOL[planes])
     assert (o[..., :24] == -7).all() and (o[..., 24 + cout:] == -7).all()
+
+
+@pytest.mark.parametrize("N,H,W,cin,cout", [(1, 8, 16, 16, 64),        # one tile, one K step
+                                            (1, 9, 17, 32, 68)])       # ragged tiles, two K steps, a second ragged channel tile
+def test_split_bf16_conv_on_a_second_device(N, H, W, cin, cout):
+    """tile_cfg 0, two planes, stride 1 is the k_conv3 instantiation with 114 688 B of dynamic LDS: above the 64 KB a kernel gets
+    without hipFuncSetAttribute(MaxDynamicSharedMemorySize), and that attribute holds for the device it was set on only.  The
+    same seeded layer on cuda:0 and then on cuda:1: both launches succeed and give the same bits."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs: the dynamic-LDS limit of a kernel is set per device")
+    from hvpr_amd._lib import lib
+    g = torch.Generator().manual_seed(cin * 1000 + cout)
+    x = _rand(g, N, H, W, cin)
+    w = _rand(g, cout, cin, 3, 3) / np.sqrt(cin * 9)
+    scale, shift = torch.rand(cout, generator=g) + 0.5, _rand(g, cout) * 0.3
+    outs = []
+    for dev in ("cuda:0", "cuda:1"):
+        with torch.cuda.device(dev):
+            pc = kernels.pack_conv_bf3(w.to(dev), scale.to(dev), shift.to(dev), stride=1, relu=True, tile_cfg=0, planes=2)
+            xs = kernels.split_bf16(x.to(dev), 2)
+            cstride = (cout + 7) // 8 * 8                      # the kernel wants a channel stride that is a multiple of 8
+            y = torch.full((N, H, W, cstride), float("nan"), device=dev)
+            status = lib().hvpr_conv2d_nhwc_bf16x3(xs.data_ptr(), N, H, W, cin, pc.w.data_ptr(), pc.bias.data_ptr(), 1, cout, pc.cout_pad,
+                                                   1, None, None, 0, y.data_ptr(), 0, cstride, 0, 0, 2, kernels._stream())
+            torch.cuda.synchronize()
+            print(f"{dev}: status {status}")
+            assert status == 0, (dev, status)
+            outs.append(y[..., :cout].cpu())
+    assert not bool(outs[0].isnan().any()) and torch.equal(outs[0], outs[1])

@@ -130,7 +130,7 @@ def _walk_make(H, W):
 
 
 def _walk_table_numpy(N, H, W, cout):
-    """wino_walk_step + wino_walk_item + the packing of wino_tab_entry, per step"""
+    """conv_walk_step + wino_walk_item + the packing of wino_tab_entry, per step"""
     w = _walk_make(H, W)
     n_ct = (cout + 63) // 64
     n_pt = N * w["per_image"]

@@ -30,7 +30,7 @@ static long long replay(int N, int H, int W, int tile_h, int pairing, int n_ct) 
     long long items = 0;
     for (int it = 0; it < total_walk; ++it) {
         int ct;
-        const int pt = wino_walk_step(it, n_ct, ct);
+        const int pt = conv_walk_step(it, n_ct, ct);
         if (pt >= n_pt) continue;
         ++items;
         const WinoItem m = wino_walk_item(w, pt);
