@@ -140,14 +140,14 @@ __global__ void __launch_bounds__(64) k_atss_candidates(const float *__restrict_
     const float lx = pb[4], ly = pb[3];
     const bool inside = xl <= lx / 2 && xl >= -lx / 2 && yl <= ly / 2 && yl >= -ly / 2;
     if (v >= thresh && inside)                                        // the maximum is the highest IoU, then the lowest g (:123)
-        atomicMax(&plane[(size_t)b * A + a], ((unsigned long long)ord_of(v) << 8) | (unsigned)(255 - g));
+        atomicMax(&plane[(size_t)b * A + a], ((unsigned long long)hvpr_ord_of(v) << 8) | (unsigned)(255 - g));
 }
 
 // ---- the best anchor of every ground truth: sweep_pairs (assign_common.h) over every row that stays, no class mask ---------------------
 struct AtssLds {
     PolyStore ps;
     __attribute__((aligned(16))) BoxLite gl[kMaxGt];
-    unsigned long long gv[kMaxGt];           // the workgroup's best (ord_of(iou), ~anchor) per ground truth; 0: no pair reached the clip
+    unsigned long long gv[kMaxGt];           // the workgroup's best (hvpr_ord_of(iou), ~anchor) per ground truth; 0: no pair reached the clip
     unsigned short ring[kSweepRing];         // (anchor in workgroup) << 8 | g
 };
 
@@ -163,7 +163,7 @@ __device__ __forceinline__ void atss_clip_round(AtssLds &s, const float *__restr
         make_box(pa, A);
         make_box(pb, B);
         const float v = MATCH_HEIGHT ? iou_3d(pa, pb, A, B, s.ps, lane) : iou_bev(A, B, s.ps, lane);
-        atomicMax(&s.gv[g], ((unsigned long long)ord_of(v) << 32) | (unsigned)~(unsigned)(a0 + al));
+        atomicMax(&s.gv[g], ((unsigned long long)hvpr_ord_of(v) << 32) | (unsigned)~(unsigned)(a0 + al));
     }
 }
 
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(256) k_atss_forced(int A, int G, int batch, co
     if (g >= n_rows[b]) return;
     const unsigned long long key = gbest[t];
     unsigned a = 0u;
-    if (key && of_ord((unsigned)(key >> 32)) > 0.f) a = ~(unsigned)key;
+    if (key && hvpr_of_ord((unsigned)(key >> 32)) > 0.f) a = ~(unsigned)key;
     atomicMax(&plane[(size_t)b * A + a], kAtssForced | (unsigned)g);
 }
 

@@ -11,12 +11,6 @@ namespace {
 constexpr int kMaxGt = 256;          // ground-truth rows per frame (hvpr.yaml pads to ~50); a ring entry keeps the row in 8 bits
 constexpr int kSweepRing = 128;      // pairs; a step adds at most 64 to fewer than 64
 
-__device__ __forceinline__ unsigned ord_of(float v) {          // order-preserving map to unsigned; 0 is below every float
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float of_ord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-
 // The last row of a frame that is no padding: trailing rows whose SIGNED fp32 sum over the 7 box fields, class column excluded, is
 // exactly 0 are cut, row 0 always stays (`while cnt > 0 and cur_gt[cnt].sum() == 0`, axis_aligned_target_assigner.py:53-57,
 // atss_target_assigner.py:40-46).  Every thread of the workgroup calls it, whatever the block size; s_last is one int of LDS.

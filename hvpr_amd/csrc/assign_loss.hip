@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) k_assign_gt_max(const float *__restrict__
         __syncthreads();
         if (threadIdx.x == 0) {
             const float m = fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3]));
-            atomicMax(&g2a_ord[(size_t)b * G + g], ord_of(m));
+            atomicMax(&g2a_ord[(size_t)b * G + g], hvpr_ord_of(m));
         }
         __syncthreads();
     }
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256) k_assign_labels(const float *__restrict__
     if (threadIdx.x == 0) s_pos = 0;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         float m = -2.f;
-        if (s.use[g]) m = of_ord(g2a_ord[(size_t)b * G + g]);
+        if (s.use[g]) m = hvpr_of_ord(g2a_ord[(size_t)b * G + g]);
         s_g2a[g] = m <= 0.f ? -1.f : m;                           // no overlap at all: no forced match (:155-156)
     }
     __syncthreads();
@@ -154,13 +154,13 @@ __global__ void __launch_bounds__(256) k_assign_labels(const float *__restrict__
 // + 3.3 KB of tables and the ring = 29.9 KB static, five workgroups per CU.
 // Two launches of the same sweep: pass 1 gives the per-ground-truth maximum (LDS atomicMax per workgroup, then one global atomicMax
 // per ground truth on the order-preserving bits), pass 2 clips the same pairs with the same function — the forced-match test
-// `iou == g2a_max` is an equality on identical bits — and keeps per anchor the 64-bit key (ord_of(iou), 255 - g), whose maximum is
+// `iou == g2a_max` is an equality on identical bits — and keeps per anchor the 64-bit key (hvpr_ord_of(iou), 255 - g), whose maximum is
 // the FIRST maximum over g in any arrival order.  Integer atomics only: labels, targets and counts are the same bits on every run.
 struct A3Lds {
     PolyStore ps;
     __attribute__((aligned(16))) BoxLite gl[kMaxGt];
     unsigned long long key[64];      // pass 2: best clipped (iou, first g) per anchor of the workgroup
-    unsigned gv[kMaxGt];             // pass 1: ord_of of the workgroup's best iou per ground truth; pass 2: the bits of g2a_max
+    unsigned gv[kMaxGt];             // pass 1: hvpr_ord_of of the workgroup's best iou per ground truth; pass 2: the bits of g2a_max
     int cls[kMaxGt];
     int force[64];
     unsigned short ring[kSweepRing]; // (anchor in workgroup) << 8 | g
@@ -168,7 +168,7 @@ struct A3Lds {
     int last;
 };
 
-__device__ __forceinline__ unsigned long long a3_key(float v, int g) { return ((unsigned long long)ord_of(v) << 32) | (unsigned)(255 - g); }
+__device__ __forceinline__ unsigned long long a3_key(float v, int g) { return ((unsigned long long)hvpr_ord_of(v) << 32) | (unsigned)(255 - g); }
 
 template <int PASS>
 __device__ __forceinline__ void a3_clip_round(A3Lds &s, const float *__restrict__ anchors, int a0, const float *__restrict__ gt_frame,
@@ -183,7 +183,7 @@ __device__ __forceinline__ void a3_clip_round(A3Lds &s, const float *__restrict_
         make_box(pb, B);
         const float v = iou_3d(pa, pb, A, B, s.ps, lane);
         if (PASS == 1) {
-            atomicMax(&s.gv[g], ord_of(v));
+            atomicMax(&s.gv[g], hvpr_ord_of(v));
         } else {
             atomicMax(&s.key[al], a3_key(v, g));
             if (v == __uint_as_float(s.gv[g])) s.force[al] = 1;
@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(64) k_assign3d(const float *__restrict__ ancho
             s.gv[g] = 0u;
         } else {
             const unsigned o = use ? g2a_ord[(size_t)b * G + g] : 0u;      // 0: no pair of this ground truth reached the clip
-            const float mx = o ? of_ord(o) : 0.f;
+            const float mx = o ? hvpr_of_ord(o) : 0.f;
             s.gv[g] = __float_as_uint(mx <= 0.f ? -1.f : mx);             // no overlap at all: no forced match (:155-156)
         }
     }
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(64) k_assign3d(const float *__restrict__ ancho
         int arg;
         const unsigned long long k = s.key[lane] > best_key ? s.key[lane] : best_key;
         if (k) {
-            best = of_ord((unsigned)(k >> 32));
+            best = hvpr_of_ord((unsigned)(k >> 32));
             arg = 255 - (int)(k & 255u);
         } else {                                                          // no ground truth in use: k_assign_labels' -2 / -inf, row 0
             best = G > 0 ? -2.f : -INFINITY;

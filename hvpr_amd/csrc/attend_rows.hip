@@ -31,15 +31,6 @@ constexpr int kGroup = 16;
 constexpr int kBlock = 256;
 constexpr int kPillarsPerBlock = kBlock / kGroup;
 
-// all-lanes sum over the 16 lanes of a DPP row (the first four steps of hvpr_reduce: the same tree in every group)
-__device__ __forceinline__ float group_sum16(float v) {
-    v = v + hvpr_dpp<0xB1>(v);     // quad_perm [1,0,3,2]
-    v = v + hvpr_dpp<0x4E>(v);     // quad_perm [2,3,0,1]
-    v = v + hvpr_dpp<0x141>(v);    // row_half_mirror
-    v = v + hvpr_dpp<0x140>(v);    // row_mirror
-    return v;
-}
-
 template <int KMAX>
 __global__ void __launch_bounds__(kBlock) k_attend_rows(const float *__restrict__ q, int M, const float *__restrict__ rows, long long N,
                                                         const int *__restrict__ idx, int k, float *__restrict__ out,
@@ -69,7 +60,7 @@ __global__ void __launch_bounds__(kBlock) k_attend_rows(const float *__restrict_
             d = fmaf(qv.y, r[j].y, d);
             d = fmaf(qv.z, r[j].z, d);
             d = fmaf(qv.w, r[j].w, d);
-            lg[j] = group_sum16(d);
+            lg[j] = hvpr_reduce_sum<16>(d);
             mx = fmaxf(mx, lg[j]);
         } else {
             lg[j] = 0.f;

@@ -50,16 +50,6 @@ struct Staged {
     int b0;
 };
 
-// largest b in [0, B) with off[b] <= row, for off[0] <= row < off[B] (an empty frame repeats its offset and is never found)
-__device__ __forceinline__ int frame_of(const int *off, int B, int row) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ void load_calib(const float *row, float *dst, int i) {
     // words 12..23 hold P2 (3 x 4, row-major); dst[12 + r*3 + c] = P2^T[r][c] = P2[c][r]
     if (i < 12 || i >= 24) dst[i] = row[i];
@@ -70,7 +60,7 @@ __device__ __forceinline__ void load_calib(const float *row, float *dst, int i) 
 __device__ __forceinline__ void stage(const SelArgs &a, Staged &s, int tile_base) {
     for (int i = threadIdx.x; i <= a.B; i += kThreads) s.off[i] = min(max(a.off[i], 0), a.rows);
     __syncthreads();
-    if (threadIdx.x == 0) s.b0 = (tile_base >= s.off[0] && tile_base < s.off[a.B]) ? frame_of(s.off, a.B, tile_base) : 0;
+    if (threadIdx.x == 0) s.b0 = (tile_base >= s.off[0] && tile_base < s.off[a.B]) ? hvpr_frame_of(s.off, a.B, tile_base) : 0;
     __syncthreads();
     if ((a.mask & 1) && threadIdx.x < kCalib) load_calib(a.calib + (size_t)s.b0 * kCalib, s.cal, threadIdx.x);
     __syncthreads();
@@ -138,7 +128,7 @@ __global__ void __launch_bounds__(kThreads) k_count(SelArgs a, Carved w) {
         if (row >= lo && row < hi) {
             const float *p = a.pts + (size_t)row * a.F;
             const float x = p[0], y = p[1], z = p[2];
-            f = decide(a, s, frame_of(s.off, a.B, row), x, y, z);
+            f = decide(a, s, hvpr_frame_of(s.off, a.B, row), x, y, z);
             if constexpr (NEAR) g = f && hvpr_pred_near(x, y, z, a.near);
         }
         const unsigned long long bal = __ballot(f);
@@ -222,7 +212,7 @@ __device__ __forceinline__ void walk_tile(const SelArgs &a, const Carved &w, Pla
                 const float *p = a.pts + (size_t)row * a.F;
                 v[k].x = p[0]; v[k].y = p[1]; v[k].z = p[2];
             }
-            frame[k] = frame_of(s.off, a.B, row);
+            frame[k] = hvpr_frame_of(s.off, a.B, row);
             keep[k] = decide(a, s, frame[k], v[k].x, v[k].y, v[k].z);
             if constexpr (NEAR) isnear[k] = keep[k] && hvpr_pred_near(v[k].x, v[k].y, v[k].z, a.near);
         }

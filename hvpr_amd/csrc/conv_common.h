@@ -1,14 +1,7 @@
 // What the eval convolution kernels share (conv_igemm.hip k_conv, conv_wino.hip k_wino, conv_bf3.hip k_conv3): LDS-DMA staging,
-// the scalar load of a walk-table entry, the sizing of the persistent grid and the stamps of the timing build.
+// the scalar load of a walk-table entry and the sizing of the persistent grid (the timing build's HVPR_IF_TIMING: wave.h).
 #pragma once
 #include "common.h"
-
-// timing build (python -m hvpr_amd.build --timing): in-kernel cycle stamps; in every other build the arguments vanish
-#ifdef HVPR_EXP_TIMING
-#define HVPR_IF_TIMING(...) __VA_ARGS__
-#else
-#define HVPR_IF_TIMING(...)
-#endif
 
 namespace {
 

@@ -281,19 +281,14 @@ __global__ void __launch_bounds__(256) k_bn_reduce(const float *__restrict__ z, 
 }
 
 // fwd: mean, biased variance and 1/sqrt(var + eps) per channel; bwd: s1, s2 per channel.  One wave per channel: lanes stride over
-// the workgroup rows in double, then a fixed butterfly — deterministic.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// the workgroup rows in double, then a fixed butterfly (hvpr_wave_sum_xor) — deterministic.
 __global__ void __launch_bounds__(256) k_bn_finalize(const float *__restrict__ ws, int blocks, int C, double count, float eps, int bwd,
                                                      float *__restrict__ o0, float *__restrict__ o1, float *__restrict__ o2) {
     const int c = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     if (c >= C) return;
     double a = 0.0, b = 0.0;
     for (int i = lane; i < blocks; i += 64) { a += (double)ws[(size_t)i * 2 * C + c]; b += (double)ws[(size_t)i * 2 * C + C + c]; }
-    a = wave_sum_f64(a); b = wave_sum_f64(b);
+    a = hvpr_wave_sum_xor(a); b = hvpr_wave_sum_xor(b);
     if (lane != 0) return;
     if (bwd) { o0[c] = (float)a; o1[c] = (float)b; return; }
     const double m = a / count;
@@ -317,7 +312,7 @@ __global__ void __launch_bounds__(256) k_bn_finalize4(const float *__restrict__ 
         b[0] += (double)y.x; b[1] += (double)y.y; b[2] += (double)y.z; b[3] += (double)y.w;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { a[k] = wave_sum_f64(a[k]); b[k] = wave_sum_f64(b[k]); }
+    for (int k = 0; k < 4; ++k) { a[k] = hvpr_wave_sum_xor(a[k]); b[k] = hvpr_wave_sum_xor(b[k]); }
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { s_part[wid][k] = a[k]; s_part[wid][4 + k] = b[k]; }
@@ -424,7 +419,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float4 *__restrict__
             // several waves and meet in the atomic)
             if ((groups & (groups - 1)) == 0) {
                 const int w = groups < 64 ? groups : 64;
-                for (int o = w >> 1; o > 0; o >>= 1) ga += __shfl_xor(ga, o, 64);
+                HVPR_GROUP_SUM_XOR(ga, w);
                 if (live && ((threadIdx.x & 63) & (w - 1)) == 0) atomicAdd(dgate + i / groups, ga);
             } else if (live) {       // C / 4 not a power of two (48, 96, ... channels): a pixel's lanes straddle waves unevenly
                 atomicAdd(dgate + i / groups, ga);

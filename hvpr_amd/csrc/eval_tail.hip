@@ -25,8 +25,7 @@ __global__ void __launch_bounds__(64) k_gt_count(const float *__restrict__ gt, i
         for (int c = 0; c < C; ++c) s += g[(size_t)r * C + c];
         if (!(s == 0.0f)) last = r;                       // rising r: the lane's last non-empty row
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    HVPR_WAVE_MAX_XOR(last);
     if (lane <= T) counts[(size_t)b * (1 + T) + lane] = lane == 0 ? (G > 0 ? last + 1 : 0) : 0;
 }
 
@@ -90,8 +89,7 @@ __global__ void __launch_bounds__(64) k_prediction_annos(const AnnoArgs a) {
     const int b = blockIdx.y, lane = threadIdx.x;
     int before = 0;
     for (int i = lane; i < b; i += 64) before += live_of(a.count, i, a.P);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+    HVPR_WAVE_SUM_XOR(before);
     const int n = live_of(a.count, b, a.P);
     const long long first = a.row_base[0] + before;
     if (blockIdx.x == 0 && lane == 0) {
@@ -148,8 +146,7 @@ __global__ void __launch_bounds__(64) k_advance_rows(const int32_t *__restrict__
     const int lane = threadIdx.x;
     int total = 0;
     for (int i = lane; i < B; i += 64) total += live_of(count, i, P);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
+    HVPR_WAVE_SUM_XOR(total);
     if (lane == 0) row_base[0] = min(row_base[0] + total, cap);
 }
 

@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(64) k_obj_count(const int32_t *__restrict__ bl
     const int32_t *row = blk_cnt + (size_t)blockIdx.x * max_blk;
     int s = 0;
     for (int i = threadIdx.x; i < max_blk; i += 64) s += row[i];
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    HVPR_WAVE_SUM_XOR(s);
     if (threadIdx.x == 0) obj_count[blockIdx.x] = s;
 }
 

@@ -128,9 +128,7 @@ __global__ void __launch_bounds__(64) k_nms_mask(const NmsCall nc, float thresh)
     s_bits[t] = 0ull;
     __syncthreads();
     const int ncol = min(64, n - cb * 64);
-#ifdef HVPR_EXP_TIMING
-    const long long tq0 = __builtin_readcyclecounter();
-#endif
+    HVPR_IF_TIMING(const long long tq0 = __builtin_readcyclecounter();)
     int total2_all = 0;   // (only the HVPR_EXP_TIMING build reports it)
     (void)total2_all;
 #pragma unroll 1
@@ -150,12 +148,7 @@ __global__ void __launch_bounds__(64) k_nms_mask(const NmsCall nc, float thresh)
         }
         // exclusive prefix of the per-lane pair counts
         const int cnt = __popc(near);
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            if (t >= o) incl += u;
-        }
+        const int incl = hvpr_wave_scan_incl(cnt);
         const int total = __shfl(incl, 63, 64);
         int pos = incl - cnt;
         while (near) {
@@ -184,10 +177,8 @@ __global__ void __launch_bounds__(64) k_nms_mask(const NmsCall nc, float thresh)
         total2_all += total2;
     }
     __syncthreads();
-#ifdef HVPR_EXP_TIMING
-    if (t == 0 && rb % 8 == 0 && cb % 8 == 0)
-        printf("nms tile %d %d: %d pairs clipped, %lld cycles\n", rb, cb, total2_all, (long long)__builtin_readcyclecounter() - tq0);
-#endif
+    HVPR_IF_TIMING(if (t == 0 && rb % 8 == 0 && cb % 8 == 0)
+        printf("nms tile %d %d: %d pairs clipped, %lld cycles\n", rb, cb, total2_all, (long long)__builtin_readcyclecounter() - tq0);)
     if (row < n) mask[(size_t)row * nb + cb] = s_bits[t];
 }
 
@@ -243,12 +234,7 @@ __global__ void __launch_bounds__(64) k_nms_pairs(const NmsCall nc) {
             }
         }
         const int cnt = __popc(near);
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            if (t >= o) incl += u;
-        }
+        const int incl = hvpr_wave_scan_incl(cnt);
         const int total = __shfl(incl, 63, 64);
         int pos = incl - cnt;
         while (near) {
@@ -293,12 +279,7 @@ __global__ void __launch_bounds__(1024) k_nms_scan(const NmsCall nc) {
         run += c[i];
         if (live && ++cb == nba) { ++rb; cb = rb; }
     }
-    int incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
+    const int incl = hvpr_wave_scan_incl(run);
     if (lane == 63) s_wave[wid] = incl;
     __syncthreads();
     int base = incl - run;
@@ -339,19 +320,13 @@ __global__ void __launch_bounds__(kClipThreads) k_nms_clip(const NmsCall nc, flo
             const int S = nc.n_segments, spare = (int)gridDim.x - S;
             long long all = 0;
             for (int s = t; s < S; s += 64) all += clip_total(nc, s);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) all += __shfl_xor(all, o, 64);
+            HVPR_WAVE_SUM_XOR(all);
             int base = 0;
             for (int s0 = 0; s0 < S; s0 += 64) {
                 const int s = s0 + t;
                 const int tot = s < S ? clip_total(nc, s) : 0;
                 const int mine = tot > 0 ? 1 + (int)((long long)spare * tot / all) : 0;
-                int incl = mine;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int u = __shfl_up(incl, o, 64);
-                    if (t >= o) incl += u;
-                }
+                const int incl = hvpr_wave_scan_incl(mine);
                 const int first = base + incl - mine;
                 if ((int)blockIdx.x >= first && (int)blockIdx.x < first + mine) { s_split[0] = s; s_split[1] = first; s_split[2] = mine; }
                 base += __shfl(incl, 63, 64);

@@ -188,8 +188,7 @@ __global__ void __launch_bounds__(256) k_kitti_match(const MatchArgs a) {
         }
         fp += !dontcare;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) fp += __shfl_xor(fp, o, 64);
+    HVPR_WAVE_SUM_XOR(fp);
     if (lane == 0) a.ws[((size_t)combo * T + t) * a.n_frames + f] = FrameStat{tp, fp, fn, 0, sim};
 }
 
@@ -206,11 +205,7 @@ __global__ void __launch_bounds__(64) k_kitti_reduce(const FrameStat *__restrict
             const FrameStat s = ws[(size_t)ct * n_frames + f];
             tp += s.tp; fp += s.fp; fn += s.fn; sim += s.sim;
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        tp += __shfl_xor(tp, o, 64); fp += __shfl_xor(fp, o, 64); fn += __shfl_xor(fn, o, 64);
-        sim += __shfl_xor(sim, o, 64);
-    }
+    HVPR_WAVE_SUM_XOR(tp, fp, fn, sim);
     if (lane == 0) {
         counts[ct * 3 + 0] = tp; counts[ct * 3 + 1] = fp; counts[ct * 3 + 2] = fn;
         if (sim_out) sim_out[ct] = sim;

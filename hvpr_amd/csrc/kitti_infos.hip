@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(64) k_sum(const int32_t *__restrict__ blk_cnt,
     const int32_t *row = box ? blk_cnt + (size_t)r * max_blk : fov_blk + (size_t)(r - n_obj) * max_blk;
     int s = 0;
     for (int i = threadIdx.x; i < max_blk; i += 64) s += row[i];
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    HVPR_WAVE_SUM_XOR(s);
     if (threadIdx.x == 0) {
         if (box) obj_count[r] = s; else fov_count[r - n_obj] = s;
     }

@@ -43,13 +43,6 @@ constexpr float kRelErr = 1.0e-3f, kAbsErr = 6.2e-5f, kHalfMax = 65000.f;    // 
 
 using namespace hvpr_sel;
 
-__device__ __forceinline__ float vmaxr(float a, float b) {   // v_max_f32 without the operand quieting fmaxf() adds
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-struct op_maxr { __device__ __forceinline__ float operator()(float a, float b) const { return vmaxr(a, b); } };
-
 // WAVES = 16: one pillar per wave in the per-pillar steps (a 16th of the items per wave in the others); WAVES = 8: two pillars
 // per wave in turn, 16 tiles per wave — half the workgroup, so that TWO independent workgroups share a CU and the memory phases of
 // one fall into the compute phases of the other (the sixteen waves of one workgroup move in lockstep between its barriers)
@@ -94,13 +87,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
     if (p0 >= M) return;
     const int np = min(kPillars, M - p0);
 
-#ifdef HVPR_EXP_TIMING
-#define RO_STAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ts[i] = __builtin_readcyclecounter(); } while (0)
-    long long ts[12];
-#else
-#define RO_STAMP(i)
-#endif
-    RO_STAMP(0);
+    HVPR_IF_TIMING(long long ts[12];)
+    HVPR_STAMP(ts, 0);
     // The bank tiles of the wave's first virtual wave do not depend on the features: in the 8-wave form both are requested before the
     // barrier — the features first (they return first and go to LDS while the tiles are still travelling) — so that the two round
     // trips are one (batch 16: 154 -> 150 us).
@@ -132,7 +120,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
     for (int h = 0; h < PPW; ++h) s_key[(wid * PPW + h) * 64 + lane] = 0ull;     // step 4's key lists end in zeros
     if (tid < kPillars) { s_tot[tid] = 0; s_flag[tid] = 0; }
     __syncthreads();
-    RO_STAMP(1);
+    HVPR_STAMP(ts, 1);
 
     // ---- step 1: A[p][j] on the fp16 matrix cores.  D (16 items x 16 pillars) = A (items x K) . B (K x pillars), K = 2 x 32
     // channels.  Lane (l15, q) holds channels 32h + 8q .. 32h + 8q + 7 of item / pillar l15 for both operands (the k index of
@@ -183,15 +171,15 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
                             if (16 * t + 4 * q + r >= n_items) c[r] = -INFINITY;
                     }
                     acc[vw][i] = c;
-                    lmax = vmaxr(vmaxr(lmax, vmaxr(c[0], c[1])), vmaxr(c[2], c[3]));
+                    lmax = hvpr_vmax_raw(hvpr_vmax_raw(lmax, hvpr_vmax_raw(c[0], c[1])), hvpr_vmax_raw(c[2], c[3]));
                 }
             }
             s_pm[(v * 4 + q) * kPmP + l15] = lmax;
         }
     }
-    RO_STAMP(2);
+    HVPR_STAMP(ts, 2);
     __syncthreads();
-    RO_STAMP(3);
+    HVPR_STAMP(ts, 3);
 
     // ---- step 2: wave w -> thresholds of its pillars w (, w + 8) ----
 #pragma unroll
@@ -206,14 +194,14 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
             if (!(wtop <= kHalfMax)) eps2 = INFINITY;
             if (!(eps2 < INFINITY) && lane == 0) s_flag[p] = 1;      // outside the fp16 range: no pre-filter for this pillar
             // tau <= k-th largest of the 64 lane maxima (its 16 leading bits): a lower bound of the k-th largest A
-            const float tau = ord_to_float(wave_kth_largest_hi16(ord_bits(s_pm[lane * kPmP + p]), k));
+            const float tau = hvpr_of_ord(wave_kth_largest_hi16(hvpr_ord_of(s_pm[lane * kPmP + p]), k));
             // tau = -inf or eps2 = inf / NaN let every live item through; the -inf padding past n_items never passes
             if (lane == 0) s_tau[p] = fmaxf(tau - eps2, -3.4028235e38f);
         }
     }
-    RO_STAMP(4);
+    HVPR_STAMP(ts, 4);
     __syncthreads();
-    RO_STAMP(5);
+    HVPR_STAMP(ts, 5);
 
     // ---- step 3: every wave: which of its values per lane reach the threshold of the lane's pillar ----
 #pragma unroll
@@ -245,9 +233,9 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
             }
         }
     }
-    RO_STAMP(6);
+    HVPR_STAMP(ts, 6);
     __syncthreads();
-    RO_STAMP(7);
+    HVPR_STAMP(ts, 7);
 
     // ---- step 4: the per-pillar step, ONE instruction stream for the wave's pillars (WAVES = 8: two pillars together) ----
     // Pillar slot h of the wave is pillar wid + WAVES h.  The candidates of both slots share the wave's 64 candidate lanes (slot 0's
@@ -291,13 +279,13 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
         const int kk = mine ? (hh == sa ? kk_a : kk_b) : 0;
         const int2 me = r < kk ? top[hh * 32 + r] : make_int2(0, 0);
         const float logit = r < kk ? __int_as_float(me.y) : -INFINITY;
-        const float mx = hvpr_reduce<32>(logit, op_maxr());
+        const float mx = hvpr_reduce<32>(logit, hvpr_op_max_raw());
         const float e = r < kk ? __expf(logit - mx) : 0.f;
         const float a = e / hvpr_reduce_sum<32>(e);
         if (mine) top[hh * 32 + r] = make_int2(me.x, __float_as_int(r < kk ? a : 0.f));
         if (topk_idx && r < kk) topk_idx[(size_t)(p0 + wid + WAVES * hh) * k + r] = me.x;
     };
-    RO_STAMP(8);
+    HVPR_STAMP(ts, 8);
 #pragma unroll 1
     for (int round = 0; round < PPW; ++round) {            // ONE copy of the body; the slot's values are picked by scalar selects
         if (joint && round == 1) break;
@@ -368,7 +356,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
         }
         // rank inside the pillar by (L desc, id asc): the number of its candidates that come before this one.  Every slot has
         // its own key list, zero beyond its end (zero is below every key): all lanes walk max(na, nb) entries, two per read
-        const unsigned long long key = ((unsigned long long)ord_bits(L) << 32) | (unsigned)(0xffffffffu - (unsigned)my_idx);
+        const unsigned long long key = ((unsigned long long)hvpr_ord_of(L) << 32) | (unsigned)(0xffffffffu - (unsigned)my_idx);
         unsigned long long *const kp = keys + 64 * (sa + ((both && second) ? 1 : 0));
         if (ln < tot) kp[ln - (second ? na : 0)] = key;
         int rank = 0;
@@ -416,20 +404,14 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
                     unsigned long long best = 0ull;
 #pragma unroll 4
                     for (int t = 0; t < kItemsPad / 64; ++t) {
-                        const unsigned long long c = ((unsigned long long)ord_bits(s_u.logit[64 * t + lane]) << 32) |
+                        const unsigned long long c = ((unsigned long long)hvpr_ord_of(s_u.logit[64 * t + lane]) << 32) |
                                                      (unsigned)(0xffffffffu - (unsigned)(lane + 64 * t));
                         if (c < prev && c > best && lane + 64 * t < n_items) best = c;
                     }
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) {
-                        const unsigned lo = __shfl_xor((unsigned)(best & 0xffffffffull), o, 64);
-                        const unsigned hi = __shfl_xor((unsigned)(best >> 32), o, 64);
-                        const unsigned long long ob = ((unsigned long long)hi << 32) | lo;
-                        best = ob > best ? ob : best;
-                    }
+                    HVPR_WAVE_MAX_XOR_U64(best);
                     if (lane == 0)
                         top[sa * 32 + r] = make_int2((int)(0xffffffffu - (unsigned)(best & 0xffffffffull)),
-                                                     __float_as_int(ord_to_float((unsigned)(best >> 32))));
+                                                     __float_as_int(hvpr_of_ord((unsigned)(best >> 32))));
                     prev = best;
                 }
                 softmax_ranks(false, sa, k, 0);
@@ -437,7 +419,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
             __syncthreads();                               // the buffer is free for the next such pillar
         }
     }
-    RO_STAMP(9);
+    HVPR_STAMP(ts, 9);
     // ---- weighted sum of the selected rows for all of the wave's slots at once, lane = (slot, channel pair), in rank order (a
     // fixed function of the pillar: not of its place in the wave or the batch); all loads in flight at once (ranks past k carry
     // item 0 with weight 0; rows past 16 / 24 are skipped as a block) ----
@@ -516,13 +498,11 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_memory_readout(const float *_
             if (canvas && cell >= 0) *(float2 *)(canvas + (size_t)cell * canvas_channels + canvas_offset + cp2) = make_float2(ox, oy);
         }
     }
-#ifdef HVPR_EXP_TIMING
-    RO_STAMP(10);
-    if ((blockIdx.x == 3 || blockIdx.x == 100) && lane == 0 && (wid & 7) == 0)
+    HVPR_STAMP(ts, 10);
+    HVPR_IF_TIMING(if ((blockIdx.x == 3 || blockIdx.x == 100) && lane == 0 && (wid & 7) == 0)
         printf("readout wg %d wave %d: features %lld | logits %lld | bar %lld | tau %lld | bar %lld | hits %lld | bar %lld | counts %lld (cands %d + %d%s) | "
                "rounds %lld | rows %lld cycles\n", (int)blockIdx.x, wid, ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3],
-               ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[7], cnt_s[0], cnt_s[1], joint ? " joint" : "", ts[9] - ts[8], ts[10] - ts[9]);
-#endif
+               ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[7], cnt_s[0], cnt_s[1], joint ? " joint" : "", ts[9] - ts[8], ts[10] - ts[9]);)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -681,7 +661,7 @@ __global__ void __launch_bounds__(1024) k_bank_wmax(const float *__restrict__ ba
 // wmax[64] = sum_c wmax[c], wmax[65] = max_c wmax[c]: the same for every pillar, so not the read-out's work
 __global__ void __launch_bounds__(64) k_wmax_stats(float *__restrict__ wmax) {
     const float wm = wmax[threadIdx.x];
-    const float wsum = hvpr_reduce_sum<64>(wm), wtop = hvpr_reduce<64>(wm, op_maxr());
+    const float wsum = hvpr_reduce_sum<64>(wm), wtop = hvpr_reduce<64>(wm, hvpr_op_max_raw());
     if (threadIdx.x == 0) { wmax[kC] = wsum; wmax[kC + 1] = wtop; }
 }
 

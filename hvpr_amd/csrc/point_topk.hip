@@ -33,7 +33,7 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
 
 // keep the entries with A >= thr, compacted to the front (one wave; entries e0 = cand[lane], e1 = cand[64 + lane])
 __device__ __forceinline__ int prune(unsigned long long *cand, int lcnt, float thr, int lane) {
-    const unsigned tb = ord_bits(thr);
+    const unsigned tb = hvpr_ord_of(thr);
     const unsigned long long e0 = lane < lcnt ? cand[lane] : 0ull, e1 = 64 + lane < lcnt ? cand[64 + lane] : 0ull;
     const bool k0 = lane < lcnt && tb <= (unsigned)(e0 >> 32), k1 = 64 + lane < lcnt && tb <= (unsigned)(e1 >> 32);
     const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1);
@@ -67,8 +67,8 @@ __device__ __forceinline__ void commit(const float *__restrict__ items, float fc
             if ((lane >> 5) == (part & 1)) { if (part < 2) L0 = s; else L1 = s; }
         }
     }
-    const unsigned long long key0 = lane < cnt ? (((unsigned long long)ord_bits(L0) << 32) | (unsigned)(0xffffffffu - (unsigned)i0)) : 0ull;
-    const unsigned long long key1 = 64 + lane < cnt ? (((unsigned long long)ord_bits(L1) << 32) | (unsigned)(0xffffffffu - (unsigned)i1)) : 0ull;
+    const unsigned long long key0 = lane < cnt ? (((unsigned long long)hvpr_ord_of(L0) << 32) | (unsigned)(0xffffffffu - (unsigned)i0)) : 0ull;
+    const unsigned long long key1 = 64 + lane < cnt ? (((unsigned long long)hvpr_ord_of(L1) << 32) | (unsigned)(0xffffffffu - (unsigned)i1)) : 0ull;
     const int total = min(cnt, 64) + max(cnt - 64, 0) + __popcll(__ballot(ck != 0ull));
     const int kk = min(k, total);
     unsigned long long kth = 0ull;
@@ -98,7 +98,7 @@ __device__ __forceinline__ void commit(const float *__restrict__ items, float fc
     __builtin_amdgcn_wave_barrier();
     ck = lane < kk ? cand[lane] : 0ull;
     __builtin_amdgcn_wave_barrier();
-    if (kk == k) Lk = ord_to_float((unsigned)(readlane_u64(ck, k - 1) >> 32));
+    if (kk == k) Lk = hvpr_of_ord((unsigned)(readlane_u64(ck, k - 1) >> 32));
 }
 
 __global__ void __launch_bounds__(kThreads) k_point_topk(const float *__restrict__ f, int M, const float *__restrict__ items,
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(kThreads) k_point_topk(const float *__restrict
             unsigned hits = 0u;
             float thr = -3.4028235e38f;
             if (!unfiltered) {
-                const float tau = ord_to_float(wave_kth_largest_hi16(ord_bits(lmax), k));     // NaN when the block has < k live lanes
+                const float tau = hvpr_of_ord(wave_kth_largest_hi16(hvpr_ord_of(lmax), k));     // NaN when the block has < k live lanes
                 T = fmaxf(T, tau);                                                            // fmaxf drops a NaN
                 thr = fmaxf(fmaxf(T - eps2, Lk - 0.5f * eps2), -3.4028235e38f);
 #pragma unroll
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(kThreads) k_point_topk(const float *__restrict
                 const int t = has ? __ffs((int)left) - 1 : 0;
                 left &= left - 1u;
                 if (has) cand[lcnt + __popcll(m & ((1ull << lane) - 1ull))] =
-                    ((unsigned long long)ord_bits(row[lane + 64 * t]) << 32) | (unsigned)(blk * kBlk + lane + 64 * t);
+                    ((unsigned long long)hvpr_ord_of(row[lane + 64 * t]) << 32) | (unsigned)(blk * kBlk + lane + 64 * t);
                 lcnt += __popcll(m);
             }
         }

@@ -13,8 +13,9 @@ namespace {
 // `npoint` dependent steps is: update with the last pick, thread-local arg-max, wave arg-max, 16-wave arg-max through LDS.
 constexpr int FPS_THREADS = 1024;
 
+// d >= 0 (a distance, or the padding's -1 that never gets here), where the raw bits already order like hvpr_ord_of (wave.h)
 __device__ __forceinline__ unsigned long long fps_key(float d, int idx) {
-    return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(0xffffffffu - (unsigned)idx);   // d >= 0
+    return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(0xffffffffu - (unsigned)idx);
 }
 
 template <int PPT>
@@ -47,13 +48,7 @@ __global__ void __launch_bounds__(FPS_THREADS) k_fps(const float *__restrict__ x
                 best = key > best ? key : best;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned lo = __shfl_xor((unsigned)(best & 0xffffffffull), o, 64);
-            const unsigned hi = __shfl_xor((unsigned)(best >> 32), o, 64);
-            const unsigned long long ob = ((unsigned long long)hi << 32) | lo;
-            best = ob > best ? ob : best;
-        }
+        HVPR_WAVE_MAX_XOR_U64(best);
         const int buf = j & 1;
         if (lane == 0) s_best[buf][wid] = best;
         __syncthreads();

@@ -114,14 +114,16 @@ __global__ void __launch_bounds__(256) k_head_decode(const float *__restrict__ h
 }
 
 // ------------------------------------------------------------------------------------------------ score filter + top-k
-// -0.0 takes the key of +0.0: the two compare equal, so they tie and the lower id goes first
-__device__ __forceinline__ unsigned ord_bits(float v) {
-    const unsigned b = __float_as_uint(v) == 0x80000000u ? 0u : __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+// The score top-k's ordered key.  -0.0 takes the key of +0.0 here, and only here: this top-k orders EQUAL scores by ascending id, the
+// two zeros compare equal, and hvpr_ord_of alone would put every +0.0 in front of every -0.0.  (The other users of hvpr_ord_of
+// compare keys with keys and read the value back with its sign: wave.h.)  tools/check_wave_host.cpp compiles the lines between the
+// two marks for the host.
+// [topk_ord]
+HVPR_WAVE_HD unsigned topk_ord(float v) {
+    const unsigned b = __builtin_bit_cast(unsigned, v);
+    return hvpr_ord_of_bits(b == 0x80000000u ? 0u : b);
 }
-__device__ __forceinline__ float unord_bits(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
+// [/topk_ord]
 
 // key = (orderable score bits << 32) | ~id : descending key order = descending score, ascending id
 __global__ void __launch_bounds__(256) k_score_compact(const float *__restrict__ scores, int A, float thresh, int use_thresh,
@@ -134,7 +136,7 @@ __global__ void __launch_bounds__(256) k_score_compact(const float *__restrict__
         const bool pass = use_thresh ? (v >= thresh) : !(v != v);
         if (pass) {
             const int pos = atomicAdd(&counts[n], 1);   // the compiler folds this into one atomic per wave
-            k[pos] = ((unsigned long long)ord_bits(v) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+            k[pos] = ((unsigned long long)topk_ord(v) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
         }
     }
 }
@@ -150,7 +152,7 @@ __global__ void __launch_bounds__(256) k_score_hist(const float *__restrict__ sc
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < A; i += gridDim.x * blockDim.x) {
         const float v = s[i];
         const bool pass = use_thresh ? (v >= thresh) : !(v != v);
-        if (pass) atomicAdd(&h[ord_bits(v) >> 16], 1u);
+        if (pass) atomicAdd(&h[topk_ord(v) >> 16], 1u);
     }
 }
 
@@ -230,10 +232,10 @@ __global__ void __launch_bounds__(256) k_score_compact_bin(const float *__restri
     const unsigned tb = tbin[n];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < A; i += gridDim.x * blockDim.x) {
         const float v = s[i];
-        const bool pass = (use_thresh ? (v >= thresh) : !(v != v)) && (ord_bits(v) >> 16) >= tb;
+        const bool pass = (use_thresh ? (v >= thresh) : !(v != v)) && (topk_ord(v) >> 16) >= tb;
         if (pass) {
             const int pos = atomicAdd(&counts[n], 1);
-            k[pos] = ((unsigned long long)ord_bits(v) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+            k[pos] = ((unsigned long long)topk_ord(v) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
         }
     }
 }
@@ -325,7 +327,7 @@ __global__ void __launch_bounds__(TK_THREADS) k_topk_select(const unsigned long 
     for (int i = threadIdx.x; i < take; i += TK_THREADS) {
         const unsigned long long v = s_keys[i];
         order[(size_t)n * pre_max + i] = (int)(0xffffffffu - (unsigned)(v & 0xffffffffull));
-        if (sorted_scores) sorted_scores[(size_t)n * pre_max + i] = unord_bits((unsigned)(v >> 32));
+        if (sorted_scores) sorted_scores[(size_t)n * pre_max + i] = hvpr_of_ord((unsigned)(v >> 32));
     }
     if (threadIdx.x == 0) {
         out_counts[n] = take;
@@ -369,7 +371,7 @@ __global__ void __launch_bounds__(256) k_rank_place(const unsigned long long *__
     if ((int)r < min(cnt, pre_max)) {
         const unsigned long long v = keys[(size_t)n * A + i];
         order[(size_t)n * pre_max + r] = (int)(0xffffffffu - (unsigned)(v & 0xffffffffull));
-        if (sorted_scores) sorted_scores[(size_t)n * pre_max + r] = unord_bits((unsigned)(v >> 32));
+        if (sorted_scores) sorted_scores[(size_t)n * pre_max + r] = hvpr_of_ord((unsigned)(v >> 32));
     }
 }
 

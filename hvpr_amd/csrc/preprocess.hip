@@ -48,8 +48,7 @@ __global__ void __launch_bounds__(kThreads) k_tile_counts(const unsigned char *_
     int c = 0;
 #pragma unroll
     for (int k = 0; k < kItems; ++k) c += (base + k < n && flags[base + k]) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    HVPR_WAVE_SUM_XOR(c);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) tile_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -64,8 +63,7 @@ __global__ void __launch_bounds__(kThreads) k_compact_rows(const float *__restri
     // exclusive prefix of the tile counts in front of this tile (a few hundred words at most)
     int part = 0;
     for (int t = threadIdx.x; t < blockIdx.x; t += kThreads) part += tile_count[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    HVPR_WAVE_SUM_XOR(part);
     if (lane == 0) s_w[wid] = part;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -77,9 +75,7 @@ __global__ void __launch_bounds__(kThreads) k_compact_rows(const float *__restri
     int f[kItems], c = 0;
 #pragma unroll
     for (int k = 0; k < kItems; ++k) { f[k] = (base + k < n && flags[base + k]) ? 1 : 0; c += f[k]; }
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+    const int inc = hvpr_wave_scan_incl(c);
     __syncthreads();
     if (lane == 63) s_w[wid] = inc;
     __syncthreads();

@@ -98,45 +98,6 @@ struct Wreg {
     float b1c, z0c;               // lane = channel constants of the two LDS loops
 };
 
-// lane ^ j exchanges without the LDS crossbar (common.h, select.h use the same ones)
-__device__ __forceinline__ unsigned xchg(unsigned v, int j) {
-    const int iv = (int)v;
-    if (j == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, iv, 0xB1, 0xf, 0xf, true);
-    if (j == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, iv, 0x4E, 0xf, 0xf, true);
-    if (j == 4) {
-        int r = __builtin_amdgcn_update_dpp(0, iv, 0x104, 0xf, 0x5, false);
-        return (unsigned)__builtin_amdgcn_update_dpp(r, iv, 0x114, 0xf, 0xa, false);
-    }
-    if (j == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, iv, 0x128, 0xf, 0xf, true);
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);   // j == 16
-    return (threadIdx.x & 16) ? r[0] : r[1];
-}
-// ascending sort of one key per column inside each 32-lane half
-__device__ __forceinline__ unsigned bitonic32_asc(unsigned v, int col) {
-#pragma unroll
-    for (int k = 2; k <= 32; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const unsigned o = xchg(v, j);
-            const bool up = (col & k) == 0;
-            const bool lower = (col & j) == 0;
-            v = (lower == up) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
-}
-__device__ __forceinline__ int bitonic_asc(int v, int lane, int width) {
-    for (int k = 2; k <= width; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j, 64);
-            const bool up = (lane & k) == 0;
-            const bool lower = (lane & j) == 0;
-            v = (lower == up) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
-}
-
 __device__ __forceinline__ f32x16 zero16() { return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
 __device__ __forceinline__ unsigned uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 
@@ -191,22 +152,6 @@ __device__ __forceinline__ void load_weights(const VfeParams &v, float *stage, f
     zt[96 + lane] = -INFINITY;
 }
 
-#ifdef HVPR_EXP_TIMING
-#define VFE_STAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); tstamp[i] = __builtin_readcyclecounter(); } while (0)
-#define VFE_TARG , long long *tstamp
-#define VFE_TPASS , tstamp
-#else
-#define VFE_STAMP(i)
-#define VFE_TARG
-#define VFE_TPASS
-#endif
-
-// v_max_f32 as is: fmaxf() first quiets both operands (two more instructions per max under the IEEE mode bit)
-__device__ __forceinline__ float vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // lane i <- lane i - D of the same 16-lane row (row_shr), ANDed with a per-lane mask; lanes without a source get 0
 template <int D>
 __device__ __forceinline__ float row_up_and(float x, int mask) {
@@ -248,9 +193,10 @@ __device__ __forceinline__ double to_grid(float v, int k) { return trunc(ldexp((
 template <bool GATHER>
 __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float *zt, const VfeParams &v, float4 pt, bool live, bool inmax,
                                          bool proc, bool hz, int n, int seg0, int4 cd, int row, int cell, unsigned endmask,
-                                         unsigned startsproc, float *spatial, int spatial_channels, float *spatial_scale VFE_TARG) {
+                                         unsigned startsproc, float *spatial, int spatial_channels, float *spatial_scale
+                                         HVPR_IF_TIMING(, long long *tstamp)) {
     const int lane = threadIdx.x & 63, h = lane >> 5, col = lane & 31;
-    VFE_STAMP(3);
+    HVPR_STAMP(tstamp, 3);
     endmask = uni(endmask); startsproc = uni(startsproc);
     const int q = proc ? __popc(startsproc & (0xffffffffu >> (31 - col))) - 1 : 0;   // pillar of this column inside the pass
     const bool isend = (endmask >> col) & 1u;
@@ -284,7 +230,7 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
         *(float4 *)&L.s[512 + q * 8] = make_float4(fn, nrm, mx, my);
         *(float4 *)&L.s[512 + q * 8 + 4] = make_float4(mz, 0.f, __int_as_float(row), __int_as_float(cell));
     }
-    VFE_STAMP(4);
+    HVPR_STAMP(tstamp, 4);
 
     // ---- layer 0: (16 x 10) . (10 x 32 points) ---------------------------------------------------------------------------
     f32x16 acc0 = zero16();
@@ -305,7 +251,7 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
 #pragma unroll
         for (int t = 0; t < 8; ++t) acca[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(W.aw[mb][t], y0[t], acca[mb], 0, 0, 0);
     }
-    VFE_STAMP(5);
+    HVPR_STAMP(tstamp, 5);
 
     // ---- x_max per pillar: segmented inclusive max-scan along the columns (DPP inside the 16-lane rows + one carry across the
     // row border); the pillar's last column ends up with the max over the pillar and leaves it as row q of the pillar table
@@ -316,19 +262,19 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             float x = fand(y0[r], im);
-            x = vmax(x, row_up_and<1>(x, g1));
-            x = vmax(x, row_up_and<2>(x, g2));
-            x = vmax(x, row_up_and<4>(x, g4));
-            x = vmax(x, row_up_and<8>(x, g8));
-            x = vmax(x, row_carry_and(x, gx));
-            xr[r] = vmax(x, fand(fmaxf(0.f + W.b0h[r], 0.f), hm));   // the padded slot's layer-0 output
+            x = hvpr_vmax_raw(x, row_up_and<1>(x, g1));
+            x = hvpr_vmax_raw(x, row_up_and<2>(x, g2));
+            x = hvpr_vmax_raw(x, row_up_and<4>(x, g4));
+            x = hvpr_vmax_raw(x, row_up_and<8>(x, g8));
+            x = hvpr_vmax_raw(x, row_carry_and(x, gx));
+            xr[r] = hvpr_vmax_raw(x, fand(fmaxf(0.f + W.b0h[r], 0.f), hm));   // the padded slot's layer-0 output
         }
         if (isend && proc) {   // lane (col, h) holds channels 4 h .. 4 h + 3 and 8 + 4 h .. 8 + 4 h + 3
             *(float4 *)&L.s[q * 16 + 4 * h] = make_float4(xr[0], xr[1], xr[2], xr[3]);
             *(float4 *)&L.s[q * 16 + 8 + 4 * h] = make_float4(xr[4], xr[5], xr[6], xr[7]);
         }
     }
-    VFE_STAMP(6);
+    HVPR_STAMP(tstamp, 6);
 
     // ---- per-pillar matrix products, pillars as columns: C = W1b . x_max, and the scale stream ---------------------------
     {
@@ -381,7 +327,7 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
             }
         }
     }
-    VFE_STAMP(7);
+    HVPR_STAMP(tstamp, 7);
 
     // ---- per point: floor by the padded slot's column (at ONE column of the pillar: the max over the pillar sees it), add
     // the pillar's constant; rows back to LDS.  Columns outside the maxes read a row of -inf as their constant
@@ -404,14 +350,14 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float4 o;
-                o.x = vmax(acca[mb][4 * g], zv[mb][g].x) + cv[mb][g].x;
-                o.y = vmax(acca[mb][4 * g + 1], zv[mb][g].y) + cv[mb][g].y;
-                o.z = vmax(acca[mb][4 * g + 2], zv[mb][g].z) + cv[mb][g].z;
-                o.w = vmax(acca[mb][4 * g + 3], zv[mb][g].w) + cv[mb][g].w;
+                o.x = hvpr_vmax_raw(acca[mb][4 * g], zv[mb][g].x) + cv[mb][g].x;
+                o.y = hvpr_vmax_raw(acca[mb][4 * g + 1], zv[mb][g].y) + cv[mb][g].y;
+                o.z = hvpr_vmax_raw(acca[mb][4 * g + 2], zv[mb][g].z) + cv[mb][g].z;
+                o.w = hvpr_vmax_raw(acca[mb][4 * g + 3], zv[mb][g].w) + cv[mb][g].w;
                 *(float4 *)&L.a[col * kPA + 32 * mb + 8 * g + 4 * h] = o;
             }
     }
-    VFE_STAMP(8);
+    HVPR_STAMP(tstamp, 8);
 
     // ---- max over each pillar's points, bias, ReLU: lane = channel, one coalesced row per pillar --------------------------
     {
@@ -421,7 +367,7 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
         float m = ninf;
 #pragma unroll
         for (int c = 0; c < 32; ++c) {
-            m = vmax(m, av[c]);
+            m = hvpr_vmax_raw(m, av[c]);
             if ((endmask >> c) & 1u) {
                 const float o = fmaxf(m + W.b1c, 0.f);
                 const int r = __builtin_amdgcn_readlane(row, c);
@@ -431,37 +377,27 @@ __device__ __forceinline__ void vfe_pass(const Wreg &W, WaveLds &L, const float 
             }
         }
     }
-    VFE_STAMP(9);
+    HVPR_STAMP(tstamp, 9);
 }
 
 __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, GatherSrc g) {
     const int fill_blocks = (int)gridDim.x - g.work_blocks;   // dispatched first: they are the bandwidth work
     if ((int)blockIdx.x < fill_blocks) {
-#ifdef HVPR_EXP_TIMING
-        const long long f0 = __builtin_amdgcn_s_memrealtime();
-#endif
+        HVPR_IF_TIMING(const long long f0 = __builtin_amdgcn_s_memrealtime();)
         hvpr_canvas_clear(g.clear, blockIdx.x, fill_blocks);
-#ifdef HVPR_EXP_TIMING
-        if ((blockIdx.x == 0 || blockIdx.x == fill_blocks - 1 || blockIdx.x == fill_blocks / 2) && threadIdx.x == 0)
-            printf("vfe-abs fill blk %d: %lld .. %lld (x10 ns)\n", (int)blockIdx.x, f0, (long long)__builtin_amdgcn_s_memrealtime());
-#endif
+        HVPR_IF_TIMING(if ((blockIdx.x == 0 || blockIdx.x == fill_blocks - 1 || blockIdx.x == fill_blocks / 2) && threadIdx.x == 0)
+            printf("vfe-abs fill blk %d: %lld .. %lld (x10 ns)\n", (int)blockIdx.x, f0, (long long)__builtin_amdgcn_s_memrealtime());)
         return;
     }
-#ifdef HVPR_EXP_TIMING
-    const long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    HVPR_IF_TIMING(const long long rt0 = __builtin_amdgcn_s_memrealtime();)
     __shared__ __attribute__((aligned(16))) WaveLds s_wave[4];
     __shared__ __attribute__((aligned(16))) float s_stage[C1 * 36 + CS1 * 20 + C0 * CIN];
     __shared__ __attribute__((aligned(16))) float s_zt[4][160];
     __shared__ int s_sel[4][32];
     __shared__ __attribute__((aligned(16))) float4 s_selp[4][32];
     __shared__ int s_voff[kMaxB + 1], s_fbase[kMaxB + 1], s_cut[kMaxB];
-#ifdef HVPR_EXP_TIMING
-    long long tstamp[10];
-    tstamp[0] = __builtin_readcyclecounter();
-    int t_passes = 0;
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_front0 = 0, t_win = 0, t_winacc = 0;
-#endif
+    HVPR_IF_TIMING(long long tstamp[10]; tstamp[0] = __builtin_readcyclecounter(); int t_passes = 0;)
+    HVPR_IF_TIMING(long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_front0 = 0, t_win = 0, t_winacc = 0;)
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, col = lane & 31;
     // One frame is a single round of windows with most SIMDs idle, and the launch lasts as long as its slowest wave: a wave
     // whose window needs a second pass (a voxel with more points than slots, a pillar that did not fit) takes twice as long as
@@ -503,7 +439,7 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
     Wreg W;
     load_weights(v, s_stage, s_zt[wid], W, g.w.vfe_aux);   // a barrier inside: the frame tables are visible afterwards
     WaveLds &L = s_wave[wid];
-    VFE_STAMP(1);
+    HVPR_STAMP(tstamp, 1);
     const int cells_per_frame = g.nx * g.ny;
     const unsigned idxmask = (1u << g.idx_bits) - 1u;
 
@@ -524,14 +460,9 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
         unsigned long long todo = __ballot(flag && lane <= kWin && rec.y >= 0);
 
         bool first = true;
-#ifdef HVPR_EXP_TIMING
-        t_win = __builtin_readcyclecounter();
-#endif
+        HVPR_IF_TIMING(t_win = __builtin_readcyclecounter();)
         while (todo != 0ull) {
-#ifdef HVPR_EXP_TIMING
-            t_front0 = __builtin_readcyclecounter();
-            t_winacc += t_front0 - t_win;
-#endif
+            HVPR_IF_TIMING(t_front0 = __builtin_readcyclecounter(); t_winacc += t_front0 - t_win;)
             const bool mine = !g.split || (first ? role == 0 : role == 1);
             if (g.split && role == 0 && !first) break;
             first = false;
@@ -600,7 +531,7 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
                     vsel = slot < P ? ((volatile int *)s_sel[wid])[slot] : kIdle;
                     int at = slot;
                     if (g.voxels_out) {       // the optional `voxels` output lists the points by ascending index
-                        const int key = bitonic_asc(vsel == kIdle ? kIdle : (vsel << 5) | slot, slot, 32);
+                        const int key = hvpr_bitonic_asc(vsel == kIdle ? kIdle : (vsel << 5) | slot, slot, 32);
                         vsel = key == kIdle ? kIdle : key >> 5;
                         at = key & 31;
                     }
@@ -612,14 +543,14 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
                 } else {
                     // very dense cell: 64-lane bitonic selection with chunked merging, then the points from the point array
                     int u = lane < cnt ? g.w.arena_rec[a0 + lane].x : kIdle;
-                    u = bitonic_asc(u, lane, 64);
+                    u = hvpr_bitonic_asc(u, lane, 64);
                     const int chunk = 64 - P;
                     for (int done = 64; done < cnt; done += chunk) {
                         if (lane >= P) {
                             const int j = done + (lane - P);
                             u = j < cnt ? g.w.arena_rec[a0 + j].x : kIdle;
                         }
-                        u = bitonic_asc(u, lane, 64);
+                        u = hvpr_bitonic_asc(u, lane, 64);
                     }
                     vsel = __shfl(u, slot, 64);       // ascending
                     if (slot < P && vsel != kIdle) {
@@ -673,7 +604,7 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
                         if (proc) from = 2 * seg0 + cn - 1 - col;
                     } else {
                         unsigned key = ((unsigned)seg0 << (g.idx_bits + 5)) | (((unsigned)idx0 & idxmask) << 5) | (unsigned)col;
-                        key = bitonic32_asc(key, col);
+                        key = hvpr_bitonic32_asc_dpp(key, col);
                         from = (int)(key & 31u);
                     }
                 }
@@ -712,35 +643,23 @@ __global__ void __launch_bounds__(256, 2) k_vfe_gather(int P, VfeParams v, Gathe
                     }
                 }
             }
-#ifdef HVPR_EXP_TIMING
-            t_passes++;
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            tstamp[2] = __builtin_readcyclecounter();
-            tacc[0] += tstamp[2] - t_front0;
-#endif
+            HVPR_IF_TIMING(t_passes++;)
+            HVPR_STAMP(tstamp, 2);
+            HVPR_IF_TIMING(tacc[0] += tstamp[2] - t_front0;)
             vfe_pass<true>(W, L, s_zt[wid], v, pt, live, live, proc, proc && n < P, n, seg0, cd, row, cell, endmask, startsproc, g.spatial,
-                           g.spatial_channels, g.spatial_scale VFE_TPASS);
-#ifdef HVPR_EXP_TIMING
-            for (int q = 0; q < 7; ++q) tacc[1 + q] += tstamp[3 + q] - tstamp[2 + q];
-            t_win = __builtin_readcyclecounter();
-#endif
-#ifdef HVPR_EXP_TIMING
-            if (false)
-                printf("vfe wg %d pass %d (pillars %d): prologue %lld | to first pass %lld | front %lld | decor %lld | l0+a %lld | xmax %lld | "
-                       "pillar mfma %lld | combine %lld | final %lld cycles\n", (int)blockIdx.x - fill_blocks, t_passes, __popc(endmask),
-                       tstamp[1] - tstamp[0], tstamp[2] - tstamp[1], tstamp[3] - tstamp[2], tstamp[4] - tstamp[3], tstamp[5] - tstamp[4],
-                       tstamp[6] - tstamp[5], tstamp[7] - tstamp[6], tstamp[8] - tstamp[7], tstamp[9] - tstamp[8]);
-#endif
+                           g.spatial_channels, g.spatial_scale HVPR_IF_TIMING(, tstamp));
+            HVPR_IF_TIMING(for (int q = 0; q < 7; ++q) tacc[1 + q] += tstamp[3 + q] - tstamp[2 + q];)
+            HVPR_IF_TIMING(t_win = __builtin_readcyclecounter();)
         }
         rec = rec_next;
         apt = apt_next;
     }
-#ifdef HVPR_EXP_TIMING
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if ((wblk % 37) == 0 && threadIdx.x == 0)
-        printf("vfe-abs work blk %d role %d passes %d: %lld x10 ns, prologue %lld | sums over passes: between passes %lld front %lld | s23 %lld s34 %lld s45 %lld s56 %lld s67 %lld s78 %lld s89 %lld cycles\n", wblk, role, t_passes,
-               (long long)__builtin_amdgcn_s_memrealtime() - rt0, tstamp[1] - tstamp[0], t_winacc, tacc[0], tacc[1], tacc[2], tacc[3], tacc[4], tacc[5], tacc[6], tacc[7]);
-#endif
+    HVPR_IF_TIMING(asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");)
+    HVPR_IF_TIMING(if ((wblk % 37) == 0 && threadIdx.x == 0)
+        printf("vfe-abs work blk %d role %d passes %d: %lld x10 ns, prologue %lld | sums over passes: between passes %lld front %lld | "
+               "s23 %lld s34 %lld s45 %lld s56 %lld s67 %lld s78 %lld s89 %lld cycles\n", wblk, role, t_passes,
+               (long long)__builtin_amdgcn_s_memrealtime() - rt0, tstamp[1] - tstamp[0], t_winacc, tacc[0], tacc[1], tacc[2], tacc[3], tacc[4],
+               tacc[5], tacc[6], tacc[7]);)
 }
 
 // separate-call form: padded voxels in, one pillar per pass
@@ -767,11 +686,9 @@ __global__ void __launch_bounds__(256, 2) k_vfe_rows(const float4 *__restrict__ 
         if (v.pillar_mask && lane < P) v.pillar_mask[(size_t)p * P + lane] = live ? 1.f : 0.f;
         const unsigned endmask = 1u << (n > 0 ? n - 1 : 0);
         // a pillar without points still has its padded slots: column 0 stands in for them
-#ifdef HVPR_EXP_TIMING
-        long long tstamp[10];
-#endif
+        HVPR_IF_TIMING(long long tstamp[10];)
         vfe_pass<false>(W, L, s_zt[wid], v, pt, live, live || (n == 0 && col == 0), true, n < P, n, 0, cd, p, 0, endmask, 1u,
-                        nullptr, 0, nullptr VFE_TPASS);
+                        nullptr, 0, nullptr HVPR_IF_TIMING(, tstamp));
     }
 }
 

@@ -21,28 +21,6 @@
 
 namespace {
 
-__device__ __forceinline__ int frame_of(const int *__restrict__ off, int batch, int i) {
-    // largest b in [0,batch) with off[b] <= i
-    int lo = 0, hi = batch;   // invariant: off[lo] <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Inclusive add-scan over the 64 lanes on DPP moves (row_shr inside the 16-lane rows, row_bcast across them): ~10 instructions
-// per value instead of six ds_bpermute round trips.
-__device__ __forceinline__ unsigned wave_scan_incl(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);     // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);     // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);     // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);     // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);    // row_bcast:15 -> rows 1, 3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);    // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
 // A LiDAR sweep delivers the points of a cell in bursts, so consecutive lanes of a wave often hold the same cell — and atomics on
 // one word are performed one after the other (~12 ns each, the hottest cell's queue is what phase 1 waits for).  Runs of equal
 // cells inside the wave are folded first: the run's head (its lowest lane = its smallest point index) issues ONE atomicMin and
@@ -74,7 +52,7 @@ __device__ __forceinline__ int k1_cell(const float *__restrict__ pts, int i, int
     const float cz = floorf(__fdiv_rn(__fsub_rn(p[2], loz), vsz));
     int g = -1;
     if (cx >= 0.f && cx < (float)nx && cy >= 0.f && cy < (float)ny && cz >= 0.f && cz < (float)nz) {
-        const int b = frame_of(foff, batch, i);
+        const int b = hvpr_frame_of(foff, batch, i);
         g = ((b * nz + (int)cz) * ny + (int)cy) * nx + (int)cx;
     }
     w.pt_cell[i] = g;
@@ -143,11 +121,7 @@ __global__ void __launch_bounds__(kScanThreads) k2_scan(int n, const int *__rest
     // block exclusive scan of (ta, tb)
     unsigned ia = ta, ib = tb;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned ua = __shfl_up(ia, o, 64), ub = __shfl_up(ib, o, 64);
-        if (lane >= o) { ia += ua; ib += ub; }
-    }
+    HVPR_WAVE_SCAN_INCL2_SHFL(ia, ib, lane);
     if (lane == 63) { s_wave_a[wid] = ia; s_wave_b[wid] = ib; }
     __syncthreads();
     unsigned wa = 0, wb = 0, tot_a = 0, tot_b = 0;
@@ -177,8 +151,7 @@ __global__ void __launch_bounds__(kScanThreads) k2_scan(int n, const int *__rest
             const int stop = incl ? __ffsll((long long)incl) - 1 : 63;   // nearest predecessor with an inclusive prefix
             unsigned pa = (t >= 0 && lane <= stop) ? (unsigned)((st >> 31) & 0x7fffffffu) : 0u;
             unsigned pb = (t >= 0 && lane <= stop) ? (unsigned)(st & 0x7fffffffu) : 0u;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pb += __shfl_xor(pb, o, 64); }
+            HVPR_WAVE_SUM_XOR(pa, pb);
             ea += pa; eb += pb;
             if (incl) break;
         }
@@ -197,7 +170,7 @@ __global__ void __launch_bounds__(kScanThreads) k2_scan(int n, const int *__rest
         const int i = base + k;
         if (i < n) {
             // frame bases: the thread owning the first point of a frame knows that frame's first voxel rank
-            const int b = frame_of(foff, batch, i);
+            const int b = hvpr_frame_of(foff, batch, i);
             if (foff[b] == i)
                 for (int bb = b; bb >= 0 && foff[bb] == i; --bb) w.frame_base[bb] = (int)ra;
             if (fl[k]) {
@@ -344,12 +317,8 @@ __global__ void __launch_bounds__(T, T == 1024 ? 8 : 1) k_index(const float *__r
     __shared__ int s_local, s_abort;
     const int tile = blockIdx.x >> 3, i = tile * T + (int)threadIdx.x;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#ifdef HVPR_EXP_TIMING
-    long long ts[12];
-#define IDX_STAMP(k) ts[k] = __builtin_amdgcn_s_memrealtime()
-#else
-#define IDX_STAMP(k)
-#endif
+    HVPR_IF_TIMING(long long ts[12];)
+#define IDX_STAMP(k) HVPR_IF_TIMING(ts[k] = __builtin_amdgcn_s_memrealtime())   // the wall clock, no wait: not HVPR_STAMP
     IDX_STAMP(0);
     unsigned long long *const census = reinterpret_cast<unsigned long long *>(w.sync);   // sync[0..1]; sync[3]: exits; sync[4]: error; sync[8..71]: barrier 2's flags
     int *const err_word = w.sync + kSyncError;
@@ -369,7 +338,7 @@ __global__ void __launch_bounds__(T, T == 1024 ? 8 : 1) k_index(const float *__r
         const float cx = floorf(__fdiv_rn(__fsub_rn(pt.x, lox), vsx));
         const float cy = floorf(__fdiv_rn(__fsub_rn(pt.y, loy), vsy));
         const float cz = floorf(__fdiv_rn(__fsub_rn(pt.z, loz), vsz));
-        b = frame_of(foff, batch, i);
+        b = hvpr_frame_of(foff, batch, i);
         if (cx >= 0.f && cx < (float)nx && cy >= 0.f && cy < (float)ny && cz >= 0.f && cz < (float)nz) {
             g = ((b * nz + (int)cz) * ny + (int)cy) * nx + (int)cx;
         }
@@ -429,7 +398,7 @@ __global__ void __launch_bounds__(T, T == 1024 ? 8 : 1) k_index(const float *__r
         if (first == i) { fl = 1; ct = (unsigned)count; }
     }
     IDX_STAMP(5);
-    const unsigned ia = wave_scan_incl(fl), ib = wave_scan_incl(ct);
+    const unsigned ia = hvpr_wave_scan_incl(fl), ib = hvpr_wave_scan_incl(ct);
     if (lane == 63) { s_wave_a[wid] = ia; s_wave_b[wid] = ib; }
     __syncthreads();
     unsigned wa = 0, wb = 0, tot_a = 0, tot_b = 0;
@@ -458,8 +427,7 @@ __global__ void __launch_bounds__(T, T == 1024 ? 8 : 1) k_index(const float *__r
             const int stop = incl ? __ffsll((long long)incl) - 1 : 63;
             unsigned pa = (t >= 0 && lane <= stop) ? (unsigned)((st >> 31) & 0x7fffffffu) : 0u;
             unsigned pb = (t >= 0 && lane <= stop) ? (unsigned)(st & 0x7fffffffu) : 0u;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pb += __shfl_xor(pb, o, 64); }
+            HVPR_WAVE_SUM_XOR(pa, pb);
             ea += pa; eb += pb;
             if (incl) break;
         }
@@ -531,14 +499,12 @@ __global__ void __launch_bounds__(T, T == 1024 ? 8 : 1) k_index(const float *__r
         if (tile == 0 && (int)threadIdx.x <= batch) voxel_offsets[threadIdx.x] = 0;
     }
     IDX_STAMP(9);
-#ifdef HVPR_EXP_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    HVPR_IF_TIMING(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)
     IDX_STAMP(10);
-    if (threadIdx.x == 0 && (tile == 0 || tile == point_blocks - 1 || tile == point_blocks / 2))
+    HVPR_IF_TIMING(if (threadIdx.x == 0 && (tile == 0 || tile == point_blocks - 1 || tile == point_blocks / 2))
         printf("k_index tile %d local %d: start %lld | p1 issued +%lld | drained +%lld | sync +%lld | barrier1 +%lld | p2 loads +%lld | scan+lookback +%lld | "
                "stores drained +%lld | barrier2 +%lld | p3 issued +%lld | drained +%lld (x10 ns)\n", tile, (int)local, ts[0], ts[1] - ts[0], ts[2] - ts[1],
-               ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[7], ts[9] - ts[8], ts[10] - ts[9]);
-#endif
+               ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[8] - ts[7], ts[9] - ts[8], ts[10] - ts[9]);)
     // the last owner out returns the counters to idle (nobody is behind it: all have passed both barriers); device scope, so that
     // the next launch finds them whatever its placement
     // (an owner that gave up a wait comes through here as well: the words are idle again after ANY launch whose owners all ran)
@@ -594,7 +560,7 @@ __global__ void __launch_bounds__(256) k3_fill(int n, const int *__restrict__ fo
         pt = make_float4(src[0], src[1], src[2], src[3]);
     }
     const int r = w.cell_vid[g];
-    const int b = frame_of(foff, batch, i);
+    const int b = hvpr_frame_of(foff, batch, i);
     const int local = r - w.frame_base[b];
     // the point's slot in its voxel: handed out by K1 (k1_keys<true>: arrival numbers, counted from the top here like the atomicSub) or
     // taken now — which also returns the count map to its idle 0
@@ -611,20 +577,6 @@ __global__ void __launch_bounds__(256) k3_fill(int n, const int *__restrict__ fo
     } else if (local < max_voxels) {
         w.arena[pos] = i;
     }
-}
-
-__device__ __forceinline__ int bitonic64_asc(int v, int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j, 64);
-            const bool up = (lane & k) == 0;
-            const bool lower = (lane & j) == 0;
-            v = (lower == up) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
 }
 
 __global__ void __launch_bounds__(256) k4_gather(const float *__restrict__ pts, int stride, int xyz_col, int n_feat,
@@ -654,14 +606,14 @@ __global__ void __launch_bounds__(256) k4_gather(const float *__restrict__ pts, 
         const int a0 = rec.z;
         // the max_points smallest indices, ascending, in lanes [0, max_points)
         int v = lane < cnt ? w.arena[a0 + lane] : kIdle;
-        v = bitonic64_asc(v, lane);
+        v = hvpr_bitonic_asc(v, lane, 64);
         const int chunk = 64 - max_points;
         for (int done = 64; done < cnt; done += chunk) {
             if (lane >= max_points) {
                 const int j = done + (lane - max_points);
                 v = j < cnt ? w.arena[a0 + j] : kIdle;
             }
-            v = bitonic64_asc(v, lane);
+            v = hvpr_bitonic_asc(v, lane, 64);
         }
         const bool live = lane < max_points && v < cutoff;   // v == kIdle is never < cutoff
         const int num = __popcll(__ballot(live));

@@ -27,7 +27,7 @@ def car_boxes(rng, n, spread=40.0, clustered=True):
 
 
 def ord_bits(scores):
-    """ord_bits of the kernel: float32 -> uint32 whose unsigned order is the score order; -0.0 takes the key of +0.0."""
+    """topk_ord of the kernel (csrc/postprocess.hip): float32 -> uint32 whose unsigned order is the score order; -0.0 takes the key of +0.0."""
     b = np.asarray(scores, np.float32).view(np.uint32).copy()
     b[b == 0x80000000] = 0
     return np.where(b & 0x80000000, ~b, b | 0x80000000).astype(np.uint32)

@@ -211,9 +211,10 @@ def test_collision_kernel_against_the_restatement(bank, batched):
 
 
 # ------------------------------------------------------------------------------------------------ points
-def point_frames(bank, blk, seed=11):
+def point_frames(bank, blk, seed=11, wide=False):
     """Frames of 0, 1, blk - 1, blk, blk + 1 and 3 blk + 7 scene points; 0 or 20 accepted boxes; every point removed, none
-    removed, a mix; a frame whose output is candidate points only (no scene point at all)."""
+    removed, a mix; a frame whose output is candidate points only (no scene point at all).  wide: two frames of 40 blk + 3 and
+    30 blk + 1 points, a mix — 2 x 41 block counts, more than the 64 lanes of the scan's first wave."""
     r = np.random.RandomState(seed)
     boxes = AC.grid_boxes(20, x0=6.0, y0=-30.0)
     arena_off = bank.host_points()[1]
@@ -230,8 +231,11 @@ def point_frames(bank, blk, seed=11):
         p[:, 2] += 5.0
         return p
 
+    mix = lambda n: np.concatenate([inside(n // 2), outside(n - n // 2)])[r.permutation(n)]
     specs = [(0, True, None), (1, True, inside), (blk - 1, False, inside), (blk, True, outside), (blk + 1, True, inside),
-             (3 * blk + 7, True, lambda n: np.concatenate([inside(n // 2), outside(n - n // 2)])[r.permutation(n)])]
+             (3 * blk + 7, True, mix)]
+    if wide:
+        specs = [(40 * blk + 3, True, mix), (30 * blk + 1, True, mix)]
     frames = []
     for n, with_boxes, make in specs:
         pts = make(n).astype(np.float32) if n else np.zeros((0, 4), np.float32)
@@ -256,6 +260,23 @@ def test_point_kernels_against_the_restatement(bank, extra):
     kept = [len(w["kept"]) for w in w64]
     assert kept[1] == 0 and kept[2] == blk - 1 and kept[3] == blk and kept[4] == 0 and 0 < kept[5] < 3 * blk + 7     # all / none / some removed
     assert len(w64[0]["points"]) > 0 and len(frames[0]["points"]) == 0                                               # candidate points only
+    assert got["off"].tolist() == np.cumsum([0] + [len(w["points"]) for w in w64]).tolist()
+    check_against_restatement(frames, ops, bank, got, w32, w64)
+
+
+def test_point_kernels_with_block_counts_past_one_wave(bank):
+    """Two frames whose 2 x 41 per-block counts do not fit the first wave of k_points_scan's block scan: offsets, kept sets, order
+    and floats as in the restatement."""
+    from hvpr_amd import kernels
+    blk = kernels.augment_block_points()
+    frames = point_frames(bank, blk, seed=12, wide=True)
+    ops = [AC.OP_FLIP_X, AC.OP_ROTATE, AC.OP_SCALE]
+    for f in frames:
+        assert AC.margins_ok(f["points"], f["gt_boxes"], f["plan"], (0.0, 0.0, 0.0), np.zeros((0, 8)), RANGE)[0]
+    got = run_device(frames, ops, bank, remove_outside=False)
+    w32, w64 = restate(frames, ops, bank, remove_outside=False, dtype=np.float32), restate(frames, ops, bank, remove_outside=False)
+    kept = [len(w["kept"]) for w in w64]
+    assert 19 * blk < kept[0] < 21 * blk and 14 * blk < kept[1] < 16 * blk                # half of each frame removed
     assert got["off"].tolist() == np.cumsum([0] + [len(w["points"]) for w in w64]).tolist()
     check_against_restatement(frames, ops, bank, got, w32, w64)
 

@@ -32,10 +32,12 @@ def size_cases():
     rng = np.random.RandomState(5)
     return {"empty": [0], "one": [1], "tile": [T], "tile+1": [T + 1], "boundary_in_tile": [T - 1, 2],
             "boundaries_in_wave": [1, 1, 1, 0, 2], "leading_empty": [0, 0, 5], "multi_tile": [3 * T + 17, 0, T],
-            "64_frames": list(rng.randint(1, 4, size=64))}
+            "64_frames": list(rng.randint(1, 4, size=64)),
+            "tiles_past_a_wave": [40 * T + 3, 30 * T + 1]}      # 72 tile counts: the scan's second wave gets live pieces
 
 
-SIZE_NAMES = ["empty", "one", "tile", "tile+1", "boundary_in_tile", "boundaries_in_wave", "leading_empty", "multi_tile", "64_frames"]
+SIZE_NAMES = ["empty", "one", "tile", "tile+1", "boundary_in_tile", "boundaries_in_wave", "leading_empty", "multi_tile", "64_frames",
+              "tiles_past_a_wave"]
 
 
 def kitti_calib(b):
