@@ -389,6 +389,97 @@ class BaseBEVBackbone_Scale(nn.Module):
                 "out": mk(batch_size, hw[0][0] * us0, hw[0][1] * us0, self.num_bev_features)}
 
 
+class BaseBEVBackbone(nn.Module):
+    """Plain PointPillars' backbone — base_bev_backbone.py:6-113: per level a strided entry convolution and LAYER_NUMS[i] more, all
+    3x3 + BatchNorm + ReLU, then a ConvTranspose2d (kernel == stride) + BatchNorm + ReLU into the level's slice of the concat.
+
+    The eval forward is a plan over the same fp32 ops as BaseBEVBackbone_Scale's trunk and deconvolutions (_Level with no scale
+    stream, gate or SFM steps), built once per fold and run in line on the current stream: HVPR_BEV_STREAMS is not consulted, there
+    are no branches to overlap.  fp32 only.  Settings the ops do not take raise at construction."""
+
+    def __init__(self, model_cfg, input_channels):
+        super().__init__()
+        self.model_cfg = model_cfg
+        layer_nums, strides, filters = (list(model_cfg.get(k, None) or []) for k in ("LAYER_NUMS", "LAYER_STRIDES", "NUM_FILTERS"))
+        if not (len(layer_nums) == len(strides) == len(filters)) or not layer_nums:
+            raise ValueError("hvpr_amd: BaseBEVBackbone needs LAYER_NUMS, LAYER_STRIDES and NUM_FILTERS of one length >= 1")
+        up_strides = list(model_cfg.get("UPSAMPLE_STRIDES", None) or [])
+        up_filters = list(model_cfg.get("NUM_UPSAMPLE_FILTERS", None) or [])
+        if not up_strides:
+            raise ValueError("hvpr_amd: BaseBEVBackbone is built with UPSAMPLE_STRIDES (one deblock per level writes the concat)")
+        if len(up_strides) != len(up_filters):
+            raise ValueError("hvpr_amd: UPSAMPLE_STRIDES and NUM_UPSAMPLE_FILTERS differ in length")
+        if len(up_strides) > len(layer_nums):
+            raise ValueError("hvpr_amd: BaseBEVBackbone is built for one deblock per level (no extra final deblock)")
+        if len(up_strides) < len(layer_nums):
+            raise ValueError("hvpr_amd: BaseBEVBackbone needs an UPSAMPLE_STRIDES entry for every level")
+        for s in up_strides:
+            if s < 1 or int(s) != s:
+                raise ValueError(f"hvpr_amd: BaseBEVBackbone takes integer UPSAMPLE_STRIDES (ConvTranspose2d with kernel == stride), got {s}")
+        for s in strides:
+            if s not in (1, 2):
+                raise ValueError(f"hvpr_amd: BaseBEVBackbone takes LAYER_STRIDES of 1 or 2, got {s}")
+        precision = model_cfg.get("CONV_PRECISION", "fp32")
+        if precision != "fp32":
+            raise ValueError(f"hvpr_amd: BaseBEVBackbone runs the fp32 convolutions only, CONV_PRECISION is {precision!r}")
+        cin = [input_channels] + filters[:-1]
+        if any(c % 8 for c in cin + filters) or any(c % 4 for c in up_filters):
+            raise ValueError("hvpr_amd: the convolutions take input channels in multiples of 8 and output channels in multiples of 4 "
+                             f"(input {input_channels}, NUM_FILTERS {filters}, NUM_UPSAMPLE_FILTERS {up_filters})")
+        self.layer_strides, self.layer_nums = [int(s) for s in strides], [int(n) for n in layer_nums]
+        self.upsample_strides, self.up_filters = [int(s) for s in up_strides], [int(c) for c in up_filters]
+        self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList()
+        for i in range(len(layer_nums)):
+            layers = _conv_bn_relu(cin[i], filters[i], self.layer_strides[i], zero_pad=True)
+            for _ in range(self.layer_nums[i]):
+                layers += _conv_bn_relu(filters[i], filters[i])
+            self.blocks.append(nn.Sequential(*layers))
+            s = self.upsample_strides[i]
+            self.deblocks.append(nn.Sequential(nn.ConvTranspose2d(filters[i], up_filters[i], s, stride=s, bias=False),
+                                               nn.BatchNorm2d(up_filters[i], eps=1e-3, momentum=0.01), nn.ReLU()))
+        self.num_bev_features = sum(self.up_filters)
+        self._fold = FoldCache()
+
+    def train(self, mode=True):
+        self._fold.invalidate()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._fold.invalidate()
+        return super()._load_from_state_dict(*a, **k)
+
+    def _build_plan(self):
+        def conv(conv, bn, stride=1):
+            # stride-1 3x3 layers: Winograd F(2x2,3x3) kernel unless HVPR_CONV_ALGO=direct (kernels.pack_conv_auto)
+            return _fold_pack(kernels.pack_conv_auto, conv, bn, stride=stride, tile_cfg=_TILE_CFG, px_groups=_WINO_PX_GROUPS)
+
+        levels, coff = [], 0
+        for i, blk in enumerate(self.blocks):
+            trunk = [conv(blk[1], blk[2], stride=self.layer_strides[i])]
+            trunk += [conv(blk[4 + 3 * k], blk[5 + 3 * k]) for k in range(self.layer_nums[i])]
+            de = self.deblocks[i]
+            deconv = _fold_pack(kernels.pack_deconv, de[0], de[1], tile_cfg=_TILE_CFG)
+            levels.append(_Level(i, trunk, None, None, [], deconv, coff))
+            coff += self.up_filters[i]
+        return _Plan(levels, 0)
+
+    def forward(self, data_dict):
+        if self.training:
+            raise NotImplementedError("hvpr_amd: BaseBEVBackbone has no training forward (plain PointPillar is eval only; train MixAnchor_Memory)")
+        x = _nhwc(data_dict["spatial_features"])
+        plan = self._fold.get(x.device, self._build_plan)
+        B, H, W, _ = x.shape
+        s0, us0 = self.layer_strides[0], self.upsample_strides[0]
+        out = torch.empty((B, ((H + 2 - 3) // s0 + 1) * us0, ((W + 2 - 3) // s0 + 1) * us0, self.num_bev_features),
+                          dtype=torch.float32, device=x.device)
+        for lv in plan.levels:
+            x = _trunk(lv, x)
+            kernels.conv2d_nhwc(x, lv.deconv, out=out, out_coff=lv.coff, use_table=True)
+        data_dict["spatial_features_2d"] = out.permute(0, 3, 1, 2)   # (B, sum(NUM_UPSAMPLE_FILTERS), H, W), channels_last
+        return data_dict
+
+
 __all__ = {
     "BaseBEVBackbone_Scale": BaseBEVBackbone_Scale,
+    "BaseBEVBackbone": BaseBEVBackbone,
 }

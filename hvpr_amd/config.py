@@ -120,6 +120,11 @@ def hvpr_car_atss_cfg():
     return cfg_from_yaml_file(os.path.join(CFG_DIR, "kitti_models", "hvpr_car_atss.yaml"))
 
 
+def pointpillar_cfg():
+    """Plain PointPillars, KITTI 3-class, 432 x 496 pillars (eval only)."""
+    return cfg_from_yaml_file(os.path.join(CFG_DIR, "kitti_models", "pointpillar.yaml"))
+
+
 def hvpr_3class_cfg():
     """BASELINE.json configs[3]: Car / Pedestrian / Cyclist, 6 anchors per location."""
     return cfg_from_yaml_file(os.path.join(CFG_DIR, "kitti_models", "hvpr_3class.yaml"))

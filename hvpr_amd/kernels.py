@@ -84,6 +84,22 @@ def pillar_vfe_fwd(voxels, num_points, coords, folded, voxel_size, offsets, m_de
     return pf, sf, mask
 
 
+def pillar_vfe_plain_fwd(voxels, num_points, coords, w, b, voxel_size, offsets, m_device=None, want_mask=True):
+    """Plain PointPillars' one-layer pillar encoder (hvpr_pillar_vfe_plain_fwd_f32).  w (c_out, 10), b (c_out,): the folded
+    Linear + BatchNorm (f32 cuda), c_out in {32, 64, 128}.  Returns (pillar (M, c_out), mask (M, P, 1)|None)."""
+    M, P, C = voxels.shape
+    if C != 4:
+        raise ValueError("hvpr_pillar_vfe_plain_fwd_f32 is built for 4 raw point features")
+    if w.dim() != 2 or w.shape[1] != 10 or tuple(b.shape) != (w.shape[0],):
+        raise ValueError("hvpr_pillar_vfe_plain_fwd_f32 takes w (c_out, 10) and b (c_out,)")
+    dev = voxels.device
+    pf = torch.empty((M, w.shape[0]), dtype=torch.float32, device=dev)
+    mask = torch.empty((M, P, 1), dtype=torch.float32, device=dev) if want_mask else None
+    call("hvpr_pillar_vfe_plain_fwd_f32", voxels, num_points, coords, M, P, m_device, float(voxel_size[0]), float(voxel_size[1]),
+         float(voxel_size[2]), float(offsets[0]), float(offsets[1]), float(offsets[2]), w, b, int(w.shape[0]), pf, mask, _stream())
+    return pf, mask
+
+
 # ------------------------------------------------------------------------------------------------ memory + scatter
 class PackedBank:
     """Memory bank with its streaming copy for the read-out kernel (hvpr_memory_bank_pack_f32): IEEE fp16 tiles in the matrix-core

@@ -94,6 +94,60 @@ class PillarVFE_Scale(VFETemplate):
         return batch_dict
 
 
+class PillarVFE(VFETemplate):
+    """Plain PointPillars' pillar encoder — pillar_vfe.py:52-124: one PFN layer, no scale stream.  The eval forward is ONE launch
+    of hvpr_pillar_vfe_plain_fwd_f32 on the folded layer; settings the kernel is not built for raise at construction."""
+
+    WIDTHS = (32, 64, 128)
+
+    def __init__(self, model_cfg, num_point_features, voxel_size, point_cloud_range):
+        super().__init__(model_cfg=model_cfg)
+        self.num_filters = list(model_cfg.NUM_FILTERS)
+        if len(self.num_filters) != 1:
+            raise ValueError(f"hvpr_amd: PillarVFE is built for one PFN layer, NUM_FILTERS has {len(self.num_filters)} entries")
+        if self.num_filters[0] not in self.WIDTHS:
+            raise ValueError(f"hvpr_amd: PillarVFE is built for NUM_FILTERS [32], [64] or [128], got {self.num_filters}")
+        if not model_cfg.USE_NORM:
+            raise ValueError("hvpr_amd: PillarVFE is built for USE_NORM: True (the kernel takes the folded BatchNorm)")
+        if model_cfg.WITH_DISTANCE:
+            raise ValueError("hvpr_amd: PillarVFE is built for WITH_DISTANCE: False (ten features per point)")
+        if not model_cfg.USE_ABSLOTE_XYZ:
+            raise ValueError("hvpr_amd: PillarVFE is built for USE_ABSLOTE_XYZ: True (ten features per point)")
+        if num_point_features != 4:
+            raise ValueError(f"hvpr_amd: PillarVFE is built for 4 raw point features, got {num_point_features}")
+        self.pfn_layers = nn.ModuleList([PFNLayer(num_point_features + 6, self.num_filters[0], True, last_layer=True)])
+        self.voxel_size = [float(v) for v in voxel_size]
+        self.offsets = [self.voxel_size[i] / 2 + float(point_cloud_range[i]) for i in range(3)]
+        self._fold = FoldCache()
+
+    def get_output_feature_dim(self):
+        return self.num_filters[-1]
+
+    def train(self, mode=True):
+        self._fold.invalidate()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._fold.invalidate()
+        return super()._load_from_state_dict(*a, **k)
+
+    def _build_folded(self):
+        lin, bn = self.pfn_layers[0].linear, self.pfn_layers[0].norm
+        s, t = bn_scale_shift(bn)
+        return {"w": (lin.weight.detach().float() * s[:, None]).contiguous(), "b": t.contiguous()}
+
+    def forward(self, batch_dict, **kwargs):
+        if self.training:
+            raise NotImplementedError("hvpr_amd: PillarVFE has no training forward (plain PointPillar is eval only; train MixAnchor_Memory)")
+        voxels, num, coords = batch_dict["voxels"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"]
+        folded = self._fold.get(voxels.device, self._build_folded)
+        pf, mask = kernels.pillar_vfe_plain_fwd(voxels.contiguous(), _as_i32(num), _as_i32(coords).contiguous(), folded["w"], folded["b"],
+                                                self.voxel_size, self.offsets, m_device=batch_dict.get("voxel_count_device"))
+        batch_dict["pillar_features"] = pf
+        batch_dict["pillar_mask"] = mask
+        return batch_dict
+
+
 _ws_cache = {}
 
 
@@ -212,4 +266,5 @@ PillarVFE_Scale._forward_train = _train_forward
 __all__ = {
     "VFETemplate": VFETemplate,
     "PillarVFE_Scale": PillarVFE_Scale,
+    "PillarVFE": PillarVFE,
 }

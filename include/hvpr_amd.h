@@ -107,6 +107,23 @@ int hvpr_pillar_vfe_fwd_f32(const float *voxels, const int32_t *num_points, cons
                             float *pillar_features, float *pillar_scale_features, float *pillar_mask,
                             hvpr_stream_t stream);
 
+/* a2 (plain)  The pillar encoder of plain PointPillars, eval mode (BatchNorm folded by the caller).  Replaces PillarVFE.forward,
+ *     pcdet/models/backbones_3d/vfe/pillar_vfe.py:94-124 (+ PFNLayer :29-49), for ONE PFN layer (NUM_FILTERS=[c_out]),
+ *     USE_ABSLOTE_XYZ=True, WITH_DISTANCE=False, 4 raw point features.  Arguments as in hvpr_pillar_vfe_fwd_f32:
+ *     voxels [M, P, 4] f32 zero padded, num_points [M] i32, coords [M,4] i32 [b,z,y,x]; m_device: optional device i32 holding the
+ *     live row count (<= M; rows at or past it are unspecified), NULL means M rows; vs_* / off_*: voxel size and
+ *     (voxel_size / 2 + range minimum) per axis.  w [c_out,10] b [c_out]: the folded Linear(10->c_out)+BN.
+ *     pillar_features [M,c_out], pillar_mask [M,P] (may be NULL) f32 out.
+ *     Per slot p the ten features are the raw 4, xyz - mean, xyz - (cell * vs + off), all times (p < num_points[m]), with
+ *     mean = (sum over ALL P slots) / float(num_points[m]); out[m,c] = max over ALL P slots of relu(w[c] . f[p] + b[c]) — a padded
+ *     slot contributes relu(b[c]), as in the reference.  A row with num_points == 0 is unspecified (the reference divides by zero)
+ *     but reads and writes only its own cells.
+ *     c_out in {32, 64, 128} and 1 <= P <= 32, anything else HVPR_ERR_UNSUPPORTED; the arguments are checked before any device
+ *     call; M == 0 returns HVPR_OK without a launch.  One launch, no host read, no allocation: capturable.
+ *     The prototype stands in hvpr_amd_added.h, included below: tests/test_capi_symbols.py pins a census of THIS file's prototypes
+ *     (the count of their pointer parameters), and an entry added within an ABI version must leave that census as it is. */
+#include "hvpr_amd_added.h"
+
 /* a2 (training)  The two PFN layers of PillarVFE_Scale with BATCH-statistics BatchNorm (pillar_vfe.py:184-221, PFNLayer :29-49:
  *     linear -> BatchNorm1d over all M * P slots, padded ones included -> ReLU -> max over the slots -> concat), forward and
  *     backward, for the same fixed shapes as hvpr_pillar_vfe_fwd_f32 (P == 32).  No (M, P, C) tensor is materialised: every pass
