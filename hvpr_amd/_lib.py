@@ -1,8 +1,7 @@
 """ctypes binding of libhvpr_amd.so, derived from the declaration of its C-ABI, include/hvpr_amd.h: one header, one pair of tables.
 
 parse_header turns the header's prototypes into ctypes signatures (SIGNATURES) and, per parameter, the element type a
-tensor passed there must have; call() checks every tensor against that before it becomes a pointer.  The entries that
-include/hvpr_amd_added.h holds (added within an ABI version) go through the same parser into ADDED_SIGNATURES / ADDED_PARAMS.
+tensor passed there must have (PARAMS); call() checks every tensor against that before it becomes a pointer.
 The product path has NO CPU fallback: if the library is missing or fails to load, every op raises.
 """
 import ctypes
@@ -25,7 +24,7 @@ class HvprLibraryError(RuntimeError):
     pass
 
 
-# The closed vocabulary of the headers; any other type in a prototype is an error, never a guess.
+# The closed vocabulary of the header; any other type in a prototype is an error, never a guess.
 ANY = "any dtype"        # parameter kind of a `void *`
 _RETURNS = {"int": _c.c_int, "size_t": _c.c_size_t, "void": None, "const char *": _c.c_char_p}
 _SCALARS = {"int": _c.c_int, "float": _c.c_float, "double": _c.c_double, "size_t": _c.c_size_t, "long long": _c.c_longlong,
@@ -72,20 +71,6 @@ PARAMS = {}              # name -> ((parameter name, kind), ...)
 SIGNATURES = {}          # name -> (restype, argtypes)
 for _name, (_res, _args, _params) in read_header(HEADER_PATH).items():
     SIGNATURES[_name], PARAMS[_name] = (_res, _args), _params
-# Entries added within an ABI version stand in include/hvpr_amd_added.h (hvpr_amd.h includes it and says why): the same derivation,
-# tables of their own, so that SIGNATURES / PARAMS stay what hvpr_amd.h itself declares.  lib() binds both, call() takes both.
-ADDED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hvpr_amd_added.h")
-ADDED_PARAMS = {}
-ADDED_SIGNATURES = {}
-for _name, (_res, _args, _params) in read_header(ADDED_HEADER_PATH).items():
-    if _name in SIGNATURES:
-        raise HvprLibraryError(f"{_name} is declared in {HEADER_PATH} and in {ADDED_HEADER_PATH}")
-    ADDED_SIGNATURES[_name], ADDED_PARAMS[_name] = (_res, _args), _params
-
-
-def params_of(name):
-    """((parameter name, kind), ...) of a declared function, whichever header declares it."""
-    return PARAMS[name] if name in PARAMS else ADDED_PARAMS[name]
 
 _lib = None
 _calls = {}              # name -> (bound function, ((index, name, kind) of each pointer), (index of each scalar)): made once in lib(),
@@ -103,12 +88,12 @@ def lib():
             L = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise HvprLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(ADDED_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
             if res is _c.c_int:
-                kinds = params_of(name)
+                kinds = PARAMS[name]
                 _calls[name] = (fn, tuple((i, p, k) for i, (p, k) in enumerate(kinds) if k is not None),
                                 tuple(i for i, (_, k) in enumerate(kinds) if k is None))
         if L.hvpr_abi_version() != ABI_VERSION:      # a stale .so next to newer Python wrappers (buffer sizes, argument lists)
@@ -141,7 +126,7 @@ def call(name, *args):
     if not _PLAIN.issuperset(map(type, map(args.__getitem__, scalars))):      # one pass in C: this runs hundreds of times a step
         for i in scalars:
             if isinstance(args[i], torch.Tensor):
-                raise TypeError(f"{name}: {params_of(name)[i][0]} is a scalar, got a tensor")
+                raise TypeError(f"{name}: {PARAMS[name][i][0]} is a scalar, got a tensor")
     argv = list(args)
     for i, pname, kind in pointers:
         t = argv[i]

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels
-from .folding import FoldCache
+from .folding import FoldCached
 
 
 class ResidualCoder:
@@ -186,7 +186,7 @@ class AnchorHeadTemplate(nn.Module):
         return batch_cls, boxes
 
 
-class AnchorHeadSingle(AnchorHeadTemplate):
+class AnchorHeadSingle(FoldCached, AnchorHeadTemplate):
     """anchor_head_single.py:6-145."""
 
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
@@ -200,20 +200,11 @@ class AnchorHeadSingle(AnchorHeadTemplate):
         self.num_dir_bins = model_cfg.NUM_DIR_BINS if model_cfg.get("USE_DIRECTION_CLASSIFIER", None) is not None else 0
         self.conv_dir_cls = nn.Conv2d(input_channels, na * self.num_dir_bins, kernel_size=1) if self.num_dir_bins else None
         self.init_weights()
-        self._fold = FoldCache()
 
     def init_weights(self):
         pi = 0.01
         nn.init.constant_(self.conv_cls.bias, -np.log((1 - pi) / pi))
         nn.init.normal_(self.conv_box.weight, mean=0, std=0.001)
-
-    def train(self, mode=True):
-        self._fold.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._fold.invalidate()
-        return super()._load_from_state_dict(*a, **k)
 
     def _build_packed(self, device):
         convs = [self.conv_cls, self.conv_box] + ([self.conv_dir_cls] if self.conv_dir_cls is not None else [])

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels
-from .folding import FoldCache, bn_scale_shift
+from .folding import FoldCached, bn_scale_shift
 
 
 class ConvLayer(nn.Module):
@@ -50,6 +50,20 @@ def _conv_bn_relu(cin, cout, stride=1, zero_pad=False):
     return [nn.Conv2d(cin, cout, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(cout, eps=1e-3, momentum=0.01), nn.ReLU()]
 
 
+def _block(cin, cout, stride, layer_num):
+    """One level's trunk: the strided entry convolution and layer_num more."""
+    layers = _conv_bn_relu(cin, cout, stride, zero_pad=True)
+    for _ in range(layer_num):
+        layers += _conv_bn_relu(cout, cout)
+    return nn.Sequential(*layers)
+
+
+def _deblock(cin, cout, stride):
+    """One level's upsampling into the concat: ConvTranspose2d with kernel == stride."""
+    return nn.Sequential(nn.ConvTranspose2d(cin, cout, int(stride), stride=int(stride), bias=False),
+                         nn.BatchNorm2d(cout, eps=1e-3, momentum=0.01), nn.ReLU())
+
+
 # Workgroup tile of hvpr_conv2d_nhwc_f32 (0 = 128 px x 128 ch, 1 = 64 px x 64 ch, 2 = 128 px x 64 ch): 64 x 64 on every layer group (trunk,
 # SFM, scale, deconv) and level.  Measured on MI355X at batch 1 inside the whole frame (bench.py; the streams of the backbone interact, so
 # the per-layer micro-benchmarks tools/bench_conv.py / bench_conv1x1.py do not decide alone); the sweeps are in profiles/NOTES_r04.md.
@@ -71,6 +85,15 @@ def _fold_pack(pack, conv, bn, **kw):
     """Fold the eval-mode BatchNorm `bn` into `conv`'s weights and pack them with kernels.pack_*."""
     scale, shift = bn_scale_shift(bn)
     return pack(conv.weight, scale, shift, **kw)
+
+
+def _conv_f32(conv, bn, stride=1):
+    # stride-1 3x3 layers: Winograd F(2x2,3x3) kernel unless HVPR_CONV_ALGO=direct (kernels.pack_conv_auto)
+    return _fold_pack(kernels.pack_conv_auto, conv, bn, stride=stride, tile_cfg=_TILE_CFG, px_groups=_WINO_PX_GROUPS)
+
+
+def _deconv_f32(de):
+    return _fold_pack(kernels.pack_deconv, de[0], de[1], tile_cfg=_TILE_CFG)
 
 
 def _nhwc(t):
@@ -149,7 +172,28 @@ def _branch(lv, x, y, out, fork, y_out=None):
     return y
 
 
-class BaseBEVBackbone_Scale(nn.Module):
+class _BEVTrunk(FoldCached):
+    """What both backbones' eval forwards share, over the subclass's blocks, deblocks, layer_strides, layer_nums, upsample_strides
+    and up_filters: every level's packed trunk with its deblock and slice of the concat, and the concat canvas."""
+
+    def _trunks(self, conv):
+        """(level, packed trunk, deblock, channel offset in the concat) of every level; conv(conv, bn, stride=1) folds and packs."""
+        coff = 0
+        for i, blk in enumerate(self.blocks):
+            trunk = [conv(blk[1], blk[2], stride=self.layer_strides[i])]
+            trunk += [conv(blk[4 + 3 * k], blk[5 + 3 * k]) for k in range(self.layer_nums[i])]
+            yield i, trunk, self.deblocks[i], coff
+            coff += self.up_filters[i]
+
+    def _canvas(self, x):
+        """The concat for the NHWC input x, empty: level-0 resolution after its own stride, times its upsample stride."""
+        B, H, W, _ = x.shape
+        s0, us0 = self.layer_strides[0], int(self.upsample_strides[0])
+        return torch.empty((B, ((H + 2 - 3) // s0 + 1) * us0, ((W + 2 - 3) // s0 + 1) * us0, self.num_bev_features),
+                           dtype=torch.float32, device=x.device)
+
+
+class BaseBEVBackbone_Scale(_BEVTrunk):
     """base_bev_backbone.py:116-315."""
 
     def __init__(self, model_cfg, input_channels):
@@ -168,21 +212,15 @@ class BaseBEVBackbone_Scale(nn.Module):
         self.sfmblocks_down, self.sfmblocks_up = nn.ModuleList(), nn.ModuleList()
         self.scale_layers, self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for i in range(len(layer_nums)):
-            layers = _conv_bn_relu(cin[i], filters[i], strides[i], zero_pad=True)
-            for _ in range(layer_nums[i]):
-                layers += _conv_bn_relu(filters[i], filters[i])
-            self.blocks.append(nn.Sequential(*layers))
+            self.blocks.append(_block(cin[i], filters[i], strides[i], layer_nums[i]))
             self.sfmblocks_down.append(nn.Sequential(*_conv_bn_relu(filters[i], filters[i])))
             s = up_strides[i]
             assert s >= 1 and int(s) == s, "HIP path: integer upsample strides (ConvTranspose2d with kernel == stride)"
-            self.deblocks.append(nn.Sequential(
-                nn.ConvTranspose2d(filters[i], up_filters[i], int(s), stride=int(s), bias=False),
-                nn.BatchNorm2d(up_filters[i], eps=1e-3, momentum=0.01), nn.ReLU()))
+            self.deblocks.append(_deblock(filters[i], up_filters[i], s))
             self.scale_layers.append(nn.Sequential(*_conv_bn_relu(cin_s[i], scale_filters[i], strides[i], zero_pad=True)))
         self.up_filters = up_filters
         self.num_bev_features = sum(up_filters)
         self.attention = SpatialAttention()
-        self._fold = FoldCache()
         self._sides = None
         # HIP streams of the eval forward: "1" none, "2" trunk + one branch stream, "4" trunk + one stream per level's branch
         self.n_streams = int(os.environ.get("HVPR_BEV_STREAMS", "4"))
@@ -209,44 +247,29 @@ class BaseBEVBackbone_Scale(nn.Module):
             self._sides = [own[i % len(own)] for i in range(n)]
         return self._sides
 
-    def train(self, mode=True):
-        self._fold.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._fold.invalidate()
-        return super()._load_from_state_dict(*a, **k)
-
     def _build_plan(self):
+        """Every level's trunk and deconvolution, plus its scale conv, gate and SFM steps; in split-bf16 planes when selected."""
         planes = self.PRECISIONS[self.conv_precision]
-
-        def conv_f32(conv, bn, stride=1):
-            # stride-1 3x3 layers: Winograd F(2x2,3x3) kernel unless HVPR_CONV_ALGO=direct (kernels.pack_conv_auto)
-            return _fold_pack(kernels.pack_conv_auto, conv, bn, stride=stride, tile_cfg=_TILE_CFG, px_groups=_WINO_PX_GROUPS)
 
         def conv_bf3(conv, bn, stride=1):
             # tile_cfg 4: 64 px x 64 ch tiles, weights staged per kernel row (2-3 workgroups per CU)
             return _fold_pack(kernels.pack_conv_bf3, conv, bn, stride=stride, tile_cfg=4, planes=planes)
 
-        conv = conv_bf3 if planes else conv_f32          # trunk and SFM layers; the scale stream is always fp32
+        conv = conv_bf3 if planes else _conv_f32         # trunk and SFM layers; the scale stream is always fp32
         gate = self.attention.gate_params()
-        levels, coff = [], 0
-        for i, blk in enumerate(self.blocks):
-            s = self.layer_strides[i]
-            trunk = [conv(blk[1], blk[2], stride=s)] + [conv(blk[4 + 3 * k], blk[5 + 3 * k]) for k in range(self.layer_nums[i])]
+        levels = []
+        for i, trunk, de, coff in self._trunks(conv):
             sfm = conv(*self.sfmblocks_down[i][:2])
-            scale = conv_f32(*self.scale_layers[i][1:3], stride=s)
-            de = self.deblocks[i]
+            scale = _conv_f32(*self.scale_layers[i][1:3], stride=self.layer_strides[i])
             # two planes: the deconvolution runs split as well; three planes: its six-product 1x1 is slower than the fp32 kernel
             if planes == 2 and de[0].weight.shape[0] % 64 == 0:
                 deconv = _fold_pack(kernels.pack_deconv_bf3, de[0], de[1], planes=planes)
             else:
-                deconv = _fold_pack(kernels.pack_deconv, de[0], de[1], tile_cfg=_TILE_CFG)
+                deconv = _deconv_f32(de)
             sfm_steps = [sfm] * self.sfm_layer_nums[i]
             if planes and sfm_steps and isinstance(deconv, kernels.PackedConv):
                 sfm_steps[-1] = sfm.fp32_output()          # the last step hands fp32 to the deconvolution only when that one runs on the fp32 kernel
             levels.append(_Level(i, trunk, scale, gate, sfm_steps, deconv, coff))
-            coff += self.up_filters[i]
         return _Plan(levels, planes)
 
     def _forward_train(self, data_dict):
@@ -335,11 +358,7 @@ class BaseBEVBackbone_Scale(nn.Module):
             return self._forward_train(data_dict)
         x, y = _nhwc(data_dict["spatial_features"]), _nhwc(data_dict["spatial_scale_features"])
         plan = self._fold.get(y.device, self._build_plan)
-        # output size of the concat: level-0 resolution after its own stride, times its upsample stride
-        B, H, W, _ = x.shape
-        s0, us0 = self.layer_strides[0], int(self.upsample_strides[0])
-        out = torch.empty((B, ((H + 2 - 3) // s0 + 1) * us0, ((W + 2 - 3) // s0 + 1) * us0, self.num_bev_features),
-                          dtype=torch.float32, device=x.device)
+        out = self._canvas(x)
         if plan.planes:
             x = kernels.split_bf16(x, plan.planes)        # the trunk runs in split-bf16 form from here on
         self._head(plan, x, y, out, len(plan.levels))
@@ -389,7 +408,7 @@ class BaseBEVBackbone_Scale(nn.Module):
                 "out": mk(batch_size, hw[0][0] * us0, hw[0][1] * us0, self.num_bev_features)}
 
 
-class BaseBEVBackbone(nn.Module):
+class BaseBEVBackbone(_BEVTrunk):
     """Plain PointPillars' backbone — base_bev_backbone.py:6-113: per level a strided entry convolution and LAYER_NUMS[i] more, all
     3x3 + BatchNorm + ReLU, then a ConvTranspose2d (kernel == stride) + BatchNorm + ReLU into the level's slice of the concat.
 
@@ -430,48 +449,20 @@ class BaseBEVBackbone(nn.Module):
         self.upsample_strides, self.up_filters = [int(s) for s in up_strides], [int(c) for c in up_filters]
         self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList()
         for i in range(len(layer_nums)):
-            layers = _conv_bn_relu(cin[i], filters[i], self.layer_strides[i], zero_pad=True)
-            for _ in range(self.layer_nums[i]):
-                layers += _conv_bn_relu(filters[i], filters[i])
-            self.blocks.append(nn.Sequential(*layers))
-            s = self.upsample_strides[i]
-            self.deblocks.append(nn.Sequential(nn.ConvTranspose2d(filters[i], up_filters[i], s, stride=s, bias=False),
-                                               nn.BatchNorm2d(up_filters[i], eps=1e-3, momentum=0.01), nn.ReLU()))
+            self.blocks.append(_block(cin[i], filters[i], self.layer_strides[i], self.layer_nums[i]))
+            self.deblocks.append(_deblock(filters[i], up_filters[i], self.upsample_strides[i]))
         self.num_bev_features = sum(self.up_filters)
-        self._fold = FoldCache()
-
-    def train(self, mode=True):
-        self._fold.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._fold.invalidate()
-        return super()._load_from_state_dict(*a, **k)
 
     def _build_plan(self):
-        def conv(conv, bn, stride=1):
-            # stride-1 3x3 layers: Winograd F(2x2,3x3) kernel unless HVPR_CONV_ALGO=direct (kernels.pack_conv_auto)
-            return _fold_pack(kernels.pack_conv_auto, conv, bn, stride=stride, tile_cfg=_TILE_CFG, px_groups=_WINO_PX_GROUPS)
-
-        levels, coff = [], 0
-        for i, blk in enumerate(self.blocks):
-            trunk = [conv(blk[1], blk[2], stride=self.layer_strides[i])]
-            trunk += [conv(blk[4 + 3 * k], blk[5 + 3 * k]) for k in range(self.layer_nums[i])]
-            de = self.deblocks[i]
-            deconv = _fold_pack(kernels.pack_deconv, de[0], de[1], tile_cfg=_TILE_CFG)
-            levels.append(_Level(i, trunk, None, None, [], deconv, coff))
-            coff += self.up_filters[i]
-        return _Plan(levels, 0)
+        """Every level's trunk and deconvolution on the fp32 kernels, no branch."""
+        return _Plan([_Level(i, trunk, None, None, [], _deconv_f32(de), coff) for i, trunk, de, coff in self._trunks(_conv_f32)], 0)
 
     def forward(self, data_dict):
         if self.training:
             raise NotImplementedError("hvpr_amd: BaseBEVBackbone has no training forward (plain PointPillar is eval only; train MixAnchor_Memory)")
         x = _nhwc(data_dict["spatial_features"])
         plan = self._fold.get(x.device, self._build_plan)
-        B, H, W, _ = x.shape
-        s0, us0 = self.layer_strides[0], self.upsample_strides[0]
-        out = torch.empty((B, ((H + 2 - 3) // s0 + 1) * us0, ((W + 2 - 3) // s0 + 1) * us0, self.num_bev_features),
-                          dtype=torch.float32, device=x.device)
+        out = self._canvas(x)
         for lv in plan.levels:
             x = _trunk(lv, x)
             kernels.conv2d_nhwc(x, lv.deconv, out=out, out_coff=lv.coff, use_table=True)

@@ -38,7 +38,7 @@ def build(force=False, verbose=False, timing=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("hvpr_amd.h", "hvpr_amd_added.h")]
+    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "hvpr_amd.h"))
     objdir = os.path.join(HERE, "csrc", "_obj_timing" if timing else "_obj")
     out = os.path.join(HERE, "libhvpr_amd_timing.so") if timing else OUT
     extra = (["-DHVPR_EXP_TIMING"] + os.environ.get("HVPR_EXP_DEFINES", "").split()) if timing else []

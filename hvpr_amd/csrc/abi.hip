@@ -18,7 +18,7 @@
 // hvpr_fused_sgd_f32 are added (csrc/train_ops.hip); hvpr_assign_targets_ex_f32 and hvpr_assign_targets_ex_workspace_bytes are added
 // (csrc/assign_loss.hip: MATCH_HEIGHT and NORM_BY_NUM_EXAMPLES of the target assigner); hvpr_assign_targets_atss_f32 and
 // hvpr_assign_targets_atss_workspace_bytes are added (csrc/assign_atss.hip: NAME: ATSS); hvpr_pillar_vfe_plain_fwd_f32 is added within 8
-// (csrc/vfe_plain.hip: the one-layer pillar encoder of plain PointPillars; prototype in include/hvpr_amd_added.h, which hvpr_amd.h includes)
+// (csrc/vfe_plain.hip: the one-layer pillar encoder of plain PointPillars)
 extern "C" int hvpr_abi_version(void) { return 8; }
 
 extern "C" const char *hvpr_status_string(int status) {

@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import anchor_head, bev_backbone, iou3d_nms_utils, kernels, map_to_bev, pointnet2, vfe
+from .folding import FoldCached
 from .voxel_generator import VoxelGenerator
 
 backbones_3d_all = pointnet2.__all__   # PointNet2MSG: the training-only point stream
@@ -549,7 +550,7 @@ class _CapturedState:
     def __init__(self, model):
         self.slots = []
         for m in model.modules():
-            if hasattr(m, "_fold") and hasattr(m._fold, "value"):
+            if isinstance(m, FoldCached):
                 self.slots.append((m._fold, "value"))
             if hasattr(m, "_packed"):
                 self.slots.append((m, "_packed"))

@@ -1,5 +1,6 @@
 """Eval-mode BatchNorm folding shared by the modules: y = x*s + t with s = gamma/sqrt(var+eps), t = beta - mean*s."""
 import torch
+import torch.nn as nn
 
 
 def bn_scale_shift(bn):
@@ -24,3 +25,20 @@ class FoldCache:
                 self.value = build()
             self.device = device
         return self.value
+
+
+class FoldCached(nn.Module):
+    """A module whose eval forward runs on folded / packed weights kept in `self._fold`: train() and load_state_dict() drop them.
+    List it in front of the module's other bases.  detector._CapturedState finds these modules by this class."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._fold = FoldCache()
+
+    def train(self, mode=True):
+        self._fold.invalidate()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._fold.invalidate()
+        return super()._load_from_state_dict(*a, **k)

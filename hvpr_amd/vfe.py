@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from . import kernels
 from ._lib import call, lib
-from .folding import FoldCache, bn_scale_shift
+from .folding import FoldCached, bn_scale_shift
 
 
 class VFETemplate(nn.Module):
@@ -39,13 +39,38 @@ def _as_i32(t):
     return t if t.dtype == torch.int32 else t.to(torch.int32)
 
 
-class PillarVFE_Scale(VFETemplate):
+class _PillarEncoder(FoldCached, VFETemplate):
+    """What the two pillar encoders share: the grid geometry the kernels take, the fold of one layer and the voxel keys of
+    batch_dict.  The eval forward runs on `self._fold`, built by the subclass's _build_folded."""
+
+    def __init__(self, model_cfg, voxel_size, point_cloud_range):
+        super().__init__(model_cfg=model_cfg)
+        self.num_filters = list(model_cfg.NUM_FILTERS)
+        self.voxel_size = [float(v) for v in voxel_size]
+        self.offsets = [self.voxel_size[i] / 2 + float(point_cloud_range[i]) for i in range(3)]
+
+    def get_output_feature_dim(self):
+        return self.num_filters[-1]
+
+    @staticmethod
+    def _fold_layer(lin, bn):
+        """(w, b) of Linear (no bias) + eval-mode BatchNorm1d as one affine layer."""
+        s, t = bn_scale_shift(bn)
+        return (lin.weight.detach().float() * s[:, None]).contiguous(), t.contiguous()
+
+    @staticmethod
+    def _voxel_inputs(batch_dict):
+        """voxels, voxel_num_points, voxel_coords and the optional live row count, in the form the kernels take."""
+        return (batch_dict["voxels"].contiguous(), _as_i32(batch_dict["voxel_num_points"]),
+                _as_i32(batch_dict["voxel_coords"]).contiguous(), batch_dict.get("voxel_count_device"))
+
+
+class PillarVFE_Scale(_PillarEncoder):
     """Pillar encoder + scale stream — pillar_vfe.py:127-221."""
 
     def __init__(self, model_cfg, num_point_features, voxel_size, point_cloud_range):
-        super().__init__(model_cfg=model_cfg)
+        super().__init__(model_cfg, voxel_size, point_cloud_range)
         assert model_cfg.USE_ABSLOTE_XYZ and not model_cfg.WITH_DISTANCE, "HIP VFE: USE_ABSLOTE_XYZ=True, WITH_DISTANCE=False"
-        self.num_filters = list(model_cfg.NUM_FILTERS)
         self.num_scale_features = list(model_cfg.NUM_SCALE_FEATURES)
         widths = [num_point_features + 6] + self.num_filters
         self.pfn_layers = nn.ModuleList(
@@ -55,20 +80,6 @@ class PillarVFE_Scale(VFETemplate):
         self.pfn_scale_layers = nn.ModuleList(
             nn.Sequential(nn.Linear(sw[i], sw[i + 1], bias=False), nn.BatchNorm1d(sw[i + 1], eps=1e-3, momentum=0.01), nn.ReLU())
             for i in range(len(sw) - 1))
-        self.voxel_size = [float(v) for v in voxel_size]
-        self.offsets = [self.voxel_size[i] / 2 + float(point_cloud_range[i]) for i in range(3)]
-        self._fold = FoldCache()
-
-    def get_output_feature_dim(self):
-        return self.num_filters[-1]
-
-    def train(self, mode=True):
-        self._fold.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._fold.invalidate()
-        return super()._load_from_state_dict(*a, **k)
 
     def _build_folded(self):
         f = {}
@@ -76,33 +87,29 @@ class PillarVFE_Scale(VFETemplate):
                              ("1", self.pfn_layers[1].linear, self.pfn_layers[1].norm),
                              ("s0", self.pfn_scale_layers[0][0], self.pfn_scale_layers[0][1]),
                              ("s1", self.pfn_scale_layers[1][0], self.pfn_scale_layers[1][1])):
-            s, t = bn_scale_shift(bn)
-            f["w" + key] = (lin.weight.detach().float() * s[:, None]).contiguous()
-            f["b" + key] = t.contiguous()
+            f["w" + key], f["b" + key] = self._fold_layer(lin, bn)
         return f
 
     def forward(self, batch_dict, **kwargs):
-        voxels, num, coords = batch_dict["voxels"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"]
         if self.training:
-            return self._forward_train(batch_dict, voxels, num, coords)
+            return self._forward_train(batch_dict, batch_dict["voxels"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"])
+        voxels, num, coords, m_device = self._voxel_inputs(batch_dict)
         folded = self._fold.get(voxels.device, self._build_folded)
-        pf, sf, mask = kernels.pillar_vfe_fwd(voxels.contiguous(), _as_i32(num), _as_i32(coords).contiguous(), folded,
-                                              self.voxel_size, self.offsets, m_device=batch_dict.get("voxel_count_device"))
+        pf, sf, mask = kernels.pillar_vfe_fwd(voxels, num, coords, folded, self.voxel_size, self.offsets, m_device=m_device)
         batch_dict["pillar_features"] = pf
         batch_dict["pillar_scale_features"] = sf
         batch_dict["pillar_mask"] = mask
         return batch_dict
 
 
-class PillarVFE(VFETemplate):
+class PillarVFE(_PillarEncoder):
     """Plain PointPillars' pillar encoder — pillar_vfe.py:52-124: one PFN layer, no scale stream.  The eval forward is ONE launch
     of hvpr_pillar_vfe_plain_fwd_f32 on the folded layer; settings the kernel is not built for raise at construction."""
 
     WIDTHS = (32, 64, 128)
 
     def __init__(self, model_cfg, num_point_features, voxel_size, point_cloud_range):
-        super().__init__(model_cfg=model_cfg)
-        self.num_filters = list(model_cfg.NUM_FILTERS)
+        super().__init__(model_cfg, voxel_size, point_cloud_range)
         if len(self.num_filters) != 1:
             raise ValueError(f"hvpr_amd: PillarVFE is built for one PFN layer, NUM_FILTERS has {len(self.num_filters)} entries")
         if self.num_filters[0] not in self.WIDTHS:
@@ -116,33 +123,17 @@ class PillarVFE(VFETemplate):
         if num_point_features != 4:
             raise ValueError(f"hvpr_amd: PillarVFE is built for 4 raw point features, got {num_point_features}")
         self.pfn_layers = nn.ModuleList([PFNLayer(num_point_features + 6, self.num_filters[0], True, last_layer=True)])
-        self.voxel_size = [float(v) for v in voxel_size]
-        self.offsets = [self.voxel_size[i] / 2 + float(point_cloud_range[i]) for i in range(3)]
-        self._fold = FoldCache()
-
-    def get_output_feature_dim(self):
-        return self.num_filters[-1]
-
-    def train(self, mode=True):
-        self._fold.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._fold.invalidate()
-        return super()._load_from_state_dict(*a, **k)
 
     def _build_folded(self):
-        lin, bn = self.pfn_layers[0].linear, self.pfn_layers[0].norm
-        s, t = bn_scale_shift(bn)
-        return {"w": (lin.weight.detach().float() * s[:, None]).contiguous(), "b": t.contiguous()}
+        w, b = self._fold_layer(self.pfn_layers[0].linear, self.pfn_layers[0].norm)
+        return {"w": w, "b": b}
 
     def forward(self, batch_dict, **kwargs):
         if self.training:
             raise NotImplementedError("hvpr_amd: PillarVFE has no training forward (plain PointPillar is eval only; train MixAnchor_Memory)")
-        voxels, num, coords = batch_dict["voxels"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"]
+        voxels, num, coords, m_device = self._voxel_inputs(batch_dict)
         folded = self._fold.get(voxels.device, self._build_folded)
-        pf, mask = kernels.pillar_vfe_plain_fwd(voxels.contiguous(), _as_i32(num), _as_i32(coords).contiguous(), folded["w"], folded["b"],
-                                                self.voxel_size, self.offsets, m_device=batch_dict.get("voxel_count_device"))
+        pf, mask = kernels.pillar_vfe_plain_fwd(voxels, num, coords, folded["w"], folded["b"], self.voxel_size, self.offsets, m_device=m_device)
         batch_dict["pillar_features"] = pf
         batch_dict["pillar_mask"] = mask
         return batch_dict

@@ -119,10 +119,11 @@ int hvpr_pillar_vfe_fwd_f32(const float *voxels, const int32_t *num_points, cons
  *     slot contributes relu(b[c]), as in the reference.  A row with num_points == 0 is unspecified (the reference divides by zero)
  *     but reads and writes only its own cells.
  *     c_out in {32, 64, 128} and 1 <= P <= 32, anything else HVPR_ERR_UNSUPPORTED; the arguments are checked before any device
- *     call; M == 0 returns HVPR_OK without a launch.  One launch, no host read, no allocation: capturable.
- *     The prototype stands in hvpr_amd_added.h, included below: tests/test_capi_symbols.py pins a census of THIS file's prototypes
- *     (the count of their pointer parameters), and an entry added within an ABI version must leave that census as it is. */
-#include "hvpr_amd_added.h"
+ *     call; M == 0 returns HVPR_OK without a launch.  One launch, no host read, no allocation: capturable. */
+int hvpr_pillar_vfe_plain_fwd_f32(const float *voxels, const int32_t *num_points, const int32_t *coords, int M, int P,
+                                  const int32_t *m_device, float vs_x, float vs_y, float vs_z, float off_x, float off_y,
+                                  float off_z, const float *w, const float *b, int c_out, float *pillar_features,
+                                  float *pillar_mask, hvpr_stream_t stream);
 
 /* a2 (training)  The two PFN layers of PillarVFE_Scale with BATCH-statistics BatchNorm (pillar_vfe.py:184-221, PFNLayer :29-49:
  *     linear -> BatchNorm1d over all M * P slots, padded ones included -> ReLU -> max over the slots -> concat), forward and

@@ -56,7 +56,7 @@ def test_no_cpu_fallback():
 # ------------------------------------------------------------------------------------------------ the binding derived from the header
 _c = ctypes
 _P, _I, _F, _Z, _LL = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_longlong
-# copied from the hand-typed table the derived one replaced: one of each kind of type
+# copied from the hand-typed table the derived one replaced: one of each kind of type (and the plain pillar encoder's, added since)
 PINNED = {
     "hvpr_abi_version": (_I, []),
     "hvpr_status_string": (_c.c_char_p, [_I]),
@@ -65,6 +65,7 @@ PINNED = {
     "hvpr_bn_workspace_bytes": (_Z, [_LL, _I]),
     "hvpr_bn_relu_bwd_apply_nhwc_f32": (_I, [_P, _I, _I, _P, _LL, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _c.c_double, _P]),
     "hvpr_fused_sgd_f32": (_I, [_P, _P, _P, _LL, _F, _F, _F, _P, _P]),
+    "hvpr_pillar_vfe_plain_fwd_f32": (_I, [_P, _P, _P, _I, _I, _P, _F, _F, _F, _F, _F, _F, _P, _P, _I, _P, _P, _P]),
     "hvpr_kitti_match_f64": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I,
                                   _P, _P, _P, _P, _P, _Z, _P]),
     "hvpr_render_bev_u8": (_I, [_P, _LL, _I, _I, _P, _I, _P, _F, _P, _I, _I, _P, _P, _F, _P, _I, _P, _I, _I, _P, _P, _F, _P, _I,
@@ -94,7 +95,8 @@ def test_parameter_kinds_come_from_the_header():
     assert kinds["n_frames"] is None and kinds["n_gt_total"] is None and kinds["stream"] is None   # scalars (the frame count F)
     assert dict(_lib.PARAMS["hvpr_max_samples_f32"])["G"] is None
     every = [k for ps in _lib.PARAMS.values() for _, k in ps if k is not None]
-    assert len(every) == 569 and {k for k in every} == {torch.float32, torch.int32, torch.int64, torch.float64, torch.uint8, _lib.ANY}
+    # + 8: voxels, num_points, coords, m_device, w, b, pillar_features, pillar_mask of hvpr_pillar_vfe_plain_fwd_f32
+    assert len(every) == 569 + 8 == 577 and {k for k in every} == {torch.float32, torch.int32, torch.int64, torch.float64, torch.uint8, _lib.ANY}
 
 
 def test_parser_on_synthetic_headers():

@@ -9,7 +9,7 @@ import torch
 
 import pointpillar_cases as PC
 from detparams import det_state
-from hvpr_amd import bev_backbone, config, detector, vfe
+from hvpr_amd import anchor_head, bev_backbone, config, detector, folding, vfe
 
 VS, RNG = [0.16, 0.16, 3.0], [0, -19.84, -2.5, 47.36, 19.84, 0.5]          # make_golden.VOXEL_SIZE / PC_RANGE: G28's vfe cases
 
@@ -95,7 +95,8 @@ def test_shipped_config_builds_on_the_cpu():
     assert isinstance(model.backbone_2d, bev_backbone.BaseBEVBackbone) and model.backbone_2d.num_bev_features == 384
     assert model.dense_head.num_anchors_per_location == 6
     assert sum(int(np.prod(a.shape[:-1])) for a in model.dense_head.anchors) == 321408 == 216 * 248 * 6
-    assert hasattr(model.vfe, "_fold") and hasattr(model.backbone_2d, "_fold")          # what _CapturedState walks
+    assert hasattr(model.vfe, "_fold") and hasattr(model.backbone_2d, "_fold")
+    assert all(isinstance(m, folding.FoldCached) for m in (model.vfe, model.backbone_2d, model.dense_head))   # what _CapturedState walks
     assert [type(m).__name__ for m in model.module_list] == ["PillarVFE", "PointPillarScatter", "BaseBEVBackbone", "AnchorHeadSingle"]
 
 
@@ -142,7 +143,12 @@ def test_modules_build_with_supported_settings_and_refuse_training_forwards():
 
 
 def test_fold_caches_are_dropped_by_train_and_load_state_dict():
-    for m in (vfe.PillarVFE(PC.vfe_cfg(), 4, VS, RNG), bev_backbone.BaseBEVBackbone(PC.backbone_cfg(), input_channels=64)):
+    hvpr = config.hvpr_car_cfg().MODEL
+    head = anchor_head.AnchorHeadSingle(model_cfg=hvpr.DENSE_HEAD, input_channels=64, num_class=1, class_names=["Car"],
+                                        grid_size=np.array([16, 16, 1]), point_cloud_range=np.array([0, -1.28, -3, 2.56, 1.28, 1], np.float32))
+    for m in (vfe.PillarVFE(PC.vfe_cfg(), 4, VS, RNG), bev_backbone.BaseBEVBackbone(PC.backbone_cfg(), input_channels=64),
+              vfe.PillarVFE_Scale(hvpr.VFE, 4, VS, RNG), bev_backbone.BaseBEVBackbone_Scale(hvpr.BACKBONE_2D, input_channels=64), head):
+        assert isinstance(m, folding.FoldCached) and type(m._fold) is folding.FoldCache and m._fold.value is None
         m.eval()
         m._fold.value, m._fold.device = "stale", torch.device("cpu")
         m.load_state_dict(m.state_dict())
@@ -150,6 +156,58 @@ def test_fold_caches_are_dropped_by_train_and_load_state_dict():
         m._fold.value = "stale"
         m.train(False)
         assert m._fold.value is None
+
+
+def test_fold_cached_alone_drops_its_fold_and_registers_nothing():
+    class Toy(folding.FoldCached):
+        pass
+
+    m = Toy()
+    assert type(m._fold) is folding.FoldCache and m._fold.value is None and m._fold.device is None
+    for drop in (lambda: m.train(False), lambda: m.train(True), lambda: m.load_state_dict(m.state_dict())):
+        m._fold.value = "stale"
+        drop()
+        assert m._fold.value is None
+    assert len(m.state_dict()) == 0 and not list(m.parameters()) and not list(m.buffers()) and not list(m.children())
+    assert m.train(False) is m and m.training is False and m.train() is m and m.training is True
+
+
+# Every shipped model's names in registration order, taken at the commit before the modules got their common bases: optimizer
+# checkpoints and the fused flat optimizer steps index parameters by position.  Per kind the count and sha256("\n".join(names))[:16];
+# RUNS: the submodules in that order with their (named_parameters, state_dict) counts, which say where an order first departs.
+_HVPR_RUNS = [("global_step", 0, 1), ("backbone_3d.SA_modules", 36, 72), ("backbone_3d.FP_modules", 12, 24), ("vfe.pfn_layers", 6, 12),
+              ("vfe.pfn_scale_layers", 6, 12), ("map_to_bev_module.memory", 1, 1), ("backbone_2d.sfmblocks_down", 9, 18),
+              ("backbone_2d.scale_layers", 9, 18), ("backbone_2d.blocks", 36, 72), ("backbone_2d.deblocks", 9, 18),
+              ("backbone_2d.attention", 4, 7), ("dense_head.conv_cls", 2, 2), ("dense_head.conv_box", 2, 2), ("dense_head.conv_dir_cls", 2, 2)]
+_HVPR_NAMES = {"named_parameters": (134, "2affb0e0d6df95bf"), "state_dict": (261, "759ab6ee4bab47ed"), "runs": _HVPR_RUNS}
+NAME_ORDER = {"hvpr_car_cfg": _HVPR_NAMES, "hvpr_3class_cfg": _HVPR_NAMES, "hvpr_car_atss_cfg": _HVPR_NAMES,
+              "pointpillar_cfg": {"named_parameters": (66, "c1d37bc01841e3aa"), "state_dict": (127, "073b7e2706caa69b"),
+                                  "runs": [("global_step", 0, 1), ("vfe.pfn_layers", 3, 6), ("backbone_2d.blocks", 48, 96),
+                                           ("backbone_2d.deblocks", 9, 18), ("dense_head.conv_cls", 2, 2), ("dense_head.conv_box", 2, 2),
+                                           ("dense_head.conv_dir_cls", 2, 2)]}}
+
+
+def _first_departure(names, runs):
+    """'' when `names` follow `runs` = [(prefix, count), ...]; else the first position that does not, with both neighbours."""
+    want = [p for p, n in runs for _ in range(n)]
+    for i in range(max(len(names), len(want))):
+        if i >= len(names) or i >= len(want) or not (names[i] + ".").startswith(want[i] + "."):
+            return f"position {i}: {names[max(i - 1, 0):i + 2]} where {want[max(i - 1, 0):i + 2]} stood"
+    return ""
+
+
+@pytest.mark.parametrize("which", sorted(NAME_ORDER))
+def test_parameter_and_state_dict_names_keep_their_order(which):
+    import hashlib
+    cfg = getattr(config, which)()
+    model = detector.build_network(cfg.MODEL, len(cfg.CLASS_NAMES), detector.SyntheticDataset(cfg))
+    for col, kind, names in ((1, "named_parameters", [n for n, _ in model.named_parameters()]), (2, "state_dict", list(model.state_dict()))):
+        count, digest = NAME_ORDER[which][kind]
+        assert sum(r[col] for r in NAME_ORDER[which]["runs"]) == count
+        where = _first_departure(names, [(r[0], r[col]) for r in NAME_ORDER[which]["runs"]])
+        print(f"{which} {kind}(): {where or 'every submodule in its place'}")
+        assert not where, f"{which}: {kind}() order changed at {where}"
+        assert (len(names), hashlib.sha256("\n".join(names).encode()).hexdigest()[:16]) == (count, digest)
 
 
 def test_c_entry_refuses_unsupported_shapes_without_a_device():
@@ -165,22 +223,23 @@ def test_c_entry_refuses_unsupported_shapes_without_a_device():
     assert status(0, 32, 64) == 0 and status(0, 1, 128) == 0 and status(0, 32, 32) == 0             # nothing to do: no launch
 
 
-def test_added_header_is_bound_like_the_main_one():
-    """include/hvpr_amd_added.h: included by hvpr_amd.h, parsed by the same parser into tables of their own, every entry exported and
-    bound with the derived types, none declared in both files."""
+def test_plain_entry_is_declared_in_the_one_header_and_bound_from_it():
+    """hvpr_pillar_vfe_plain_fwd_f32 stands in include/hvpr_amd.h, the only header, and is bound through the one pair of tables with
+    the derived types."""
     import ctypes as c
     from hvpr_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert '#include "hvpr_amd_added.h"' in open(os.path.join(root, "include", "hvpr_amd.h")).read()
-    assert sorted(_lib.ADDED_SIGNATURES) == sorted(_lib.ADDED_PARAMS) == ["hvpr_pillar_vfe_plain_fwd_f32"]
-    assert not set(_lib.ADDED_SIGNATURES) & set(_lib.SIGNATURES)
+    assert not any(hasattr(_lib, name) for name in ("ADDED_SIGNATURES", "ADDED_PARAMS", "params_of"))
+    # one header per library: libhvpr_amd.so's, and hvpr_cpu.h of the host-side libhvpr_cpu.so (gt_sampling.py), which declares no GPU entry
+    headers = sorted(f for f in os.listdir(os.path.join(root, "include")) if f.endswith(".h"))
+    assert headers == ["hvpr_amd.h", "hvpr_cpu.h"] and [h for h in headers if h != "hvpr_cpu.h"] == ["hvpr_amd.h"]
+    assert '#include "hvpr_' not in open(os.path.join(root, "include", "hvpr_amd.h")).read()
     P, I, F = c.c_void_p, c.c_int, c.c_float
-    res, args = _lib.ADDED_SIGNATURES["hvpr_pillar_vfe_plain_fwd_f32"]
+    res, args = _lib.SIGNATURES["hvpr_pillar_vfe_plain_fwd_f32"]
     assert res is I and args == [P, P, P, I, I, P, F, F, F, F, F, F, P, P, I, P, P, P]
-    kinds = dict(_lib.ADDED_PARAMS["hvpr_pillar_vfe_plain_fwd_f32"])
+    kinds = dict(_lib.PARAMS["hvpr_pillar_vfe_plain_fwd_f32"])
     assert len(kinds) == 18 and kinds["voxels"] == torch.float32 and kinds["num_points"] == kinds["coords"] == kinds["m_device"] == torch.int32
     assert kinds["pillar_mask"] == torch.float32 and kinds["c_out"] is None and kinds["stream"] is None
-    assert _lib.params_of("hvpr_pillar_vfe_plain_fwd_f32") is _lib.ADDED_PARAMS["hvpr_pillar_vfe_plain_fwd_f32"]
     fn = _lib.lib().hvpr_pillar_vfe_plain_fwd_f32
     assert fn.restype is I and list(fn.argtypes) == args
     with pytest.raises(TypeError, match="c_out is a scalar"):
