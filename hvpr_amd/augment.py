@@ -21,15 +21,13 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import kernels
+from . import kernels, preprocess
+from .calibration import lidar_to_rect, rect_to_lidar
+from .config import _get
 
 OP_FLIP_X, OP_FLIP_Y, OP_ROTATE, OP_SCALE = 1, 2, 3, 4
 PLAN_MAGIC = 0x31475541
 PLAN_HEADER = 8
-
-
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
 
 
 # ------------------------------------------------------------------------------------------------ the database
@@ -87,7 +85,6 @@ class ObjectBank:
         device tensor; `rows_of[id(record)]` = (first row, rows) of that record's points in it.  The PREPARE filters run on the
         records as ever; the survivors' segments are gathered into the bank's order on the device, and the host copy
         (`host_points`) is made from that only when someone asks."""
-        from . import preprocess
         kw.setdefault("num_point_features", int(arena.shape[1]))
         kw.setdefault("device", arena.device)
         bank = cls(db_infos, None, class_names, **kw)
@@ -144,31 +141,14 @@ class ObjectBank:
         return self._dev
 
 
-# ------------------------------------------------------------------------------------------------ calibration, road plane
-def lidar_to_rect(calib, pts_lidar):
-    """calibration_kitti.py:65-73 over the dict of matrices `preprocess.fov_matrices` takes."""
-    hom = np.hstack((pts_lidar, np.ones((pts_lidar.shape[0], 1), dtype=np.float32)))
-    return np.dot(hom, np.dot(calib["Tr_velo2cam"].T, calib["R0"].T))
-
-
-def rect_to_lidar(calib, pts_rect):
-    """calibration_kitti.py:50-63."""
-    hom = np.hstack((pts_rect, np.ones((pts_rect.shape[0], 1), dtype=np.float32)))
-    R0_ext = np.hstack((calib["R0"], np.zeros((3, 1), dtype=np.float32)))
-    R0_ext = np.vstack((R0_ext, np.zeros((1, 4), dtype=np.float32)))
-    R0_ext[3, 3] = 1
-    V2C_ext = np.vstack((calib["Tr_velo2cam"], np.zeros((1, 4), dtype=np.float32)))
-    V2C_ext[3, 3] = 1
-    return np.dot(hom, np.linalg.inv(np.dot(R0_ext, V2C_ext).T))[:, 0:3]
-
-
+# ------------------------------------------------------------------------------------------------ road plane
 def put_boxes_on_road_planes(gt_boxes, road_plane, calib):
     """database_sampler.py:99-116.  Row-wise, so it may run over every candidate before the collision test decides."""
     a, b, c, d = road_plane
-    center_cam = lidar_to_rect(calib, gt_boxes[:, 0:3])
+    center_cam = lidar_to_rect(gt_boxes[:, 0:3], calib)
     cur_height_cam = (-d - a * center_cam[:, 0] - c * center_cam[:, 2]) / b
     center_cam[:, 1] = cur_height_cam
-    cur_lidar_height = rect_to_lidar(calib, center_cam)[:, 2]
+    cur_lidar_height = rect_to_lidar(center_cam, calib)[:, 2]
     mv_height = gt_boxes[:, 2] - gt_boxes[:, 5] / 2 - cur_lidar_height
     gt_boxes[:, 2] -= mv_height
     return gt_boxes, mv_height
@@ -360,12 +340,7 @@ class DeviceAugmentor:
         self.planner = AugmentPlanner(augmentor_cfg, class_names, bank)
         self.point_cloud_range = np.ascontiguousarray(point_cloud_range, np.float32)
         self.remove_outside_boxes = bool(remove_outside_boxes)
-        self._stage = None
-
-    def _staging(self, words):
-        if self._stage is None or self._stage.numel() < words:
-            self._stage = torch.empty((max(words, 4096),), dtype=torch.int32).pin_memory()
-        return self._stage
+        self._stage = preprocess.PinnedBuffer()
 
     def __call__(self, frames, rng=np.random, points=None, point_counts=None):
         dev = self.bank.device
@@ -385,7 +360,7 @@ class DeviceAugmentor:
         _, obj_off = self.bank.host_points()
         G = sum(len(g) for g in gt_boxes)
         C = sum(len(p["cand_obj"]) for p in plans)
-        stage = self._staging(plan_words(B, NG, G, C))
+        stage = self._stage.take(plan_words(B, NG, G, C))
         words = pack_plans(stage.numpy(), plans, gt_boxes, gt_cls, point_counts, self.planner.ops_word, NG, obj_off)
         plan_dev = stage[:words].to(dev, non_blocking=True)                      # the one upload of the call
         g_cap = max(1, max(int((gt_cls[f] > 0).sum()) + len(plans[f]["cand_obj"]) for f in range(B)))

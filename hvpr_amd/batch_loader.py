@@ -39,7 +39,7 @@ frame passes one generator per frame.)
 only through n, the rows the mask keeps, c, how many of them are near (||xyz|| < 40), and P = NUM_POINTS[mode]:
 `rng.choice(a, k, replace=False)` is `a[rng.choice(np.arange(len(a)), k, replace=False)]`, and `rng.shuffle` moves positions
 whatever the values.  So `plan_sample_points` draws over ORDINALS (a near row's position among the frame's near kept rows, a far
-row's among the far ones, or the plain in-frame rank) from the two counts, call for call as `preprocess.sample_points_choice`
+row's among the far ones, or the plain in-frame rank) from the two counts, call for call as the reference
 does, composes the following permutation, and the write pass of csrc/collate.hip turns each kept row's two ranks into its ordinal
 and scatters it through the resulting table.  The near counts ride in read 2 of a training batch and in the one read of a test
 batch (which samples too): no read is added.  A frame the reference refuses (more far rows than P, P - n > n, an empty frame)
@@ -51,59 +51,13 @@ import numpy as np
 import torch
 
 from . import augment as AUG
-from . import eval_loop, kernels, preprocess
+from . import calibration, kernels, preprocess
+from .config import _get
+from .preprocess import PinnedBuffer, plan_sample_points, resolve_sample_choice, to_device
 
 NEAR = 40.0                # data_processor.py:88
 
 SUPPORTED_PROCESSORS = ("mask_points_and_boxes_outside_range", "shuffle_points", "transform_points_to_voxels")
-
-
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
-
-
-def _pinned(array):
-    return torch.from_numpy(np.ascontiguousarray(array)).pin_memory()
-
-
-def plan_sample_points(n, c, num_points, rng=np.random, shuffle=False):
-    """DataProcessor.sample_points for a frame of n rows of which c are near, from the counts alone: the generator calls of
-    `preprocess.sample_points_choice`, one for one (the draw at data_processor.py:91 in front of the size test included), over
-    ordinals.  Returns a dict: `mode` 0 when an entry of `choice` is a row's in-frame rank, 1 when it is a near ordinal (< c) or
-    c + a far ordinal; `choice`, the reference's `choice` in that form; `perm`, the following `rng.permutation` (None without
-    `shuffle`); `order` = choice[perm], the source of every output row.  Raises what the reference raises."""
-    n, c, P = int(n), int(c), int(num_points)
-    if not 0 <= c <= n:
-        raise ValueError(f"plan_sample_points: {c} near rows of {n}")
-    mode = 0
-    if P == -1:
-        choice = np.arange(n)
-    elif P < n:
-        far, near_ord = n - c, np.arange(c)
-        want = P - far
-        drawn = rng.choice(near_ord, want, replace=False)               # :91, ValueError when more than P rows are far
-        if want > 0:
-            drawn = rng.choice(near_ord, want, replace=False)
-            choice = np.concatenate((drawn, c + np.arange(far)), axis=0) if far > 0 else drawn
-            mode = 1
-        else:
-            choice = rng.choice(np.arange(n), P, replace=False)
-        rng.shuffle(choice)
-    else:
-        choice = np.arange(n)
-        if P > n:                                                        # ValueError when P - n > n or the frame is empty
-            choice = np.concatenate((choice, rng.choice(choice, P - n, replace=False)), axis=0)
-        rng.shuffle(choice)
-    perm = rng.permutation(len(choice)) if shuffle else None
-    return {"mode": mode, "choice": choice, "perm": perm, "order": choice if perm is None else choice[perm]}
-
-
-def resolve_sample_choice(plan, near):
-    """The reference's `choice` (row indices) of a plan, given the frame's near flags."""
-    if plan["mode"] == 0:
-        return plan["choice"]
-    near = np.asarray(near) != 0
-    return np.concatenate((np.where(near)[0], np.where(~near)[0]))[plan["choice"]]
 
 
 def sample_destinations(order, n):
@@ -172,7 +126,10 @@ class DeviceBatchLoader:
             if bank is None:
                 raise ValueError("DeviceBatchLoader: training needs the ObjectBank of the GT sampler")
             self.planner = AUG.AugmentPlanner(dataset_cfg["DATA_AUGMENTOR"], self.class_names, bank)
-        self._stage_buf = self._table_buf = None
+        self._stage = PinnedBuffer()
+        # the destination table and the mode words of a sampled batch: the upload of batch k is enqueued before the reads of
+        # batch k + 1, and the buffer is written again only after them
+        self._table = PinnedBuffer()
         self.reads = 0
 
     # -------------------------------------------------------------------------------------------- the only host reads
@@ -181,19 +138,7 @@ class DeviceBatchLoader:
         return tensor.cpu().numpy()
 
     def _up(self, array):
-        return _pinned(array).to(self.device, non_blocking=True)
-
-    def _staging(self, words):
-        if self._stage_buf is None or self._stage_buf.numel() < words:
-            self._stage_buf = torch.empty((max(words, 4096),), dtype=torch.int32).pin_memory()
-        return self._stage_buf
-
-    def _table_staging(self, words):
-        """Pinned words for the destination table and the mode words of a sampled batch.  The upload of batch k is enqueued
-        before the reads of batch k + 1, and the buffer is written again only after them."""
-        if self._table_buf is None or self._table_buf.numel() < words:
-            self._table_buf = torch.empty((max(words, 4096),), dtype=torch.int32).pin_memory()
-        return self._table_buf
+        return to_device(array, self.device)
 
     # -------------------------------------------------------------------------------------------- pieces
     def _count(self, points, off, mask, calib=None):
@@ -213,15 +158,7 @@ class DeviceBatchLoader:
         return points, off, counts
 
     def _calib(self, frames):
-        return self._up(eval_loop.pack_calib([f["calib"] for f in frames], [f["image_shape"] for f in frames]))
-
-    @staticmethod
-    def _calib_dict(frame):
-        c = frame.get("calib")
-        if c is None or isinstance(c, dict):
-            return c
-        V2C, R0, P2 = eval_loop._calib_parts(c)
-        return {"Tr_velo2cam": V2C, "R0": R0, "P2": P2}
+        return self._up(calibration.pack_calib([f["calib"] for f in frames], [f["image_shape"] for f in frames]))
 
     @staticmethod
     def _batch(frames, points, offsets, flag, perms):
@@ -246,11 +183,11 @@ class DeviceBatchLoader:
         gt_boxes = [b.reshape(-1, 7) if b.size == 0 else b[:, :7] for b in gt_boxes]
         gt_cls = [np.asarray([self.class_names.index(n) + 1 if n in self.class_names else 0
                               for n in np.asarray(f["gt_names"]).astype(str)], np.int32) for f in frames]
-        plans = [self.planner.plan_frame(f["gt_names"], self._calib_dict(f), f.get("road_plane"), r) for f, r in zip(frames, rngs)]
+        plans = [self.planner.plan_frame(f["gt_names"], calibration.as_dict(f.get("calib")), f.get("road_plane"), r) for f, r in zip(frames, rngs)]
         _, obj_off = self.bank.host_points()
         G = sum(len(g) for g in gt_boxes)
         C = sum(len(p["cand_obj"]) for p in plans)
-        stage = self._staging(AUG.plan_words(B, NG, G, C))
+        stage = self._stage.take(AUG.plan_words(B, NG, G, C))
         words = AUG.pack_plans(stage.numpy(), plans, gt_boxes, gt_cls, counts, self.planner.ops_word, NG, obj_off)
         plan_dev = stage[:words].to(self.device, non_blocking=True)
         n_gt = np.asarray([int((c > 0).sum()) for c in gt_cls], np.int64)
@@ -325,7 +262,7 @@ class DeviceBatchLoader:
         """sample_points' draws and the permutations (host), then the write pass through the destination table: every frame
         gets exactly NUM_POINTS rows."""
         B, P, total = len(frames), self.num_points, int(new_off[-1])
-        stage = self._table_staging(2 * total + B)                              # pinned, kept from batch to batch
+        stage = self._table.take(2 * total + B)                                 # pinned, kept from batch to batch
         dest, mode = stage.numpy()[: 2 * total].reshape(total, 2), stage.numpy()[2 * total: 2 * total + B]
         perms, plans = [], []
         for b, r in enumerate(rngs):                                             # raises before the write pass is launched

@@ -32,6 +32,11 @@ def _wrap(v):
     return v
 
 
+def _get(cfg, key, default=None):
+    """cfg[key], or `default` where the block has no such key."""
+    return cfg[key] if key in cfg else default
+
+
 def _has_include(d):
     return isinstance(d, dict) and ("_BASE_CONFIG_" in d or any(_has_include(v) for v in d.values()))
 

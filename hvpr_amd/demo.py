@@ -17,15 +17,15 @@ eager path's bit for bit."""
 import argparse
 import collections
 import glob
-import logging
 import pickle
-import sys
 from pathlib import Path
 
 import numpy as np
 import torch
 
+from .common_utils import create_logger
 from .config import cfg_from_list, cfg_from_yaml_file
+from .preprocess import to_device
 
 REPO_ROOT = Path(__file__).resolve().parent.parent
 
@@ -87,10 +87,7 @@ class DemoFrames:
         return len(self.files)
 
     def __call__(self, index):
-        points = torch.from_numpy(read_points(self.files[index], self.ext))
-        if self.device.type == "cuda":
-            points = points.pin_memory()
-        return {"points": points.to(self.device, non_blocking=True), "frame_id": Path(self.files[index]).stem,
+        return {"points": to_device(read_points(self.files[index], self.ext), self.device), "frame_id": Path(self.files[index]).stem,
                 "file": self.files[index]}
 
 
@@ -139,16 +136,6 @@ _REC_KEYS = ("pred_boxes", "pred_scores", "pred_labels", "pred_count")
 
 def _to_host(records):
     return [{k: r[k].cpu().numpy() for k in _REC_KEYS} for r in records]
-
-
-def create_logger(name="hvpr_amd.demo"):
-    logger = logging.getLogger(name)
-    logger.setLevel(logging.INFO)
-    if not logger.handlers:
-        h = logging.StreamHandler(sys.stdout)
-        h.setFormatter(logging.Formatter("%(asctime)s  %(levelname)5s  %(message)s"))
-        logger.addHandler(h)
-    return logger
 
 
 def run(args, cfg, logger, device="cuda:0"):
@@ -213,7 +200,7 @@ def run(args, cfg, logger, device="cuda:0"):
 
 def main(argv=None):
     args, cfg = parse_config(argv)
-    logger = create_logger()
+    logger = create_logger(name="hvpr_amd.demo")
     logger.info("-----------------Quick Demo of hvpr_amd-------------------------")
     return run(args, cfg, logger)
 

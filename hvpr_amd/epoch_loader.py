@@ -26,11 +26,8 @@ import torch
 
 from .augment import ObjectBank
 from .batch_loader import DeviceBatchLoader
+from .config import _get
 from .kitti_dataset import KittiDataset
-
-
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
 
 
 class EpochSampler:

@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import kernels, kitti_eval, kitti_eval_device as KD
+from .calibration import CALIB_WORDS, pack_calib
 
-CALIB_WORDS = 26
 N_READS = 0                                            # calls of _read so far (tests and tools/bench_eval_tail.py watch it)
 
 
@@ -28,24 +28,6 @@ def _read(t):
     global N_READS
     N_READS += 1
     return t.cpu().numpy()
-
-
-def _calib_parts(calib):
-    if isinstance(calib, dict):
-        return calib["Tr_velo2cam"], calib["R0"], calib["P2"]
-    return calib.V2C, calib.R0, calib.P2               # the reference's Calibration object
-
-
-def pack_calib(calibs, image_shapes):
-    """(B, 26) float32, one row per frame: the 4 x 3 product np.dot(V2C.T, R0.T) formed in float32 as calibration_kitti.py:71 forms
-    it (row-major), P2 (3 x 4, row-major), image height, image width."""
-    out = np.zeros((len(calibs), CALIB_WORDS), np.float32)
-    for i, (c, shape) in enumerate(zip(calibs, image_shapes)):
-        V2C, R0, P2 = (np.asarray(m, np.float32) for m in _calib_parts(c))
-        out[i, 0:12] = np.dot(V2C.T, R0.T).astype(np.float32).reshape(-1)
-        out[i, 12:24] = P2.reshape(-1)
-        out[i, 24], out[i, 25] = float(shape[0]), float(shape[1])
-    return out
 
 
 def class_of_label(class_names):

@@ -14,17 +14,16 @@ import copy
 import datetime
 import glob
 import json
-import logging
 import os
 import re
-import sys
 import time
 from pathlib import Path
 
 import torch
 
 from . import distributed
-from .config import cfg_from_list, cfg_from_yaml_file
+from .common_utils import create_logger
+from .config import _get, cfg_from_list, cfg_from_yaml_file
 
 REPO_ROOT = Path(__file__).resolve().parent.parent
 
@@ -96,19 +95,7 @@ def eval_dir_of(args, cfg, output_dir):
 
 def test_split(cfg):
     from .kitti_dataset import DEFAULT_SPLIT
-    return (cfg.DATA_CONFIG["DATA_SPLIT"] if "DATA_SPLIT" in cfg.DATA_CONFIG else DEFAULT_SPLIT)["test"]
-
-
-def create_logger(log_file=None, rank=0, name="hvpr_amd"):
-    logger = logging.getLogger("%s.%d.%s" % (name, os.getpid(), log_file))
-    logger.setLevel(logging.INFO if rank == 0 else logging.ERROR)
-    logger.propagate = False
-    fmt = logging.Formatter("%(asctime)s  %(levelname)5s  %(message)s")
-    handlers = [logging.StreamHandler(sys.stdout)] + ([logging.FileHandler(str(log_file))] if log_file is not None and rank == 0 else [])
-    for h in handlers:
-        h.setFormatter(fmt)
-        logger.addHandler(h)
-    return logger
+    return _get(cfg.DATA_CONFIG, "DATA_SPLIT", DEFAULT_SPLIT)["test"]
 
 
 def init_launcher(args, cfg):

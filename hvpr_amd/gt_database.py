@@ -22,6 +22,8 @@ import torch
 
 from . import kernels
 from .augment import ObjectBank
+from .calibration import CALIB_WORDS, pack_calib
+from .preprocess import PinnedBuffer
 
 MAX_FRAME_BOXES = 256
 
@@ -30,64 +32,99 @@ def _align(n, a=256):
     return (n + a - 1) // a * a
 
 
-class _Chunk:
-    """A chunk's inputs in one pinned staging buffer, uploaded with one copy: pt_off, box_off (int32), boxes (float32), centres
-    (float64) and, where the frames came from the host, the points.  The host views stay valid for the library's checks."""
+def chunk_layout(B, n_boxes, n_points, F, centres=False, calib=False, points=False):
+    """({section: byte offset}, total bytes) of a chunk of B frames in its staging buffer, every section 256-byte aligned.  pt_off
+    and box_off (int32, B + 1 each) and boxes (float32, 7 a box) are always there; centres (float64, 3 a box), calib (float32,
+    CALIB_WORDS a frame) and points (float32, F a point) where asked for: a section that is not takes no bytes."""
+    sizes = [("pt_off", 4 * (B + 1)), ("box_off", 4 * (B + 1))] + ([("calib", 4 * CALIB_WORDS * B)] if calib else []) \
+        + [("boxes", 28 * n_boxes)] + ([("centres", 24 * n_boxes)] if centres else []) + ([("points", 4 * F * n_points)] if points else [])
+    offsets, total = {}, 0
+    for name, size in sizes:
+        offsets[name], total = total, total + _align(size)
+    return offsets, total
 
-    def __init__(self, points_list, boxes_list, device, stage):
+
+def _view(buf, offset, dtype, *shape):
+    """`shape` elements of `dtype` at byte `offset` of the uint8 tensor `buf`: the staging buffer or its device copy."""
+    return buf[offset: offset + int(np.prod(shape)) * dtype.itemsize].view(dtype).view(*shape)
+
+
+class StagedChunk:
+    """A chunk's inputs in one pinned staging buffer (`stage`, a preprocess.PinnedBuffer of uint8 that may be shared by the chunks
+    of a run), uploaded with one copy: pt_off, box_off (int32), boxes (float32); with `centres` the float64 box centres the
+    database's extract call takes; with `calibs` and `image_shapes` the calibration table (calibration.pack_calib) of get_infos'
+    count; and, where the frames came from the host, the points.  Frames that are on the device already stay there.  The host
+    views stay valid for the library's checks."""
+
+    def __init__(self, points_list, boxes_list, device, stage=None, centres=False, calibs=None, image_shapes=None):
         dev = torch.device(device)
         B = len(points_list)
         F = {int(p.shape[1]) for p in points_list}
         if len(F) != 1:
             raise ValueError("frames of one chunk must share a point feature width")
-        self.F = F.pop()
+        self.F = F = F.pop()
         n_pts = [int(p.shape[0]) for p in points_list]
         n_box = [int(b.shape[0]) for b in boxes_list]
         if max(n_box) > MAX_FRAME_BOXES:
             raise ValueError(f"a frame may hold {MAX_FRAME_BOXES} boxes, got {max(n_box)}")
         N, M = sum(n_pts), sum(n_box)
         on_host = all(isinstance(p, np.ndarray) for p in points_list)
-        o_pt, o_box = 0, _align(4 * (B + 1))
-        o_boxes = o_box + _align(4 * (B + 1))
-        o_ctr = o_boxes + _align(28 * M)
-        o_pts = o_ctr + _align(24 * M)
-        total = o_pts + (_align(4 * self.F * N) if on_host else 0)
-        if stage[0] is None or stage[0].numel() < total:
-            stage[0] = torch.empty((max(total, 1 << 16),), dtype=torch.uint8).pin_memory()
-        host = stage[0][:total]
+        at, total = chunk_layout(B, M, N, F, centres=centres, calib=calibs is not None, points=on_host)
+        host = (stage if stage is not None else PinnedBuffer(torch.uint8, 1 << 16)).take(total)
 
-        def hv(o, count, tdtype, width):
-            return host[o: o + count * width].view(tdtype)
+        def sections(buf):
+            return {"pt_off": _view(buf, at["pt_off"], torch.int32, B + 1), "box_off": _view(buf, at["box_off"], torch.int32, B + 1),
+                    "boxes": _view(buf, at["boxes"], torch.float32, M, 7),
+                    "centres": _view(buf, at["centres"], torch.float64, M, 3) if centres else None,
+                    "calib": _view(buf, at["calib"], torch.float32, B, CALIB_WORDS) if calibs is not None else None,
+                    "points": _view(buf, at["points"], torch.float32, N, F) if on_host else None}
 
-        self.pt_off_host, self.box_off_host = hv(o_pt, B + 1, torch.int32, 4), hv(o_box, B + 1, torch.int32, 4)
-        boxes_h, ctr_h = hv(o_boxes, 7 * M, torch.float32, 4).view(M, 7), hv(o_ctr, 3 * M, torch.float64, 8).view(M, 3)
+        h = sections(host)
+        self.pt_off_host, self.box_off_host, self.calib_host = h["pt_off"], h["box_off"], h["calib"]
         self.pt_off_host.numpy()[:] = np.concatenate([[0], np.cumsum(n_pts)])
         self.box_off_host.numpy()[:] = np.concatenate([[0], np.cumsum(n_box)])
+        if calibs is not None:
+            self.calib_host.numpy()[:] = pack_calib(calibs, image_shapes)
         if M:
             b64 = np.concatenate([np.asarray(b, np.float64).reshape(-1, b.shape[1])[:, :7] for b in boxes_list if b.shape[0]], axis=0)
-            boxes_h.numpy()[:] = b64.astype(np.float32)
-            ctr_h.numpy()[:] = b64[:, :3]
+            h["boxes"].numpy()[:] = b64.astype(np.float32)
+            if centres:
+                h["centres"].numpy()[:] = b64[:, :3]
         if on_host and N:
-            pts_h = hv(o_pts, self.F * N, torch.float32, 4).view(N, self.F)
-            np.concatenate([np.asarray(p, np.float32) for p in points_list], axis=0, out=pts_h.numpy())
-        d = host.to(dev, non_blocking=True)                                      # the one upload of the chunk
-
-        def dv(o, count, tdtype, width):
-            return d[o: o + count * width].view(tdtype)
-
-        self.pt_off, self.box_off = dv(o_pt, B + 1, torch.int32, 4), dv(o_box, B + 1, torch.int32, 4)
-        self.boxes, self.centres = dv(o_boxes, 7 * M, torch.float32, 4).view(M, 7), dv(o_ctr, 3 * M, torch.float64, 8).view(M, 3)
+            np.concatenate([np.asarray(p, np.float32) for p in points_list], axis=0, out=h["points"].numpy())
+        d = sections(host.to(dev, non_blocking=True))                            # the one upload of the chunk
+        self.pt_off, self.box_off, self.boxes, self.centres, self.calib = d["pt_off"], d["box_off"], d["boxes"], d["centres"], d["calib"]
         if on_host:
-            self.points = dv(o_pts, self.F * N, torch.float32, 4).view(N, self.F)
+            self.points = d["points"]
         else:                                                                    # frames that are on the device already stay there
             per = [torch.from_numpy(np.ascontiguousarray(p, np.float32)).to(dev) if isinstance(p, np.ndarray)
                    else p.to(dev, torch.float32) for p in points_list]
             self.points = (per[0] if B == 1 else torch.cat(per, dim=0)).contiguous()
         self.n_obj, self.n_box = M, n_box
 
-    def count(self, workspace=None):
-        return kernels.gt_database_count(self.points, self.pt_off_host, self.pt_off, self.boxes, self.box_off_host, self.box_off,
-                                         workspace=workspace)
+    def count(self, workspace=None, want_fov=False):
+        """(obj_count, fov_count, workspace).  With a calibration table get_infos' count: per box the points in the camera's view
+        and inside it, and with `want_fov` per frame the points in view.  Without one the database's: every point of the frame
+        counts, fov_count is None, and the workspace goes to gt_database_extract."""
+        chunk = (self.points, self.pt_off_host, self.pt_off, self.boxes, self.box_off_host, self.box_off)
+        if self.calib is None:
+            obj_count, workspace = kernels.gt_database_count(*chunk, workspace=workspace)
+            return obj_count, None, workspace
+        return kernels.kitti_infos_count(*chunk, self.calib_host, self.calib, want_fov=want_fov, workspace=workspace)
+
+
+class CountReader:
+    """The grown pinned stage of a chunk's counts and the chunk's ONE synchronising read; `reads` counts them."""
+
+    def __init__(self):
+        self._stage, self.reads = PinnedBuffer(torch.int32, 1024), 0
+
+    def __call__(self, counts_dev):
+        """The int32 host tensor of `counts_dev`, valid until the next call."""
+        host = self._stage.take(counts_dev.numel())
+        host.copy_(counts_dev)                                                   # the one read of the chunk (synchronises)
+        self.reads += 1
+        return host
 
 
 def _boxes_of(b):
@@ -105,12 +142,12 @@ def count_points_in_boxes(points_list, boxes_list, device="cuda:0", frames_per_c
     test over the points in the camera's view: that count is hvpr_amd.kitti_dataset's (InfoCounter, KittiDataset.get_infos)."""
     if len(points_list) != len(boxes_list):
         raise ValueError("count_points_in_boxes: one box array per frame")
-    out, stage, ws = [], [None], None
+    out, stage, read, ws = [], PinnedBuffer(torch.uint8, 1 << 16), CountReader(), None
     for c0 in range(0, len(points_list), int(frames_per_call)):
-        chunk = _Chunk([_points_of(p) for p in points_list[c0: c0 + frames_per_call]],
-                       [_boxes_of(b) for b in boxes_list[c0: c0 + frames_per_call]], device, stage)
-        counts, ws = chunk.count(ws)
-        counts = counts.cpu().numpy()
+        chunk = StagedChunk([_points_of(p) for p in points_list[c0: c0 + frames_per_call]],
+                            [_boxes_of(b) for b in boxes_list[c0: c0 + frames_per_call]], device, stage)
+        counts, _, ws = chunk.count(ws)
+        counts = read(counts).numpy()
         off = chunk.box_off_host.numpy()
         out.extend(counts[off[f]: off[f + 1]].copy() for f in range(len(chunk.n_box)))
     return out
@@ -133,7 +170,7 @@ class DatabaseBuilder:
         self.objects = []                     # every object in the reference's order: (record, used, first row, rows)
         self._arena = torch.empty((0, self.num_point_features), dtype=torch.float32, device=self.device)
         self._rows = 0
-        self._stage, self._count_stage, self._ws = [None], None, None
+        self._stage, self._read, self._ws = PinnedBuffer(torch.uint8, 1 << 16), CountReader(), None
 
     def _reserve(self, rows):
         if self._rows + rows > self._arena.shape[0]:
@@ -151,14 +188,11 @@ class DatabaseBuilder:
         pts = [_points_of(get_lidar(info["point_cloud"]["lidar_idx"])) for info in infos]
         if any(int(p.shape[1]) != self.num_point_features for p in pts):
             raise ValueError(f"get_lidar must return (N, {self.num_point_features}) points")
-        chunk = _Chunk(pts, [np.asarray(info["annos"]["gt_boxes_lidar"]) for info in infos], self.device, self._stage)
+        chunk = StagedChunk(pts, [np.asarray(info["annos"]["gt_boxes_lidar"]) for info in infos], self.device, self._stage, centres=True)
         if chunk.n_obj == 0:
             return
-        counts_dev, self._ws = chunk.count(self._ws)
-        if self._count_stage is None or self._count_stage.numel() < chunk.n_obj:
-            self._count_stage = torch.empty((max(chunk.n_obj, 1024),), dtype=torch.int32).pin_memory()
-        counts_host = self._count_stage[: chunk.n_obj]
-        counts_host.copy_(counts_dev)                                            # the one read of the chunk (synchronises)
+        counts_dev, _, self._ws = chunk.count(self._ws)
+        counts_host = self._read(counts_dev)
         counts = counts_host.numpy()
         rows = int(counts.sum(dtype=np.int64))
         self._reserve(rows)

@@ -4,8 +4,10 @@ Every wrapper hands its tensors and the current HIP stream to _lib.call, which c
 parameter (device, dtype, contiguity), passes its pointer and raises on a non-zero status.  There is no CPU path: CPU
 tensors are rejected.  Host-side arguments (pinned host tensors, numpy and ctypes arrays) go as raw addresses.
 """
+import ctypes
 import os
 
+import numpy as np
 import torch
 
 from ._lib import call, check, lib  # noqa: F401  (check: callers reach it as kernels.check)
@@ -862,7 +864,6 @@ def kitti_match(gt_rows, gt_cls, gt_dontcare, dt_rows, dt_cls, gt_off, dt_off, p
     (host).  Without thresholds, the threshold pass -> (tp_score [combos, NG] f64, n_valid [n_classes, 3] i32); with thresholds
     [combos, T] f64 and thresh_count [combos] i32 (cuda), the counting pass -> (counts [combos, T, 3] i32, sim [combos, T] f64).
     `out`: the pair of tensors to fill instead of new ones."""
-    import ctypes
     dev = pair_off.device
     F, NG = pair_off.numel() - 1, gt_rows.shape[0]
     C, K = len(classes), len(min_overlaps)
@@ -889,7 +890,6 @@ def recall_record(pred_boxes, pred_count, gt_boxes, thresholds, counts=None, bes
     """generate_recall_record for every frame of a batch, no host read.  pred_boxes (B, P, 7) f32 with pred_count (B,) i32 live
     rows; gt_boxes (B, G, C >= 7) f32; thresholds: at most 8 host floats.  -> counts (B, 1 + T) i32 = ground truths, then the
     recalled ones per threshold.  best_iou: an optional (B, G) f32 tensor to fill."""
-    import ctypes
     B, P = int(pred_boxes.shape[0]), int(pred_boxes.shape[1])
     if pred_boxes.dim() != 3 or pred_boxes.shape[2] != 7 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or pred_count.numel() != B:
         raise ValueError("recall_record: pred_boxes (B, P, 7), pred_count (B,) and gt_boxes (B, G, C) must agree")
@@ -907,8 +907,7 @@ def prediction_annos(pred_boxes, pred_scores, pred_labels, pred_count, calib, cl
                      dt_label, dt_box7, boxes_lidar, dt_off, overflow):
     """generate_prediction_dicts for a batch into the caller's split-wide tables, no host read: frame b's live rows follow frame
     b - 1's from row_base[0] (a device int64 word, advanced here) on; dt_off[frame_base + b + 1] is set.  calib (B, 26) f32 cuda
-    (eval_loop.pack_calib), class_of_label: host ints, label - 1 -> evaluator class id."""
-    import ctypes
+    (calibration.pack_calib), class_of_label: host ints, label - 1 -> evaluator class id."""
     B, P = int(pred_boxes.shape[0]), int(pred_boxes.shape[1])
     if tuple(pred_boxes.shape) != (B, P, 7) or tuple(pred_scores.shape) != (B, P) or tuple(pred_labels.shape) != (B, P) \
             or pred_count.numel() != B or tuple(calib.shape) != (B, 26):
@@ -941,7 +940,6 @@ def augment_collide(plan_host, plan_dev, words):
 
 def augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_outside, g_cap, out=None, count=None):
     """(gt_boxes (B, g_cap, 8), count (B,) int32)."""
-    import numpy as np
     B = int(plan_host.numpy()[1])
     rng6 = np.ascontiguousarray(point_cloud_range, np.float32)
     if out is None:
@@ -957,7 +955,6 @@ def augment_boxes(plan_host, plan_dev, words, valid, point_cloud_range, remove_o
 def augment_points(plan_host, plan_dev, words, valid, points, bank_points, bank_boxes, extra_width, out=None, out_off=None):
     """(out_points (capacity, F), out_off (B+1,) int32).  capacity = scene points + the points of all candidates, known on the
     host: nothing is read to allocate."""
-    import numpy as np
     h = plan_host.numpy()                      # the host copy: header B, NG, G, C; pt_off and cand_n as csrc/augment.hip lays them out
     B, NG, G, C = int(h[1]), int(h[2]), int(h[3]), int(h[4])
     n, F = points.shape
@@ -994,11 +991,14 @@ def gt_database_block_points():
     return int(lib().hvpr_gt_database_block_points())
 
 
-def _gt_database_workspace(pt_off_host, n_obj, device, workspace):
-    import numpy as np
+def _chunk_count_prologue(pt_off_host, n_obj, device, obj_count, workspace, workspace_bytes):
+    """(obj_count, workspace) as both count calls of a staged chunk begin: the largest frame from the host offsets, the workspace
+    `workspace_bytes(B, largest frame, n_obj)` asks for, and `obj_count` (n_obj,) int32 where none is given."""
     off = pt_off_host.numpy()
     max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
-    return _workspace(workspace, lib().hvpr_gt_database_workspace_bytes(off.shape[0] - 1, max_frame, int(n_obj)), device)
+    if obj_count is None:
+        obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=device)[:n_obj]
+    return obj_count, _workspace(workspace, workspace_bytes(off.shape[0] - 1, max_frame, n_obj), device)
 
 
 def gt_database_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off, obj_count=None, workspace=None):
@@ -1007,9 +1007,8 @@ def gt_database_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off,
     them before it launches anything.  The workspace goes to gt_database_extract of the same chunk."""
     n, F = points.shape
     n_obj, B = int(boxes.shape[0]), pt_off_host.numel() - 1
-    if obj_count is None:
-        obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=points.device)[:n_obj]
-    workspace = _gt_database_workspace(pt_off_host, n_obj, points.device, workspace)
+    obj_count, workspace = _chunk_count_prologue(pt_off_host, n_obj, points.device, obj_count, workspace,
+                                                 lib().hvpr_gt_database_workspace_bytes)
     # the *_host tensors live in host memory: raw addresses
     call("hvpr_gt_database_count_f32", points, n, F, pt_off_host.data_ptr(), pt_off, B, boxes, box_off_host.data_ptr(), box_off, n_obj,
          obj_count, workspace, workspace.numel(), _stream())
@@ -1042,22 +1041,18 @@ def kitti_infos_count(points, pt_off_host, pt_off, boxes, box_off_host, box_off,
                       want_fov=False, workspace=None):
     """(obj_count (n_obj,) int32, fov_count (B,) int32 or None, workspace): per box the points of its frame in the camera's view
     and inside it, per frame (with `want_fov` or a `fov_count` tensor) the points in view.  The chunk as gt_database_count takes
-    it; `calib_host` is the (B, 26) float32 host tensor (eval_loop.pack_calib) the device copy `calib` was made from.  The library
+    it; `calib_host` is the (B, 26) float32 host tensor (calibration.pack_calib) the device copy `calib` was made from.  The library
     checks the host copies before it launches anything."""
-    import numpy as np
     n, F = points.shape
     n_obj, B = int(boxes.shape[0]), pt_off_host.numel() - 1
     if calib_host.dtype != torch.float32 or calib_host.numel() != 26 * B or not calib_host.is_contiguous() or calib_host.is_cuda:
         raise ValueError("kitti_infos_count: calib_host must be a contiguous (B, 26) float32 host tensor")
     if calib.numel() != 26 * B:
         raise ValueError("kitti_infos_count: calib must be (B, 26)")
-    if obj_count is None:
-        obj_count = torch.empty((max(n_obj, 1),), dtype=torch.int32, device=points.device)[:n_obj]
     if fov_count is None and want_fov:
         fov_count = torch.empty((B,), dtype=torch.int32, device=points.device)
-    off = pt_off_host.numpy()
-    max_frame = int(np.diff(off).max()) if off.shape[0] > 1 else 0
-    workspace = _workspace(workspace, lib().hvpr_kitti_infos_workspace_bytes(B, max_frame, n_obj), points.device)
+    obj_count, workspace = _chunk_count_prologue(pt_off_host, n_obj, points.device, obj_count, workspace,
+                                                 lib().hvpr_kitti_infos_workspace_bytes)
     # the *_host tensors live in host memory: raw addresses
     call("hvpr_kitti_infos_count_f32", points, n, F, pt_off_host.data_ptr(), pt_off, B, boxes, box_off_host.data_ptr(), box_off, n_obj,
          calib_host.data_ptr(), calib, obj_count, fov_count, workspace, workspace.numel(), _stream())
@@ -1080,7 +1075,6 @@ def _workspace(workspace, need, device):
 def _ragged_head(points, off, mask, calib, range_xy):
     """(rows, F, B, head, range): `head` is the arguments every hvpr_ragged_* call begins with; `range` owns the host floats
     `head` points to and has to outlive the call."""
-    import numpy as np
     rows, F = points.shape
     B = off.numel() - 1
     r = None if range_xy is None else np.ascontiguousarray(range_xy, np.float32).reshape(4)
@@ -1102,7 +1096,7 @@ def _out_and_flag(out, flag, rows, width, device):
 
 def ragged_select_count(points, off, mask, calib=None, range_xy=None, new_off=None, workspace=None):
     """(new_off (B+1,) int32, workspace).  points (rows, F) float32 and off (B+1,) int32 on the device, `calib` (B, 26) float32
-    on the device (eval_loop.pack_calib) for mask bit 1, `range_xy` four host floats (x0, y0, x1, y1) for mask bit 2.  Rows at or
+    on the device (calibration.pack_calib) for mask bit 1, `range_xy` four host floats (x0, y0, x1, y1) for mask bit 2.  Rows at or
     past off[B] are ignored.  Nothing is read: the workspace goes to ragged_select_write of the same input."""
     rows, F, B, head, _r = _ragged_head(points, off, mask, calib, range_xy)
     new_off = _offsets(new_off, B, points.device)
@@ -1151,7 +1145,6 @@ def ragged_sample_write(points, off, mask, new_off, near_off, mode, dest, num_po
 # ------------------------------------------------------------------------------------------------ v1: the BEV picture
 def bev_grid(point_cloud_range, pixel):
     """(H, W) of the picture: round((hi - lo) / pixel) in float32, y cells by x cells (tools/vis.py:90-91)."""
-    import numpy as np
     r = np.ascontiguousarray(point_cloud_range, np.float32).reshape(6)
     g = np.round((r[3:5] - r[:2]) / np.float32(pixel)).astype(np.int64)
     return int(g[1]), int(g[0])
@@ -1164,7 +1157,6 @@ def render_bev(points, frame_offsets, point_cloud_range, pixel, palette, tables=
     table is a dict: `boxes` (B, P, >= 7) float32, optionally `count` (B,) int32, `scores` (B, P) float32 with `thresh`, `labels`
     (B, P) int64, and `ink` (a row's ink is ink + label; ink alone without labels).  `palette` (n_ink, 3) uint8 on the device,
     ink 0 unused.  heading_sign -1 draws a lidar heading as it is, +1 mirrored as the reference does.  Only enqueues."""
-    import numpy as np
     tables = list(tables)
     if len(tables) > 2:
         raise ValueError("render_bev: two box tables at the most")

@@ -26,8 +26,10 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import eval_loop, kernels
-from .gt_database import MAX_FRAME_BOXES, _align
+from .calibration import rect_to_lidar
+from .config import _get
+from .gt_database import CountReader, StagedChunk
+from .preprocess import PinnedBuffer, to_device
 
 DEFAULT_SPLIT = {"train": "train", "test": "val"}
 DEFAULT_INFO_PATH = {"train": ["kitti_infos_train.pkl"], "test": ["kitti_infos_val.pkl"]}
@@ -97,15 +99,6 @@ def read_split(root_path, split):
 
 
 # ------------------------------------------------------------------------------------------------ geometry (host, per box)
-def rect_to_lidar(pts_rect, calib):
-    """calibration_kitti.py:50-63: float32 in, float32 out, through a float32 4 x 4 inverse."""
-    hom = np.hstack((pts_rect, np.ones((pts_rect.shape[0], 1), dtype=np.float32)))
-    R0, V2C = np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float32)
-    R0[:3, :3], V2C[:3, :4] = calib["R0"], calib["Tr_velo2cam"]
-    R0[3, 3] = V2C[3, 3] = 1
-    return np.dot(hom, np.linalg.inv(np.dot(R0, V2C).T))[:, 0:3]
-
-
 def boxes3d_kitti_camera_to_lidar(boxes3d_camera, calib):
     """box_utils.py:91-105: (N, 7) camera boxes [x, y, z, l, h, w, r] to lidar boxes, in the dtype the input has."""
     l, h, w, r = (boxes3d_camera[:, i: i + 1] for i in (3, 4, 5, 6))
@@ -147,66 +140,7 @@ def _calib_info(calib):
             "Tr_velo_to_cam": np.concatenate([calib["Tr_velo2cam"], last], axis=0)}
 
 
-# ------------------------------------------------------------------------------------------------ a chunk on the device
-class _InfoChunk:
-    """A chunk's inputs in one pinned staging buffer, uploaded with one copy: pt_off, box_off (int32), the calibration table
-    (eval_loop.pack_calib), the boxes (float32) and, where the frames came from the host, the points.  A sibling of
-    gt_database._Chunk, which carries float64 centres instead of the calibration and stays as it is."""
-
-    def __init__(self, points_list, boxes_list, calibs, image_shapes, device, stage):
-        dev = torch.device(device)
-        B = len(points_list)
-        F = {int(p.shape[1]) for p in points_list}
-        if len(F) != 1:
-            raise ValueError("frames of one chunk must share a point feature width")
-        self.F = F.pop()
-        n_pts = [int(p.shape[0]) for p in points_list]
-        n_box = [int(b.shape[0]) for b in boxes_list]
-        if max(n_box) > MAX_FRAME_BOXES:
-            raise ValueError(f"a frame may hold {MAX_FRAME_BOXES} boxes, got {max(n_box)}")
-        N, M = sum(n_pts), sum(n_box)
-        on_host = all(isinstance(p, np.ndarray) for p in points_list)
-        o_pt, o_box = 0, _align(4 * (B + 1))
-        o_cal = o_box + _align(4 * (B + 1))
-        o_boxes = o_cal + _align(4 * eval_loop.CALIB_WORDS * B)
-        o_pts = o_boxes + _align(28 * M)
-        total = o_pts + (_align(4 * self.F * N) if on_host else 0)
-        if stage[0] is None or stage[0].numel() < total:
-            stage[0] = torch.empty((max(total, 1 << 16),), dtype=torch.uint8).pin_memory()
-        host = stage[0][:total]
-        d = [None]
-
-        def view(o, count, tdtype, on_device=False):
-            return (d[0] if on_device else host)[o: o + 4 * count].view(tdtype)
-
-        self.pt_off_host, self.box_off_host = view(o_pt, B + 1, torch.int32), view(o_box, B + 1, torch.int32)
-        self.calib_host = view(o_cal, eval_loop.CALIB_WORDS * B, torch.float32).view(B, eval_loop.CALIB_WORDS)
-        self.pt_off_host.numpy()[:] = np.concatenate([[0], np.cumsum(n_pts)])
-        self.box_off_host.numpy()[:] = np.concatenate([[0], np.cumsum(n_box)])
-        self.calib_host.numpy()[:] = eval_loop.pack_calib(calibs, image_shapes)
-        if M:
-            view(o_boxes, 7 * M, torch.float32).view(M, 7).numpy()[:] = np.concatenate(
-                [np.asarray(b, np.float64).reshape(-1, b.shape[1])[:, :7] for b in boxes_list if b.shape[0]], axis=0).astype(np.float32)
-        if on_host and N:
-            np.concatenate([np.asarray(p, np.float32) for p in points_list], axis=0,
-                           out=view(o_pts, self.F * N, torch.float32).view(N, self.F).numpy())
-        d[0] = host.to(dev, non_blocking=True)                                   # the one upload of the chunk
-        self.pt_off, self.box_off = view(o_pt, B + 1, torch.int32, True), view(o_box, B + 1, torch.int32, True)
-        self.calib = view(o_cal, eval_loop.CALIB_WORDS * B, torch.float32, True).view(B, eval_loop.CALIB_WORDS)
-        self.boxes = view(o_boxes, 7 * M, torch.float32, True).view(M, 7)
-        if on_host:
-            self.points = view(o_pts, self.F * N, torch.float32, True).view(N, self.F)
-        else:                                                                    # frames that are on the device already stay there
-            per = [torch.from_numpy(np.ascontiguousarray(p, np.float32)).to(dev) if isinstance(p, np.ndarray)
-                   else p.to(dev, torch.float32) for p in points_list]
-            self.points = (per[0] if B == 1 else torch.cat(per, dim=0)).contiguous()
-        self.n_obj, self.n_box = M, n_box
-
-    def count(self, workspace=None, want_fov=False):
-        return kernels.kitti_infos_count(self.points, self.pt_off_host, self.pt_off, self.boxes, self.box_off_host, self.box_off,
-                                         self.calib_host, self.calib, want_fov=want_fov, workspace=workspace)
-
-
+# ------------------------------------------------------------------------------------------------ the counts of a chunk
 class InfoCounter:
     """get_infos' count path on its own: `count(points_list, boxes_list, calibs, image_shapes)` -> per frame an (n_i,) int32 array
     of the points in the camera's view and inside each box.  points (N_i, F) on the host or the device, boxes (n_i, 7+) lidar boxes
@@ -215,34 +149,29 @@ class InfoCounter:
 
     def __init__(self, device="cuda:0", frames_per_call=32):
         self.device, self.frames_per_call = torch.device(device), max(1, int(frames_per_call))
-        self._stage, self._ws, self._count_stage = [None], None, None
-        self.reads = 0
+        self._stage, self._ws, self._read = PinnedBuffer(torch.uint8, 1 << 16), None, CountReader()
+
+    @property
+    def reads(self):
+        return self._read.reads
 
     def count(self, points_list, boxes_list, calibs, image_shapes):
         out = []
         for c0 in range(0, len(points_list), self.frames_per_call):
             c1 = c0 + self.frames_per_call
             boxes = [np.asarray(b).reshape(-1, 7) if np.asarray(b).size == 0 else np.asarray(b) for b in boxes_list[c0:c1]]
-            chunk = _InfoChunk(points_list[c0:c1], boxes, calibs[c0:c1], image_shapes[c0:c1], self.device, self._stage)
+            chunk = StagedChunk(points_list[c0:c1], boxes, self.device, self._stage, calibs=calibs[c0:c1], image_shapes=image_shapes[c0:c1])
             if chunk.n_obj == 0:
                 out.extend(np.zeros((0,), np.int32) for _ in chunk.n_box)
                 continue
             counts_dev, _, self._ws = chunk.count(self._ws)
-            if self._count_stage is None or self._count_stage.numel() < chunk.n_obj:
-                self._count_stage = torch.empty((max(chunk.n_obj, 1024),), dtype=torch.int32).pin_memory()
-            counts_host = self._count_stage[: chunk.n_obj]
-            counts_host.copy_(counts_dev)                                        # the one read of the chunk (synchronises)
-            self.reads += 1
+            counts = self._read(counts_dev).numpy()
             off = chunk.box_off_host.numpy()
-            out.extend(counts_host.numpy()[off[f]: off[f + 1]].copy() for f in range(len(chunk.n_box)))
+            out.extend(counts[off[f]: off[f + 1]].copy() for f in range(len(chunk.n_box)))
         return out
 
 
 # ------------------------------------------------------------------------------------------------ the dataset
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
-
-
 class KittiDataset:
     """dataset_cfg: the DATA_CONFIG block; DATA_SPLIT and INFO_PATH default to the reference's kitti_dataset.yaml (train / val,
     kitti_infos_train.pkl / kitti_infos_val.pkl)."""
@@ -336,10 +265,7 @@ class KittiDataset:
         info = self.kitti_infos[index]
         sample_idx = info["point_cloud"]["lidar_idx"]
         calib = self.get_calib(sample_idx)
-        points = torch.from_numpy(self.get_lidar(sample_idx))
-        if self.device.type == "cuda":                       # through pinned memory: the upload does not synchronise the host
-            points = points.pin_memory()
-        out = {"points": points.to(self.device, non_blocking=True), "frame_id": sample_idx, "calib": calib,
+        out = {"points": to_device(self.get_lidar(sample_idx), self.device), "frame_id": sample_idx, "calib": calib,
                "image_shape": info["image"]["image_shape"]}
         if "annos" in info:
             annos = info["annos"]

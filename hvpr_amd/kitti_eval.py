@@ -12,6 +12,8 @@ Metric code, not on the timed path.  The rotated-BEV intersection comes from the
 """
 import numpy as np
 
+from . import calibration
+
 CLASS_TO_NAME = {0: "Car", 1: "Pedestrian", 2: "Cyclist", 3: "Van", 4: "Person_sitting", 5: "Truck"}
 _MIN_HEIGHT, _MAX_OCCLUSION, _MAX_TRUNCATION = (40, 25, 25), (0, 1, 2), (0.15, 0.3, 0.5)
 _N_SAMPLE = 41
@@ -236,16 +238,13 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, rotated_inters
 
 
 # ------------------------------------------------------------------------------------------------ prediction formatting
-def lidar_to_rect(xyz, calib):
-    hom = np.hstack((xyz, np.ones((xyz.shape[0], 1), dtype=np.float32)))
-    return np.dot(hom, np.dot(np.asarray(calib["Tr_velo2cam"], np.float32).T, np.asarray(calib["R0"], np.float32).T))
-
-
 def boxes3d_lidar_to_kitti_camera(boxes, calib):
     """(N,7) lidar [x,y,z,dx,dy,dz,heading], centre -> camera [x,y,z,l,h,w,ry], bottom centre (box_utils.py:152-166)."""
     b = np.array(boxes, dtype=np.float32, copy=True)
     b[:, 2] -= b[:, 5] / 2
-    return np.concatenate([lidar_to_rect(b[:, 0:3], calib), b[:, 3:4], b[:, 5:6], b[:, 4:5], -b[:, 6:7] - np.pi / 2], axis=-1)
+    # the transform runs in float32 whatever is given; P2 takes no part in it
+    f32 = {"Tr_velo2cam": np.asarray(calib["Tr_velo2cam"], np.float32), "R0": np.asarray(calib["R0"], np.float32), "P2": calib.get("P2")}
+    return np.concatenate([calibration.lidar_to_rect(b[:, 0:3], f32), b[:, 3:4], b[:, 5:6], b[:, 4:5], -b[:, 6:7] - np.pi / 2], axis=-1)
 
 
 def boxes3d_kitti_camera_to_imageboxes(boxes_cam, calib, image_shape=None):

@@ -18,6 +18,7 @@ import torch
 
 from . import kernels
 from ._lib import call, lib
+from .calibration import fov_matrices
 
 
 def _flags(points, mode, range_xy=None, near=40.0, fov=None):
@@ -35,14 +36,6 @@ def mask_points_by_range(points, limit_range):
     """points (N, >=3) f32 cuda -> uint8 mask (x and y inside [lo, hi], inclusive)."""
     r = torch.as_tensor(np.asarray(limit_range, np.float32)[[0, 1, 3, 4]], device=points.device)
     return _flags(points.contiguous(), 0, r)
-
-
-def fov_matrices(calib, device):
-    """(V2C^T R0^T) and P2^T as the reference forms them (float32 numpy products), on the device."""
-    V2C, R0, P2 = (np.asarray(calib[k], np.float32) for k in ("Tr_velo2cam", "R0", "P2"))
-    a = np.ascontiguousarray(np.dot(V2C.T, R0.T).astype(np.float32))
-    p = np.ascontiguousarray(P2.T.astype(np.float32))
-    return torch.from_numpy(a).to(device), torch.from_numpy(p).to(device)
 
 
 def get_fov_flag(points, calib, img_shape):
@@ -80,29 +73,51 @@ def shuffle_points(points, rng=np.random):
     return gather_rows(points, torch.from_numpy(np.ascontiguousarray(perm).astype(np.int32)).to(points.device))
 
 
-def sample_points_choice(near, num_points, rng=np.random):
-    """Index selection of DataProcessor.sample_points (data_processor.py:77-108): same RNG call sequence, including the
-    draw at :91 that happens before the size test (so, like the reference, this raises ValueError when more than
-    num_points points lie beyond 40 m)."""
-    n = len(near)
-    if num_points == -1:
-        return np.arange(n)
-    every = np.arange(0, n, dtype=np.int32)
-    if num_points < n:
-        far_idx, near_idx = np.where(near == 0)[0], np.where(near == 1)[0]
-        want = num_points - len(far_idx)
-        drawn = rng.choice(near_idx, want, replace=False)
+def plan_sample_points(n, c, num_points, rng=np.random, shuffle=False):
+    """DataProcessor.sample_points (data_processor.py:77-108) for a frame of n rows of which c are near, from the counts alone:
+    the reference's sequence of generator calls (the draw at :91 in front of the size test included), over ordinals.  Returns a
+    dict: `mode` 0 when an entry of `choice` is a row's in-frame rank, 1 when it is a near ordinal (< c) or c + a far ordinal;
+    `choice`, the reference's `choice` in that form; `perm`, the following `rng.permutation` (None without `shuffle`); `order` =
+    choice[perm], the source of every output row.  Raises what the reference raises."""
+    n, c, P = int(n), int(c), int(num_points)
+    if not 0 <= c <= n:
+        raise ValueError(f"plan_sample_points: {c} near rows of {n}")
+    mode = 0
+    if P == -1:
+        choice = np.arange(n)
+    elif P < n:
+        far, near_ord = n - c, np.arange(c)
+        want = P - far
+        drawn = rng.choice(near_ord, want, replace=False)               # :91, ValueError when more than P rows are far
         if want > 0:
-            drawn = rng.choice(near_idx, want, replace=False)
-            choice = np.concatenate((drawn, far_idx), axis=0) if len(far_idx) > 0 else drawn
+            drawn = rng.choice(near_ord, want, replace=False)
+            choice = np.concatenate((drawn, c + np.arange(far)), axis=0) if far > 0 else drawn
+            mode = 1
         else:
-            choice = rng.choice(every, num_points, replace=False)
+            choice = rng.choice(np.arange(n), P, replace=False)
+        rng.shuffle(choice)
     else:
-        choice = every
-        if num_points > n:
-            choice = np.concatenate((choice, rng.choice(choice, num_points - n, replace=False)), axis=0)
-    rng.shuffle(choice)
-    return choice
+        choice = np.arange(n)
+        if P > n:                                                        # ValueError when P - n > n or the frame is empty
+            choice = np.concatenate((choice, rng.choice(choice, P - n, replace=False)), axis=0)
+        rng.shuffle(choice)
+    perm = rng.permutation(len(choice)) if shuffle else None
+    return {"mode": mode, "choice": choice, "perm": perm, "order": choice if perm is None else choice[perm]}
+
+
+def resolve_sample_choice(plan, near):
+    """The reference's `choice` (row indices) of a plan, given the frame's near flags."""
+    if plan["mode"] == 0:
+        return plan["choice"]
+    near = np.asarray(near) != 0
+    return np.concatenate((np.where(near)[0], np.where(~near)[0]))[plan["choice"]]
+
+
+def sample_points_choice(near, num_points, rng=np.random):
+    """Index selection of DataProcessor.sample_points for one frame whose near flags are on the host: the plan, resolved.  Like
+    the reference, this raises ValueError when more than num_points points lie beyond 40 m."""
+    near = np.asarray(near)
+    return resolve_sample_choice(plan_sample_points(len(near), np.count_nonzero(near), num_points, rng), near)
 
 
 class PointPreprocessor:
@@ -137,6 +152,26 @@ class PointPreprocessor:
 
 
 # ------------------------------------------------------------------------------------------------ f1: host -> device
+def to_device(array, device):
+    """A host array on `device` through pinned memory: the upload does not synchronise the host."""
+    t = torch.from_numpy(np.ascontiguousarray(array))
+    if torch.device(device).type == "cuda":
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+class PinnedBuffer:
+    """A grow-only pinned staging buffer: `take(n)` is its first n elements, allocated anew only when n outgrows it."""
+
+    def __init__(self, dtype=torch.int32, floor=4096):
+        self.dtype, self.floor, self._buf = dtype, int(floor), None
+
+    def take(self, n):
+        if self._buf is None or self._buf.numel() < n:
+            self._buf = torch.empty((max(int(n), self.floor),), dtype=self.dtype).pin_memory()
+        return self._buf[:n]
+
+
 class InputPipeline:
     """collate_batch's `points` branch (dataset.py:161-166: a batch-index column in front of every frame's rows) and
     load_data_to_gpu, as a double-buffered pinned-memory upload on its own HIP stream: frame k+1 is copied while frame k

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import distributed, evaluate as E
+from .common_utils import create_logger
 
 
 def parse_config(argv=None):
@@ -61,7 +62,7 @@ def main(argv=None):
     output_dir = E.output_dir_of(args, cfg)
     ckpt_dir = output_dir / "ckpt"
     ckpt_dir.mkdir(parents=True, exist_ok=True)
-    logger = E.create_logger(output_dir / ("log_train_%s.txt" % datetime.datetime.now().strftime("%Y%m%d-%H%M%S")), rank)
+    logger = create_logger(output_dir / ("log_train_%s.txt" % datetime.datetime.now().strftime("%Y%m%d-%H%M%S")), rank)
     if dist_train:
         logger.info("total_batch_size: %d" % (world * batch_size))
     E.log_run(logger, args, cfg)

@@ -99,6 +99,8 @@ def plain_count_host(points, boxes):
     """The database's count (count_points_in_boxes): the same box test over EVERY point of the frame."""
     from hvpr_amd import gt_sampling
     b32 = np.asarray(boxes, np.float64).reshape(-1, 7).astype(np.float32)
+    if not len(b32):
+        return np.zeros((0,), np.int32)
     inside = gt_sampling.points_in_boxes_cpu(np.ascontiguousarray(np.asarray(points, np.float32)[:, 0:3]), b32)
     return np.asarray(inside).reshape(len(b32), -1).sum(axis=1).astype(np.int32)
 

@@ -28,9 +28,9 @@ def blk_():
 
 def chunk_of(frames, on_device=False):
     import torch
-    from hvpr_amd import kitti_dataset as KD
+    from hvpr_amd import gt_database as GD
     pts = [torch.from_numpy(f["points"]).to(DEV) if on_device else f["points"] for f in frames]
-    return KD._InfoChunk(pts, [f["boxes"] for f in frames], [f["calib"] for f in frames], [f["image_shape"] for f in frames], DEV, [None])
+    return GD.StagedChunk(pts, [f["boxes"] for f in frames], DEV, calibs=[f["calib"] for f in frames], image_shapes=[f["image_shape"] for f in frames])
 
 
 def device_counts(frames, on_device=False):

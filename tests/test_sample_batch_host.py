@@ -1,6 +1,6 @@
 """CPU: `sample_points` for a whole batch.  The planner that draws over ordinals from the two counts of a frame
-(hvpr_amd.batch_loader.plan_sample_points) against the per-frame form that sees the flags (preprocess.sample_points_choice); the
-numpy restatement (tests/sample_batch_cases.py) against fixture G23, the reference's own path
+(hvpr_amd.preprocess.plan_sample_points, which preprocess.sample_points_choice is built on) against the oracle's independent
+per-frame form that sees the flags (oracle.hvpr_oracle.sample_points_choice); the numpy restatement (tests/sample_batch_cases.py) against fixture G23, the reference's own path
 (tests/golden/make_golden_sample_batch.py); the shipped configs; the new entry points of csrc/collate.hip, which make every
 argument check on the host."""
 import ctypes
@@ -47,13 +47,13 @@ def flag_cases():
 
 @pytest.mark.parametrize("shuffle", [False, True])
 def test_planner_equals_the_per_frame_form(shuffle):
-    from hvpr_amd import preprocess as PP
     from hvpr_amd.batch_loader import plan_sample_points, resolve_sample_choice, sample_destinations
+    from oracle import hvpr_oracle as O
     seen = set()
     for k, (name, near, P) in enumerate(flag_cases()):
         n, c = len(near), int(near.sum())
         a, b = np.random.RandomState(900 + k), np.random.RandomState(900 + k)
-        want = PP.sample_points_choice(near, P, a)
+        want = O.sample_points_choice(near, P, a)
         want_perm = a.permutation(len(want)) if shuffle else None
         plan = plan_sample_points(n, c, P, b, shuffle=shuffle)
         got = resolve_sample_choice(plan, near)
@@ -81,15 +81,15 @@ def test_planner_equals_the_per_frame_form(shuffle):
 
 
 def test_refusals_are_the_references(z):
-    from hvpr_amd import preprocess as PP
     from hvpr_amd.batch_loader import plan_sample_points
+    from oracle import hvpr_oracle as O
     P = int(z["num_sample_points"])
     assert bool(z["raises.more_far_than_p"]) and bool(z["raises.two_n_less_than_p"]) and bool(z["raises.empty_frame"])
     assert not bool(z["raises.control_far_equals_p"]) and not bool(z["raises.control_two_n_equals_p"])
     for n, c in ((P + 11, 10), (P // 2 - 1, P // 2 - 1), (0, 0)):              # the fixture's three frames
         near = np.r_[np.ones((c,), np.uint8), np.zeros((n - c,), np.uint8)]
         with pytest.raises(ValueError):
-            PP.sample_points_choice(near, P, np.random.RandomState(1))
+            O.sample_points_choice(near, P, np.random.RandomState(1))
         with pytest.raises(ValueError):
             plan_sample_points(n, c, P, np.random.RandomState(1))
     plan_sample_points(P + 10, 10, P, np.random.RandomState(1))                 # and its two controls

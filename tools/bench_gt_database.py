@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gt_database_cases as GC  # noqa: E402
 from hvpr_amd import kernels, synthetic  # noqa: E402
-from hvpr_amd.gt_database import DatabaseBuilder, _Chunk  # noqa: E402
+from hvpr_amd.gt_database import DatabaseBuilder, StagedChunk  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12           # MI355X peak
 
@@ -92,7 +92,7 @@ def main():
     for c0 in range(0, a.frames, a.frames_per_call):
         part = infos[c0: c0 + a.frames_per_call]
         pts = [torch.from_numpy(clouds[i["point_cloud"]["lidar_idx"]]).to(dev) for i in part]
-        chunks.append(_Chunk(pts, [i["annos"]["gt_boxes_lidar"] for i in part], dev, [None]))      # a staging buffer each: they stay
+        chunks.append(StagedChunk(pts, [i["annos"]["gt_boxes_lidar"] for i in part], dev, centres=True))  # a staging buffer each: they stay
     arena = torch.empty((len(want) + 16, F), dtype=torch.float32, device=dev)
     count_host = torch.empty((a.frames * a.boxes,), dtype=torch.int32).pin_memory()
     ws = None
@@ -104,7 +104,7 @@ def main():
         e[0].record()
         for j, ch in enumerate(chunks):
             e[2 + 4 * j].record()
-            cnt, ws = ch.count(ws)
+            cnt, _, ws = ch.count(ws)
             e[3 + 4 * j].record()
             ch_host = count_host[k: k + ch.n_obj]
             ch_host.copy_(cnt)                                                # the one read of the chunk

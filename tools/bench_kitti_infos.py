@@ -29,7 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gt_database_cases as GC  # noqa: E402
 import kitti_infos_cases as KC  # noqa: E402
 from hvpr_amd import kernels, synthetic  # noqa: E402
-from hvpr_amd.kitti_dataset import InfoCounter, _InfoChunk  # noqa: E402
+from hvpr_amd.gt_database import StagedChunk  # noqa: E402
+from hvpr_amd.kitti_dataset import InfoCounter  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12           # MI355X peak
 
@@ -86,8 +87,8 @@ def main():
     chunks = []
     for c0 in range(0, a.frames, per):
         part = frames[c0: c0 + per]
-        chunks.append(_InfoChunk([torch.from_numpy(f["points"]).to(dev) for f in part], [f["boxes"] for f in part],
-                                 [f["calib"] for f in part], [f["image_shape"] for f in part], dev, [None]))   # a staging buffer each
+        chunks.append(StagedChunk([torch.from_numpy(f["points"]).to(dev) for f in part], [f["boxes"] for f in part], dev,
+                                  calibs=[f["calib"] for f in part], image_shapes=[f["image_shape"] for f in part]))   # a staging buffer each
     count_host = torch.empty((a.frames * a.boxes,), dtype=torch.int32).pin_memory()
     ws = None
     ev = lambda: torch.cuda.Event(enable_timing=True)
