@@ -99,6 +99,8 @@ int hvpr_voxelize_f32(const float *points, int n_points, int point_stride, int x
  *     ws0 [16,5] bs0 [16], ws1 [32,16] bs1 [32]: the folded scale-stream layers.
  *     pillar_features [M,64], pillar_scale_features [M,32], pillar_mask [M,P] (may be NULL) f32 out.
  *     m_device: optional device i32 holding the live row count (<= M); NULL means M rows.
+ *     A row with num_points == 0 is unspecified (the reference divides by zero) but reads and writes only its own cells; a
+ *     count above P is taken as P, a negative one as 0.
  * ------------------------------------------------------------------------------------------- */
 int hvpr_pillar_vfe_fwd_f32(const float *voxels, const int32_t *num_points, const int32_t *coords, int M, int P,
                             const int32_t *m_device, float vs_x, float vs_y, float vs_z, float off_x, float off_y,
